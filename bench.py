@@ -23,10 +23,13 @@ synchronous step, the meta-gradient summed over the ranks, one Adam step per N s
 -- measured AUC deviations of 0.01-0.2 from the sequential run (profiles/round2_dp_auc_study.jsonl), outside the +-0.002
 bar -- so it is an opt-in extension (`--dp-extra`: the `minibatch_dp` block).
 
-Prints ONE JSON line on rank 0.  Extra keys: steady_state (>= 50 whole epochs of the same model in the
-same run: what a training run of many epochs sees, whatever --steps was), roofline (dominant kernel =
-the score pass, timed live with events on the launch stream), cpu_baseline (the oracle's train loop on
-this box's host cores, bounded sample), eval slides/sec.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times exactly --steps steps and prints the headline
+(`value`, `ms_per_step`); `--dump-outputs DIR` writes what the timed path left after its last step (the meta-learner's
+parameters and Adam moments, the losses of the last pass) as DIR/<name>.npy.  `--full` adds everything else, each
+block in runs of its own after the headline: steady_state (>= 50 whole epochs of the same model in the same run: what
+a training run of many epochs sees, whatever --steps was), roofline (dominant kernel = the score pass, timed live
+with events on the launch stream), cpu_baseline (the oracle's train loop on the host cores, bounded sample), eval
+slides/sec, and the extra blocks (16-bit storage, packed / batched runs, cached statistics, other multi-GPU modes).
 """
 import argparse
 import gc
@@ -72,6 +75,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=1600)
     ap.add_argument("--warmup", type=int, default=160)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: steady state, roofline, evaluation, CPU baseline and "
+                         "the extra blocks (a plain run times the --steps steps and nothing else; the --no-* / extra-block "
+                         "options below take effect with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (parameters and Adam moments after the last step, "
+                         "losses of the last pass) as DIR/<name>.npy, float32")
     ap.add_argument("--dtype", default="fp32", choices=["bf16", "fp16", "fp32"],
                     help="bag STORAGE type; arithmetic is always fp32.  fp32 (default) is the storage of the reference's h5 "
                          "embeddings and the one pinned end to end to the reference's main(); 16-bit storage moves the trained "
@@ -197,6 +207,7 @@ def main():
     a = parse()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(a)                      # does not return
+    import numpy as np
     import torch
     # stdout carries the ONE JSON line and nothing else: whatever libraries print there (librccl announces its
     # path on stdout when a communicator is created) goes to stderr instead
@@ -365,9 +376,25 @@ def main():
         dist.all_reduce(hi, op=dist.ReduceOp.MAX)
         return bool(torch.equal(lo, hi)) and int(hi[2].item()) == 0
 
-    def measure(mode, n_steps, n_warm, steady_epochs, store=store):
-        """-> dict(value, dt, steady, loop, exchange, fallback) for one scaling mode.  The timed region is EXACTLY
-        n_steps steps between two fences, after n_warm untimed steps of the same model."""
+    def step_outputs(model, opt, mode, m):
+        """What a caller of the train loop holds after the last timed step, as float32 host arrays: the meta-learner's
+        parameters and both Adam moments, and the per-slide losses of the last pass (m steps, in visit order; the
+        data-parallel modes keep no per-step losses of their own)."""
+        out = {}
+        for name, p in model.named_parameters():
+            st = opt.state[p]
+            out[f"param.{name}"], out[f"adam_exp_avg.{name}"], out[f"adam_exp_avg_sq.{name}"] = p.detach(), st["exp_avg"], st["exp_avg_sq"]
+        if not mode.startswith("dp"):
+            last = mdist.train_seq.last if mode == "seq" else M.train.last
+            out["loss_last_pass"] = last[0].meta_ws()[0]["loss"][:m]
+        return {k: v.to(torch.float32).cpu().numpy() for k, v in out.items()}
+
+    def measure(mode, n_steps, n_warm, steady_epochs, store=store, as_if_followed=False, dump=False):
+        """-> dict(value, dt, steady, loop, exchange, fallback, outputs) for one scaling mode.  The timed region is EXACTLY
+        n_steps steps between two fences, after n_warm untimed steps of the same model.  as_if_followed: with no steady
+        block, the region still announces the spacer and a whole epoch after it, as when the steady block follows (the
+        work issued ahead for them completes inside the region's fence; neither pass runs).  dump: `outputs` holds what
+        the timed steps left, on the host."""
         res = make_split(mode, store)
         model, opt = new_model()
         loop = Loop(res, model, opt, mode)
@@ -379,8 +406,9 @@ def main():
         # contains the phase A of whatever pass follows it -- so a pass as long as the region's last one follows it (the
         # `spacer`, untimed): the region then issues phase A for exactly as many slides as it consumes, as every pass of
         # a long run does.  (Before: the 32-slide phase A of the steady block trailed a 20-step region.)
-        spacer = [timed[-1]] if steady else []
-        loop.allocate(warm + timed + steady)
+        spacer = [timed[-1]] if steady or as_if_followed else []
+        after = steady or ([loop.per_pass] if as_if_followed else [])      # pass lengths after the spacer
+        loop.allocate(warm + timed + after)
         fallback = None
 
         def prime():
@@ -393,7 +421,7 @@ def main():
             saved = [p.detach().clone() for p in params]
             tmp = Loop(res, model, opt, mode)
             seq = []
-            for m in sorted(set(warm + timed + steady), reverse=True):
+            for m in sorted(set(warm + timed + after), reverse=True):
                 seq += [m] * (4 if m == loop.per_pass else 2)
             tmp.run(seq + [loop.per_pass], then=(warm + timed)[0])
             torch.cuda.synchronize()
@@ -412,7 +440,7 @@ def main():
         # measured 23 k instead of 29 k -- and switched off until the regions are over.)
         gc.collect()
         gc.disable()
-        after_timed = (spacer + steady + [None, None])[:2]
+        after_timed = (spacer + after + [None, None])[:2]
         prime()
         loop.run(warm, then=timed[0], then2=(timed + after_timed)[1])
         fence()
@@ -442,6 +470,7 @@ def main():
         loop.run(timed, then=after_timed[0], then2=after_timed[1])
         fence()
         dt = max_over_ranks(time.perf_counter() - t0)
+        outputs = step_outputs(model, opt, mode, timed[-1]) if dump else None
         if TRACE:
             st = fence.stamps
             fence.stamps = None
@@ -456,7 +485,7 @@ def main():
         ev = list(engine.SCORE_EVENTS) if engine.SCORE_EVENTS is not None else []
         assert mode == "replicas" or ranks_agree(model), "data-parallel ranks ended the timed region with different parameters"
         out = {"value": n_steps * units / dt, "dt": dt, "loop": loop, "exchange": exchange, "fallback": fallback,
-               "events": ev, "steady": None, "res": res, "model": model}
+               "events": ev, "steady": None, "res": res, "model": model, "outputs": outputs}
         if steady:
             # the same model keeps training: whole epochs only, the pass-ahead pipeline in its periodic state
             engine_events, engine.SCORE_EVENTS = engine.SCORE_EVENTS, None
@@ -486,14 +515,22 @@ def main():
             mdist.shutdown()
             dist.destroy_process_group()
         return
-    engine.SCORE_EVENTS = []          # (start, stop, algorithmic bytes) per score-pass launch
+    # (start, stop, algorithmic bytes) per score-pass launch: the roofline of a --full run
+    engine.SCORE_EVENTS = [] if a.full else None
     if world == 1:
         main_mode = "dp_weak" if a.force_dp else "seq" if a.force_seq else "single"
     else:
         main_mode = "replicas" if a.train_mode == "runs" else "seq" if a.train_mode == "seq" else "dp_" + a.scaling
-    r = measure(main_mode, a.steps, a.warmup, 0 if a.no_steady else a.steady_epochs)
+    r = measure(main_mode, a.steps, a.warmup, 0 if a.no_steady or not a.full else a.steady_epochs,
+                as_if_followed=not a.full, dump=a.dump_outputs is not None)
     value, dt, loop, exchange = r["value"], r["dt"], r["loop"], r["exchange"]
     res, model = r["res"], r["model"]
+    if a.dump_outputs is not None and rank == 0:
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        assert sum(v.nbytes for v in r["outputs"].values()) <= 64 << 20, "outputs above 64 MB"
+        for name, v in r["outputs"].items():
+            np.save(os.path.join(a.dump_outputs, name + ".npy"), v)
+        r["outputs"] = None
 
     # ---- roofline of the dominant kernel (score pass), from live HIP events on the launch stream that carry the
     # kernel's own start / end stamps (moc_scores_timed: hipExtLaunchKernel), so that the duration is the one rocprofv3
@@ -582,7 +619,7 @@ def main():
     # ---- the same loop on 16-bit copies of the bags (N = 1, default fp32 run): BASELINE configs[1] names bf16 storage,
     # but the trained AUC does not stay within +-0.002 of the fp32 reference there, so it is an extra block, not `value`
     half_block = None
-    if world == 1 and a.dtype == "fp32" and main_mode == "single" and not a.no_16bit_extra:
+    if a.full and world == 1 and a.dtype == "fp32" and main_mode == "single" and not a.no_16bit_extra:
         try:
             ev_keep, engine.SCORE_EVENTS = engine.SCORE_EVENTS, None
             rh = measure("single", a.steps, a.warmup, 0 if a.no_steady else min(20, a.steady_epochs), store=torch.bfloat16)
@@ -603,7 +640,7 @@ def main():
     # ---- the modes that are not `value`, from shorter runs of this process, as extra keys (N > 1 only)
     extras = {}
     seq_block = None
-    if world > 1 and main_mode == "replicas" and a.seq_extra:
+    if a.full and world > 1 and main_mode == "replicas" and a.seq_extra:
         try:
             k2 = max(a.slides, min(a.steps, 10 * a.slides))
             r2 = measure("seq", k2, min(a.warmup, a.slides), 0)
@@ -614,7 +651,7 @@ def main():
             r2["loop"] = r2["res"] = None
         except Exception as e:  # noqa: BLE001 -- an extra block must not cost the line its `value`
             seq_block = {"error": f"{type(e).__name__}: {e}"[:300]}
-    if world > 1 and (main_mode.startswith("dp") or a.dp_extra):
+    if a.full and world > 1 and (main_mode.startswith("dp") or a.dp_extra):
         del res, loop
         r["res"] = r["loop"] = None
         todo = [m for m in ("dp_strong", "dp_weak") if m != main_mode and not (m == "dp_strong" and a.slides % world)]
@@ -636,7 +673,7 @@ def main():
     # ---- N independent runs, one per GPU, no communication at all: how the reference itself uses several GPUs
     # (scripts/moc_train.sh gives every fold x shot its own process and GPU) -- every run the reference's trajectory
     replicas = None
-    if world > 1 and not a.no_replicas and main_mode != "replicas":
+    if a.full and world > 1 and not a.no_replicas and main_mode != "replicas":
         try:
             k3 = max(a.slides, min(a.steps, 10 * a.slides))
             r3 = measure("replicas", k3, min(a.warmup, a.slides), 0)
@@ -650,7 +687,7 @@ def main():
 
     # ---- evaluation throughput (slides/sec), batched end to end; slides sharded over the ranks, no data-path collective
     eval_rate = None
-    if not a.no_eval:
+    if a.full and not a.no_eval:
         n_eval = a.eval_slides
         ids = list(range(rank, n_eval, world))
         esizes = synth.bag_sizes(7, n_eval, a.patches, fixed=not a.lognormal)
@@ -677,7 +714,7 @@ def main():
 
     # ---- several independent runs side by side on this ONE GPU (separate processes; nothing of this process runs meanwhile)
     packed = None
-    if world == 1 and a.packed_runs > 1 and not (a.force_dp or a.force_seq):
+    if a.full and world == 1 and a.packed_runs > 1 and not (a.force_dp or a.force_seq):
         torch.cuda.synchronize()
         k3 = 20 * a.slides                      # its own length, whatever --steps is: the block states it (steps_per_run)
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(a.packed_runs), "--replicas-only", "--steps", str(k3),
@@ -744,7 +781,7 @@ def main():
                 M._run_sets.clear()
                 return {"error": f"{type(e).__name__}: {e}"[:300]}
 
-    if world == 1 and a.batched_runs not in ("", "0") and not a.replicas_only and not (a.force_dp or a.force_seq):
+    if a.full and world == 1 and a.batched_runs not in ("", "0") and not a.replicas_only and not (a.force_dp or a.force_seq):
         batched = {}
         for R_ in [int(v) for v in a.batched_runs.split(",") if int(v) > 1]:
             batched[f"runs_{R_}"] = run_batched(R_)
@@ -756,7 +793,7 @@ def main():
     # ---- opt-in: the per-row statistics kept from ONE score pass (ResidentBags(cache_scores=True)): no score pass per epoch.
     # NOT `value` -- its score pass reads the bags every pass, as the reference recomputes them -- an extra block
     cached_block = None
-    if world == 1 and main_mode == "single" and not a.no_cached_extra and not a.replicas_only:
+    if a.full and world == 1 and main_mode == "single" and not a.no_cached_extra and not a.replicas_only:
         try:
             ev_keep, engine.SCORE_EVENTS = engine.SCORE_EVENTS, None
             keep_env = os.environ.get("MOC_CACHE_SCORES")
@@ -786,7 +823,7 @@ def main():
     # ---- CPU baseline: the oracle's train loop AND evaluation loop on the host cores (rank 0, N=1 only), a bounded
     # sample of the same workload (slide-granular: wide configurations do not get through an epoch in the budget)
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu and isinstance(res, M.ResidentBags):
+    if a.full and rank == 0 and world == 1 and not a.no_cpu and isinstance(res, M.ResidentBags):
         import torch.nn.functional as F
         from oracle import moc_oracle as O
         labels = res.labels

@@ -1,5 +1,6 @@
 """bench.py as the driver runs it, on the GPU box: the one-GPU line carries what the contract asks for (value over
-exactly --steps steps, a steady_state block, roofline measured live, traffic null or matched), and `--gpus 2` starts
+exactly --steps steps; with --full a steady_state block, roofline measured live, traffic null or matched), a plain line
+that is the headline alone and dumps what its timed steps computed, and `--gpus 2` starts
 its own ranks -- rehearsed with both ranks on the one card (MOC_BENCH_ONE_DEVICE=1, gloo): runs x GPUs is `value`, the
 exact-sequential mode and minibatch data parallelism extra blocks (their ranks end with bit-identical parameters:
 bench.py asserts that itself)."""
@@ -8,6 +9,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -25,7 +27,7 @@ def _bench(*args, env=None, timeout=600):
 
 
 def test_one_gpu_line(gpu_device):
-    d = _bench("--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-seconds", "2", "--steady-epochs", "10", "--packed-runs", "2",
+    d = _bench("--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--cpu-seconds", "2", "--steady-epochs", "10", "--packed-runs", "2",
                "--batched-runs", "2")
     assert d["n_gpus"] == 1 and d["steps"] == 20 and d["warmup"] == 5 and d["unit"] == "meta-steps/s"
     assert d["value"] > 5000 and abs(d["ms_per_step"] * d["value"] - 1000.0) < 1.0
@@ -56,10 +58,33 @@ def test_one_gpu_line(gpu_device):
     assert pk["runs"] == 2 and pk["value"] > 5000 and "vs_one_run" in pk      # two independent runs on the one GPU, timed together
 
 
+def test_plain_line_is_the_headline_alone_and_dumps_what_its_steps_computed(gpu_device, tmp_path):
+    """A plain run times the --steps steps and nothing else (no steady state, roofline, evaluation, CPU baseline or extra
+    block); --dump-outputs writes what they left -- the same bits in a second plain run and in a --full run with the
+    same arguments (its timed region runs the same passes, the score pass under events)."""
+    def outputs(tag, *extra):
+        d = _bench("--gpus", "1", "--steps", "20", "--warmup", "5", "--dump-outputs", str(tmp_path / tag), *extra)
+        return d, {f.name: np.load(f) for f in sorted((tmp_path / tag).iterdir())}
+
+    d, a = outputs("a")
+    assert d["steps"] == 20 and d["warmup"] == 5 and d["unit"] == "meta-steps/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and d["value"] > 5000 and abs(d["ms_per_step"] * d["value"] - 1000.0) < 1.0
+    assert d["steady_state"] is None and d["roofline"] is None and d["cpu_baseline"] is None and d["eval_slides_per_sec"] is None
+    assert not {"bf16_storage", "packed_runs", "batched_runs", "cached_scores"} & set(d)
+    assert len(a) == 13 and a["loss_last_pass.npy"].shape == (20,)        # 4 parameters x (value, 2 Adam moments) + losses
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values())
+    _, b = outputs("b")
+    d_full, c = outputs("c", "--full", "--no-cpu", "--no-eval", "--no-16bit-extra", "--packed-runs", "0", "--batched-runs", "0",
+                        "--no-cached-extra", "--steady-epochs", "2")
+    assert d_full["steady_state"]["epochs"] == 2 and d_full["roofline"] is not None
+    for other in (b, c):
+        assert other.keys() == a.keys() and all(np.array_equal(a[k], other[k]) for k in a)
+
+
 def test_gpus_2_starts_its_own_ranks_and_reports_runs_x_gpus(gpu_device):
     """N > 1: `value` is runs x GPUs (one independent run per rank, nothing exchanged, scaling weak); the exact-sequential
     mode of ONE run over the ranks and minibatch data parallelism are opt-in extra blocks."""
-    d = _bench("--gpus", "2", "--steps", "32", "--warmup", "32", "--no-eval", "--steady-epochs", "2", "--dp-exchange", "auto", "--dp-extra",
+    d = _bench("--gpus", "2", "--steps", "32", "--warmup", "32", "--full", "--no-eval", "--steady-epochs", "2", "--dp-exchange", "auto", "--dp-extra",
                "--seq-extra", "--batched-runs", "0",
                env={"MOC_BENCH_ONE_DEVICE": "1"})
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["value"] > 100
@@ -74,7 +99,7 @@ def test_gpus_2_starts_its_own_ranks_and_reports_runs_x_gpus(gpu_device):
 
 
 def test_gpus_2_train_mode_seq_is_still_there(gpu_device):
-    d = _bench("--gpus", "2", "--steps", "32", "--warmup", "32", "--no-eval", "--steady-epochs", "2", "--train-mode", "seq", "--batched-runs", "0",
+    d = _bench("--gpus", "2", "--steps", "32", "--warmup", "32", "--full", "--no-eval", "--steady-epochs", "2", "--train-mode", "seq", "--batched-runs", "0",
                env={"MOC_BENCH_ONE_DEVICE": "1"})
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["config"]["parallelism"].startswith("seq2: exact-sequential")
     rep = d["replicas"]
