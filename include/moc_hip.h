@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define MOC_ABI_VERSION 18
+#define MOC_ABI_VERSION 19
 
 enum { MOC_TICKET_QUEUES = 64, MOC_TICKET_STRIDE = 64,     /* moc_batch_t.tile_ticket: counters, int32 words between them */
        MOC_TICKET_WORDS = (64 + 8) * 64 };
@@ -145,7 +145,8 @@ typedef struct moc_meta {
     float *v_W1, *v_b1, *v_W2, *v_b2; /* exp_avg_sq                                        */
     float *g_W1, *g_b1, *g_W2, *g_b2; /* gradient outputs (moc_train_grad), may be NULL    */
     void  *W1_image;                  /* device scratch, moc_w1_image_bytes(D, dtype): W1 re-laid in
-                                         MFMA operand order for the forward pass.  Derived data the
+                                         MFMA operand order for the forward pass, three 16-bit terms
+                                         per weight for every storage (ABI 19).  Derived data the
                                          library rebuilds / keeps in sync itself; contents need not
                                          survive between calls.                                */
     double lr, beta1, beta2, eps, weight_decay; /* the optimizer's Python floats, unrounded     */

@@ -227,9 +227,9 @@ __device__ __forceinline__ void cand_class_scores(const FwdArgs& a, const float*
 // a wave's fragment load touches 64 scattered 16-B pieces (16 rows 2 KB apart) and the address
 // unit, not HBM, sets the pace.  So the kernels keep a second copy in fragment order -- one
 // contiguous 1 KiB per wave-load -- rewritten by the W1 update itself, hence always in sync:
-//   bf16 bags: [nt][kk][term][lane][8] bf16, element j of lane l = term t of W1[nt*16 + (l&15)][kk*32 + (l>>4)*8 + j]
-//              (hi/mid/lo split, 24 mantissa bits: bf16 MFMA with fp32-exact products)
-//   fp32 bags: [nt][kq][lane][4] f32,         element m of lane l = W1[nt*16 + (l&15)][kq*16 + (l>>4)*4 + m]
+//   bf16 and fp32 bags: [nt][kk][term][lane][8] bf16, element j of lane l = term t of W1[nt*16 + (l&15)][kk*32 + (l>>4)*8 + j]
+//              (hi/mid/lo split, 24 mantissa bits: bf16 MFMA with fp32-exact products; fp32 bags split their rows
+//              the same way, fwd_split4 / fwd_mfma6 below)
 //   fp16 bags: as bf16, the three fp16 terms of W1 * 2^10 (moc_common.h); the forward scales back
 template <bool F16>
 __device__ __forceinline__ void w1_image_store_half(unsigned char* img, int D, int h, int d, float w) {
@@ -246,9 +246,7 @@ __device__ __forceinline__ void w1_image_store_bf16(unsigned char* img, int D, i
     w1_image_store_half<false>(img, D, h, d, w);
 }
 __device__ __forceinline__ void w1_image_store_f32(unsigned char* img, int D, int h, int d, float w) {
-    const int KQ = D / 16;
-    const int nt = h >> 4, kq = d >> 4, lane = (((d & 15) >> 2) << 4) | (h & 15), m = d & 3;
-    reinterpret_cast<float*>(img)[((size_t)(nt * KQ + kq) * 64 + lane) * 4 + m] = w;
+    w1_image_store_half<false>(img, D, h, d, w);            // the bf16 bags' image: fp32 rows are split into bf16 terms too
 }
 // storage code (MOC_F32 / MOC_BF16 / MOC_F16) known at run time
 __device__ __forceinline__ void w1_image_store(int dt, unsigned char* img, int D, int h, int d, float w) {
@@ -261,6 +259,48 @@ __global__ __launch_bounds__(256) void w1_image_kernel(const float* W1, int D, u
     const int e = blockIdx.x * 256 + threadIdx.x;       // grid = (H*D/256, runs)
     const int h = e / D, d = e - h * D;
     w1_image_store(dt, img + (int64_t)blockIdx.y * img_stride, D, h, d, W1[(int64_t)blockIdx.y * par_stride + e]);
+}
+
+// ---- fp32 bags on the bf16 matrix cores ------------------------------------------------------------------------------
+// fp32 has no fast matrix path on gfx950 (v_mfma_f32_16x16x4_f32: 32 cycles per 16x16x4, 1/16 of the bf16 rate).  So a
+// row value x and a weight w are each held as three bf16 terms -- x == x0 + x1 + x2 exactly (the truncating split below:
+// 8 + 8 + 8 significant bits), w == w0 + w1 + w2 exactly (moc_split3<false>, the W1 image) -- and the six products
+// x_i w_j with i + j <= 2, each exact in fp32, go through v_mfma_f32_16x16x32_bf16 (16 cycles per 16x16x32).  The three
+// dropped products are below 2^-16 of the leading one (2^-24 relative to x w, the size of one fp32 rounding).
+// The split of four fp32 values into three bf16 terms each, packed two per dword in operand order (element 0 low):
+// x0 = x with the low 16 bits cleared, r = x - x0 (exact), x1 = r truncated the same way, x2 = r - x1 (exact, <= 8 bits).
+// v_perm_b32 selector 0x07060302: the upper halves of (odd, even) side by side.
+__device__ __forceinline__ void fwd_split4(const uint4& v, uint2 (&o)[3]) {
+    const unsigned e[4] = {v.x, v.y, v.z, v.w};
+    unsigned m[4], l[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float r = moc_fsub(__uint_as_float(e[i]), __uint_as_float(e[i] & 0xFFFF0000u));
+        m[i] = __float_as_uint(r);
+        l[i] = __float_as_uint(moc_fsub(r, __uint_as_float(m[i] & 0xFFFF0000u)));
+    }
+    o[0] = make_uint2(__builtin_amdgcn_perm(e[1], e[0], 0x07060302u), __builtin_amdgcn_perm(e[3], e[2], 0x07060302u));
+    o[1] = make_uint2(__builtin_amdgcn_perm(m[1], m[0], 0x07060302u), __builtin_amdgcn_perm(m[3], m[2], 0x07060302u));
+    o[2] = make_uint2(__builtin_amdgcn_perm(l[1], l[0], 0x07060302u), __builtin_amdgcn_perm(l[3], l[2], 0x07060302u));
+}
+// eight fp32 values (an A fragment of one k-step of 32 columns, in two 16-byte pieces) -> its three bf16 terms
+__device__ __forceinline__ void fwd_split8(const uint4& p0, const uint4& p1, uint4 (&o)[3]) {
+    uint2 a[3], b[3];
+    fwd_split4(p0, a);
+    fwd_split4(p1, b);
+#pragma unroll
+    for (int t = 0; t < 3; ++t) o[t] = make_uint4(a[t].x, a[t].y, b[t].x, b[t].y);
+}
+// one k-step of 32 columns: the six products of x's terms (A) and W1's terms (B, the image's hi, mid, lo), smallest first --
+// x2 w0, x1 w1, x0 w2, x1 w0, x0 w1, x0 w0 -- into one fp32 accumulator.  Every fp32-bag forward multiplies through this
+// routine, k-steps in ascending order: the same bits from each of them.
+template <typename W>
+__device__ __forceinline__ f32x4_t fwd_mfma6(const uint4 (&x)[3], const W& w0, const W& w1, const W& w2, f32x4_t acc) {
+#define MOC_MF6(X, Wt) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, X), __builtin_bit_cast(bf16x8_t, Wt), acc, 0, 0, 0)
+    MOC_MF6(x[2], w0); MOC_MF6(x[1], w1); MOC_MF6(x[0], w2);
+    MOC_MF6(x[1], w0); MOC_MF6(x[0], w1); MOC_MF6(x[0], w0);
+#undef MOC_MF6
+    return acc;
 }
 
 // fp32 bags: one quarter's chain joins the running sum (first quarter: taken as it is), the chain starts over
@@ -276,8 +316,9 @@ __device__ __forceinline__ void fwd_fold_quarter(f32x4_t& tot, f32x4_t& acc, boo
 // TILES: the tile-record variant (training step over tile records, batched runs); without it the kernel is the round-3 code --
 // the extra live values cost this 256-register kernel 4.6 us at thirty classes when they were unconditional
 template <bool BF16, bool F16 = false, bool TILES = false>
-__global__ __launch_bounds__(256) void meta_forward_kernel(FwdArgs a) {
-    __shared__ __attribute__((aligned(16))) uint4 xt[16 * 64];     // 16 rows x 1 KiB, chunk-swizzled
+__global__ __launch_bounds__(256, BF16 ? 1 : 3) void meta_forward_kernel(FwdArgs a) {
+    // 16 rows x 1 KiB, chunk-swizzled; fp32 bags: the unit's three bf16 term planes, [3][16 rows][32 chunks]
+    __shared__ __attribute__((aligned(16))) uint4 xt[BF16 ? 16 * 64 : 3 * 16 * 32];
     __shared__ float Hs[16][H + 1];
     __shared__ float Gs[16][4];
     __shared__ float W2s[4 * H];
@@ -332,7 +373,7 @@ __global__ __launch_bounds__(256) void meta_forward_kernel(FwdArgs a) {
     // fp32 bags: the sum over D is formed as ((p0 + p1) + p2) + p3, p_q = the MFMA chain over the q-th quarter of the
     // columns -- the association of meta_forward_ksplit_kernel, which runs the four chains side by side (same bits)
     f32x4_t tot = {0.f, 0.f, 0.f, 0.f};
-    const int QS = a.D / 64;                                      // k-steps of 16 columns per quarter
+    const int QS = a.D / 128;                                     // fp32 bags: k-steps of 32 columns per quarter
     int qc = 0, qi = 0;
     for (int u = 0; u < U; ++u) {
         if (u > 0) __syncthreads();                               // every wave is done reading the previous tile
@@ -364,27 +405,32 @@ __global__ __launch_bounds__(256) void meta_forward_kernel(FwdArgs a) {
                 }
             }
         } else {
-            uint4 wv[16];
-            const uint4* wi = reinterpret_cast<const uint4*>(fr.W1img) + ((size_t)wave * KST + (size_t)u * ksteps) * 64 + lane;
+            // fp32 bags: the three-term image (8 or 4 k-steps of 32 columns per unit); the fetching wave splits its rows
+            // into bf16 terms once (fwd_split4: piece c of a row is half c & 1 of term chunk c >> 1), the six products by
+            // fwd_mfma6 -- the sixteen-wave kernel's products in its order
+            const int ks32 = UB / 128;
+            uint4 wv[8 * 3];
+            const uint4* wi = reinterpret_cast<const uint4*>(fr.W1img) + ((size_t)wave * (a.D / 32) + (size_t)u * ks32) * 3 * 64 + lane;
 #pragma unroll
-            for (int q = 0; q < 16; ++q) if (q < ksteps) wv[q] = wi[q * 64];
+            for (int q = 0; q < 8 * 3; ++q) if (q < ks32 * 3) wv[q] = wi[q * 64];
             if (lane < cpr) {
+                uint2* xt2 = reinterpret_cast<uint2*>(xt);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const int r = wave * 4 + i;
-                    xt[r * 64 + (lane ^ (r & 15))] = xv[i];
+                    uint2 tv[3];
+                    fwd_split4(xv[i], tv);
+#pragma unroll
+                    for (int p = 0; p < 3; ++p) xt2[((p * 16 + r) * 32 + ((lane >> 1) ^ r)) * 2 + (lane & 1)] = tv[p];
                 }
             }
             __syncthreads();
 #pragma unroll
-            for (int kq = 0; kq < 16; ++kq) {
-                if (kq < ksteps) {
-                    const int r = lane & 15;
-                    const uint4 xa = xt[r * 64 + ((kq * 4 + (lane >> 4)) ^ r)];
-                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(xa.x), __uint_as_float(wv[kq].x), acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(xa.y), __uint_as_float(wv[kq].y), acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(xa.z), __uint_as_float(wv[kq].z), acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(xa.w), __uint_as_float(wv[kq].w), acc, 0, 0, 0);
+            for (int kk = 0; kk < 8; ++kk) {
+                if (kk < ks32) {
+                    const int r = lane & 15, c = (kk * 4 + (lane >> 4)) ^ r;
+                    const uint4 xa[3] = {xt[r * 32 + c], xt[(16 + r) * 32 + c], xt[(32 + r) * 32 + c]};
+                    acc = fwd_mfma6(xa, wv[kk * 3], wv[kk * 3 + 1], wv[kk * 3 + 2], acc);
                     if (++qc == QS) {
                         qc = 0;
                         fwd_fold_quarter(tot, acc, qi++ == 0);
@@ -455,18 +501,20 @@ __global__ __launch_bounds__(256) void meta_forward_kernel(FwdArgs a) {
 }
 
 // ---- one slide, fp32 bags (the training step of the default storage): the columns split over four wave groups ------
-// meta_forward_kernel<false> is a chain of D/4 v_mfma_f32_16x16x4_f32 per wave (128 x 32 cycles = 1.7 us at D = 512, with
+// (round 3, when fp32 products ran on v_mfma_f32_16x16x4_f32) meta_forward_kernel<false> is a chain of D/4 v_mfma_f32_16x16x4_f32 per wave (128 x 32 cycles = 1.7 us at D = 512, with
 // three of every four SIMD cycles idle: one wave per SIMD) behind TWO dependent rounds of row loads (2-KiB rows in two
 // 1-KiB units, the second requested after the first has been multiplied) -- 5.5 us from kernel start to the last MFMA
 // against 3.2 us for bf16 bags (phase stamps, profiles/NOTES.md round 3).  Here a workgroup is 16 waves: wave w holds
 // hidden units 16 (w & 3) .. +15 and the (w >> 2)-th QUARTER of the columns, so that the four chains of a hidden tile run
 // side by side on the four waves of a SIMD (32 MFMAs each), every row is requested whole at once (wave w fetches row w:
 // D / 256 sixteen-byte loads per lane, one wave-uniform row id), and the four partial tiles meet in LDS as
-// ((p0 + p1) + p2) + p3 -- the association the 16- and 128-row kernels keep for fp32 bags, hence the same bits.
+// ((p0 + p1) + p2) + p3 -- the association the 16- and 128-row kernels keep for fp32 bags, hence the same bits.  The products
+// run on the bf16 matrix cores (fwd_split4 / fwd_mfma6): per wave D / 128 k-steps x six v_mfma_f32_16x16x32_bf16 (24 x 16
+// cycles at D = 512 instead of 32 x 32), the row split once by the wave that fetches it, the tile in LDS as three bf16 planes.
 // grid (ceil(S_bound/16), n), 1024 threads; D <= 1024.
 constexpr int FKS_PSTR = H + 4;                             // row stride of a partial tile in LDS (floats)
 __host__ __device__ constexpr int fks_lds_bytes(int D) {
-    return 16 * D * 4 + 4 * 16 * FKS_PSTR * 4 + 16 * (H + 1) * 4 + 16 * 4 * 4 + 4 * H * 4;
+    return 3 * 16 * D * 2 + 4 * 16 * FKS_PSTR * 4 + 16 * (H + 1) * 4 + 16 * 4 * 4 + 4 * H * 4;
 }
 // DQ = D / 256: every loop over a row's pieces or a quarter's fragments has a compile-time trip count.  STATS: the candidate
 // scores come from the score pass's statistics through sel_idx (cand_mode != 0: evaluation of a few slides); the training
@@ -475,8 +523,8 @@ template <int DQ, bool STATS>
 __global__ __launch_bounds__(1024) void meta_forward_ksplit_kernel(FwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int D = DQ * 256;
-    uint4* xt = reinterpret_cast<uint4*>(smem);                                     // [16][D/4] chunks, swizzled
-    float* part = reinterpret_cast<float*>(smem + (size_t)16 * D * 4);              // [4][16][FKS_PSTR]
+    uint4* xt = reinterpret_cast<uint4*>(smem);                                     // [3 terms][16][D/8] chunks, swizzled
+    float* part = reinterpret_cast<float*>(smem + (size_t)3 * 16 * D * 2);          // [4][16][FKS_PSTR]
     float (*Hs)[H + 1] = reinterpret_cast<float (*)[H + 1]>(part + 4 * 16 * FKS_PSTR);
     float (*Gs)[4] = reinterpret_cast<float (*)[4]>(reinterpret_cast<float*>(Hs) + 16 * (H + 1));
     float* W2s = reinterpret_cast<float*>(Gs) + 16 * 4;
@@ -499,21 +547,32 @@ __global__ __launch_bounds__(1024) void meta_forward_ksplit_kernel(FwdArgs a) {
     const int64_t rid = a.sel_row[base + sr];
     const unsigned char* rp = a.X + rid * row_bytes + lane * 16;
     MOC_STAMP_DRAIN(3);
-    // W1 image of (hidden tile, quarter): D / 64 fragments of 1 KiB.  (rid >> 63 is zero: the address is made to depend on
-    // the row id so that hipcc cannot hoist these loads above the row id's wait -- they must queue BEHIND the rows.)
-    constexpr int QS = D / 64;
-    const uint4* wi = reinterpret_cast<const uint4*>(fr.W1img) + ((size_t)ht * (D / 16) + (size_t)kq * QS) * 64 + lane + (rid >> 63);
+    // W1 image of (hidden tile, quarter): D / 128 k-steps x 3 terms, fragments of 1 KiB.  (rid >> 63 is zero: the address is
+    // made to depend on the row id so that hipcc cannot hoist these loads above the row id's wait -- they must queue BEHIND
+    // the rows.)
+    constexpr int QK = D / 128;                              // k-steps of 32 columns per quarter
+    const uint4* wi = reinterpret_cast<const uint4*>(fr.W1img) + ((size_t)ht * (D / 32) + (size_t)kq * QK) * 3 * 64 + lane + (rid >> 63);
     // (the rows first: loads return in issue order, and the tile must be in LDS before the first MFMA, while the image
-    // fragments -- 128 KiB per workgroup through one CU's 64 B/clk -- may keep arriving under the chain)
+    // fragments -- 192 KiB per workgroup through one CU -- may keep arriving under the chain)
     uint4 xv[cpl];
 #pragma unroll
     for (int i = 0; i < cpl; ++i) xv[i] = *reinterpret_cast<const uint4*>(rp + i * 1024);
-    uint4 wv[QS];
+    uint4 wv[QK * 3];
 #pragma unroll
-    for (int q = 0; q < QS; ++q) wv[q] = wi[q * 64];
-    constexpr int cpr = D / 4;                               // chunks per row
+    for (int q = 0; q < QK * 3; ++q) wv[q] = wi[q * 64];
+    // the row goes to LDS once, as its three bf16 terms: plane t = [16 rows][D / 8 chunks of 16 bytes], chunk c of row r at
+    // c ^ r (r < 16) -- the 16-bit-bag tile's layout, so the A-fragment reads below hit distinct banks.  Piece i of this
+    // lane (columns 4 (lane + 64 i) .. +3) is half (lane & 1) of chunk (lane + 64 i) / 2.
+    constexpr int cpr = D / 8;                               // chunks per row and term
+    uint2* xt2 = reinterpret_cast<uint2*>(smem);
 #pragma unroll
-    for (int i = 0; i < cpl; ++i) xt[wave * cpr + ((lane + i * 64) ^ wave)] = xv[i];     // chunk c of row r at c ^ r (r < 16)
+    for (int i = 0; i < cpl; ++i) {
+        uint2 tv[3];
+        fwd_split4(xv[i], tv);
+        const int o = (wave * cpr + (((lane + i * 64) >> 1) ^ wave)) * 2 + (lane & 1);
+#pragma unroll
+        for (int p = 0; p < 3; ++p) xt2[p * 16 * cpr * 2 + o] = tv[p];
+    }
     MOC_STAMP(5);
     __syncthreads();
     MOC_STAMP(6);
@@ -549,14 +608,12 @@ __global__ __launch_bounds__(1024) void meta_forward_ksplit_kernel(FwdArgs a) {
     {
         const int r = lane & 15;
         const uint4* xr = xt + r * cpr;
-        const int c0 = kq * QS * 4 + (lane >> 4);
+        const int c0 = kq * QK * 4 + (lane >> 4);
 #pragma unroll
-        for (int q = 0; q < QS; ++q) {
-            const uint4 xa = xr[(c0 + q * 4) ^ r];
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(xa.x), __uint_as_float(wv[q].x), acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(xa.y), __uint_as_float(wv[q].y), acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(xa.z), __uint_as_float(wv[q].z), acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(xa.w), __uint_as_float(wv[q].w), acc, 0, 0, 0);
+        for (int kk = 0; kk < QK; ++kk) {
+            const int c = (c0 + kk * 4) ^ r;
+            const uint4 xa[3] = {xr[c], xr[16 * cpr + c], xr[32 * cpr + c]};
+            acc = fwd_mfma6(xa, wv[kk * 3], wv[kk * 3 + 1], wv[kk * 3 + 2], acc);
         }
     }
 #ifdef MOC_STAMPS
@@ -776,12 +833,13 @@ __device__ __forceinline__ void fwd_touch4(fu32x4_t (&v)[4]) {
 }
 
 // ST: storage of the bag -- 0 bf16, 1 fp16 (three 16-bit terms of W1 per k-step of 32 columns, v_mfma_f32_16x16x32),
-// 2 fp32 (one fp32 fragment per k-step of 16 columns, four v_mfma_f32_16x16x4_f32)
+// 2 fp32 (the same image; a chunk = two 1-KiB fp32 pieces per row tile = one k-step of 32 columns, split into bf16
+// terms as it is read from LDS: fwd_split8, fwd_mfma6)
 template <int ST>
 __global__ __launch_bounds__(256, f128_wgs(ST)) void meta_forward128_kernel(FwdArgs a) {
     constexpr int F128_KC = f128_kc(ST), F128_BUF = f128_buf(F128_KC), F128_XB = f128_xb(F128_KC);
     constexpr bool F16 = ST == 1;
-    constexpr int PER = ST == 2 ? 1 : 3;                   // W1 fragments per k-step
+    constexpr int WPC = 3 * (ST == 2 ? F128_KC / 2 : F128_KC);      // W1 fragments per chunk (three terms per 32 columns)
     constexpr int ESZ = ST == 2 ? 4 : 2;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float (*Hs)[H + 1] = reinterpret_cast<float (*)[H + 1]>(smem);          // [128][H + 1]: aliases the chunk buffers, after the loop
@@ -839,10 +897,10 @@ __global__ __launch_bounds__(256, f128_wgs(ST)) void meta_forward128_kernel(FwdA
                 __builtin_amdgcn_global_load_lds((gptr_t)(rp[j] + ((int64_t)c * F128_KC + kl) * 64),
                                                  (lptr_t)(dst + ((wave * 2 + j) * F128_KC + kl) * 1024), 16, 0, 0);
     };
-    const fu32x4_t* wimg = reinterpret_cast<const fu32x4_t*>(a.W1img) + (size_t)wave * KK * PER * 64 + lane;
-    auto load_w = [&](int c, fu32x4_t (&wv)[F128_KC * PER]) {
+    const fu32x4_t* wimg = reinterpret_cast<const fu32x4_t*>(a.W1img) + (size_t)wave * (a.D / 32) * 3 * 64 + lane;
+    auto load_w = [&](int c, fu32x4_t (&wv)[WPC]) {
 #pragma unroll
-        for (int q = 0; q < F128_KC * PER; ++q) wv[q] = wimg[((size_t)c * F128_KC * PER + q) * 64];
+        for (int q = 0; q < WPC; ++q) wv[q] = wimg[((size_t)c * WPC + q) * 64];
     };
     f32x4_t acc[8];
 #pragma unroll
@@ -850,10 +908,37 @@ __global__ __launch_bounds__(256, f128_wgs(ST)) void meta_forward128_kernel(FwdA
     f32x4_t tot[ST == 2 ? 8 : 1] = {};                     // fp32 bags: running sum of the column quarters (meta_forward_kernel)
     const int qchunks = nchunk / 4;                        // chunks per quarter (D a multiple of 256)
     const unsigned lds0 = (unsigned)(uintptr_t)smem + lane * 16;
-    auto body = [&](int c, const fu32x4_t (&cur)[F128_KC * PER], fu32x4_t (&nxt)[F128_KC * PER]) {
+    // fp32: lane l's A fragment (columns 8 (l >> 4) .. +7 of the chunk's 32) is pieces 2 ((l >> 4) & 1), +1 of fp32 k-step l >> 5
+    const unsigned lds0f = (unsigned)(uintptr_t)smem + (lane >> 5) * 1024 + ((((lane >> 4) & 1) * 32) + (lane & 15)) * 16;
+    auto body = [&](int c, const fu32x4_t (&cur)[WPC], fu32x4_t (&nxt)[WPC]) {
         if (c + 1 < nchunk) {                              // chunk c + 1: image fragments and rows, all waited for at the barrier
             if (!(diag & 2u)) load_w(c + 1, nxt);
             if (!(diag & 4u)) issue_x(c + 1, (c + 1) & 1);
+        }
+        if constexpr (ST == 2) {
+            // row tile rt: its two fp32 pieces (two ds_read_b128), split, six MFMAs -- no read-ahead: the registers of a
+            // second pair would spill at three workgroups per CU, and the other workgroups' MFMAs cover the LDS latency
+            const unsigned buf = lds0f + (c & 1) * F128_BUF;
+#pragma unroll
+            for (int rt = 0; rt < 8; ++rt) {
+                fu32x4_t P[2];
+                fwd_lds16<0>(P[0], buf + rt * F128_KC * 1024);
+                fwd_lds16<256>(P[1], buf + rt * F128_KC * 1024);
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                asm volatile("" : "+v"(P[0]), "+v"(P[1]));
+                if (!(diag & 1u)) {
+                    uint4 xa[3];
+                    fwd_split8(__builtin_bit_cast(uint4, P[0]), __builtin_bit_cast(uint4, P[1]), xa);
+                    acc[rt] = fwd_mfma6(xa, cur[0], cur[1], cur[2], acc[rt]);
+                }
+            }
+            if ((c + 1) % qchunks == 0) {                  // ((p0 + p1) + p2) + p3 over the quarters of the columns
+                const bool first = c + 1 == qchunks;
+#pragma unroll
+                for (int r = 0; r < 8; ++r) fwd_fold_quarter(tot[r], acc[r], first);
+            }
+            __syncthreads();                               // chunk c + 1 has landed for everybody; this buffer is free
+            return;
         }
         const unsigned buf = lds0 + (c & 1) * F128_BUF;
         // batches of two A fragments (row tiles 2 g, 2 g + 1 at k-step kl), one batch ahead of the six MFMAs that use them
@@ -876,29 +961,14 @@ __global__ __launch_bounds__(256, f128_wgs(ST)) void meta_forward128_kernel(FwdA
             asm volatile("" : "+v"(Ac[0]), "+v"(Ac[1]));
             if (!(diag & 1u)) {
 #pragma unroll
-                for (int r = 0; r < 2; ++r) {
-                    if constexpr (ST == 2) {
+                for (int r = 0; r < 2; ++r)
 #pragma unroll
-                        for (int m = 0; m < 4; ++m)
-                            acc[g * 2 + r] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(Ac[r][m]), __uint_as_float(cur[kl][m]),
-                                                                                  acc[g * 2 + r], 0, 0, 0);
-                    } else {
-#pragma unroll
-                        for (int t = 0; t < 3; ++t) acc[g * 2 + r] = moc_mfma_half<F16>(Ac[r], cur[kl * 3 + t], acc[g * 2 + r]);
-                    }
-                }
-            }
-        }
-        if constexpr (ST == 2) {                           // fp32 bags: ((p0 + p1) + p2) + p3 over the quarters of the columns
-            if ((c + 1) % qchunks == 0) {
-                const bool first = c + 1 == qchunks;
-#pragma unroll
-                for (int r = 0; r < 8; ++r) fwd_fold_quarter(tot[r], acc[r], first);
+                    for (int t = 0; t < 3; ++t) acc[g * 2 + r] = moc_mfma_half<F16>(Ac[r], cur[kl * 3 + t], acc[g * 2 + r]);
             }
         }
         __syncthreads();                                   // chunk c + 1 has landed for everybody; this buffer is free
     };
-    fu32x4_t wA[F128_KC * PER], wB[F128_KC * PER];
+    fu32x4_t wA[WPC], wB[WPC];
     load_w(0, wA);
     issue_x(0, 0);
     __syncthreads();
@@ -3048,6 +3118,7 @@ int launch_forward(const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws_
             MOC_REQUIRE(B->D <= 1024 && B->C <= 64, "moc_train_steps_runs: fp32 bags need D <= 1024, C <= 64");
             static bool attr_r = false;
             if (!attr_r) {
+                (void)hipFuncSetAttribute((const void*)meta_forward_ksplit_kernel<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, fks_lds_bytes(512));
                 (void)hipFuncSetAttribute((const void*)meta_forward_ksplit_kernel<3, false>, hipFuncAttributeMaxDynamicSharedMemorySize, fks_lds_bytes(768));
                 (void)hipFuncSetAttribute((const void*)meta_forward_ksplit_kernel<4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, fks_lds_bytes(1024));
                 attr_r = true;
@@ -3097,8 +3168,10 @@ int launch_forward(const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws_
         // fp32 bags: the columns split over four wave groups (same bits as the four-wave kernel)
         static bool attr_ks = false;
         if (!attr_ks) {
+            (void)hipFuncSetAttribute((const void*)meta_forward_ksplit_kernel<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, fks_lds_bytes(512));
             (void)hipFuncSetAttribute((const void*)meta_forward_ksplit_kernel<3, false>, hipFuncAttributeMaxDynamicSharedMemorySize, fks_lds_bytes(768));
             (void)hipFuncSetAttribute((const void*)meta_forward_ksplit_kernel<4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, fks_lds_bytes(1024));
+            (void)hipFuncSetAttribute((const void*)meta_forward_ksplit_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, fks_lds_bytes(512));
             (void)hipFuncSetAttribute((const void*)meta_forward_ksplit_kernel<3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, fks_lds_bytes(768));
             (void)hipFuncSetAttribute((const void*)meta_forward_ksplit_kernel<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, fks_lds_bytes(1024));
             attr_ks = true;
@@ -4020,5 +4093,6 @@ extern "C" size_t moc_tile_ws_bytes(int64_t total_rows, int n_slides, int C) {
 
 extern "C" size_t moc_w1_image_bytes(int D, int dtype) {
     if (D <= 0) return 0;
-    return dtype != MOC_F32 ? (size_t)D * H * 3 * 2 : (size_t)D * H * 4;
+    (void)dtype;
+    return (size_t)D * H * 3 * 2;                            // three bf16 (fp16) terms per weight, every storage
 }
