@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define MOC_ABI_VERSION 19
+#define MOC_ABI_VERSION 20
 
 enum { MOC_TICKET_QUEUES = 64, MOC_TICKET_STRIDE = 64,     /* moc_batch_t.tile_ticket: counters, int32 words between them */
        MOC_TICKET_WORDS = (64 + 8) * 64 };
@@ -276,6 +276,16 @@ int moc_pack_selected_rows(const moc_batch_t* B, int slide0, int n, int cap, voi
  * only the backward pass reads them; 256 + 16 bytes per selected row not written). */
 int moc_meta_forward(const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws_t* ws,
                      int slide0, int n, uint32_t use_bits, moc_stream_t stream);
+
+/* Patch maps (ABI 20): every row of slides [slide0, slide0 + n) of an UNMASKED batch whose score pass has run (moc_scores
+ * or moc_phase_a, either statistics layout) gets what moc_meta_forward gives a selected row -- its gates and gated mix, bit
+ * for bit -- without the sel_row gather: row i of slide b is X row x_off[b] + i (row_off[b] + i without x_off), its slot
+ * row_off[b] + i, its candidate scores the statistics at that slot.  gates: device [total_rows, 4] or NULL; mixed: device
+ * [C, total_rows]; both indexed by slot like moc_meta_ws_t and written only at the slots of the n slides (the caller's
+ * buffers: an evaluation's ws->mixed, which moc_pool_loss reads, is left alone).  Error (not a fault) if B->mask != NULL
+ * or B->stats is unset.  use_bits as for moc_meta_forward. */
+int moc_meta_forward_dense(const moc_batch_t* B, const moc_meta_t* M, float* gates, float* mixed,
+                           int slide0, int n, uint32_t use_bits, moc_stream_t stream);
 
 /* ablation_evaluation's parameter-free mixes (main_moc.py:538-553) in place of
  * moc_meta_forward: mode 0 = avg (0.25 each), 1 = sum, 2 = max of the four candidates. */

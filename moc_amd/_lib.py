@@ -15,7 +15,7 @@ import torch  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MOC_HIP_LIB") or os.path.join(_HERE, "libmoc_hip.so")
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 MOC_F32, MOC_BF16, MOC_F16 = 0, 1, 2
 TICKET_WORDS = (64 + 8) * 64    # MOC_TICKET_WORDS (moc_batch_t.tile_ticket)
@@ -82,6 +82,7 @@ SIGNATURES = {
     "moc_pack_selected": (C.c_int, [_BP, C.c_int, C.c_int, C.c_int, _p, _p, _p]),
     "moc_pack_selected_rows": (C.c_int, [_BP, C.c_int, C.c_int, C.c_int, _p, _p, C.c_int64, _p]),
     "moc_meta_forward": (C.c_int, [_BP, _MP, _WP, C.c_int, C.c_int, C.c_uint32, _p]),
+    "moc_meta_forward_dense": (C.c_int, [_BP, _MP, _p, _p, C.c_int, C.c_int, C.c_uint32, _p]),
     "moc_mix_fixed": (C.c_int, [_BP, _WP, C.c_int, C.c_int, C.c_int, _p]),
     "moc_pool_loss": (C.c_int, [_BP, _WP, _p, C.c_int, C.c_int, _p]),
     "moc_ce_loss": (C.c_int, [_p, _p, C.c_int, C.c_int, _p, _p, _p]),

@@ -153,6 +153,9 @@ struct FwdArgs {
     // -> rows is one dependent round trip less than arguments -> n_sel -> sel_row -> rows.  Runs: S_r[run] (S_host >= 0 says so).
     int S_host;
     int32_t S_r[MOC_MAX_RUNS];
+    // the dense forward (moc_meta_forward_dense: every row of a slide, no sel_row gather): first row of each slide in X,
+    // or NULL = row_off.  Unread by every other launch.
+    const int64_t* x_off;
 };
 
 // An entry of an array inside the kernel's (single, by-value) argument struct, read straight from the kernel-argument
@@ -835,7 +838,11 @@ __device__ __forceinline__ void fwd_touch4(fu32x4_t (&v)[4]) {
 // ST: storage of the bag -- 0 bf16, 1 fp16 (three 16-bit terms of W1 per k-step of 32 columns, v_mfma_f32_16x16x32),
 // 2 fp32 (the same image; a chunk = two 1-KiB fp32 pieces per row tile = one k-step of 32 columns, split into bf16
 // terms as it is read from LDS: fwd_split8, fwd_mfma6)
-template <int ST>
+// DENSE (moc_meta_forward_dense, patch maps): every row of the slide instead of its selected ones -- row i is X row
+// x_off[b] + i (row_off[b] + i without x_off), slot row_off[b] + i, its candidate scores the statistics at that slot
+// (cand_mode 1 / 2 with the identity in place of sel_idx).  Everything after the row addresses is the same code: a row
+// gets the bits it gets when it is selected.
+template <int ST, bool DENSE = false>
 __global__ __launch_bounds__(256, f128_wgs(ST)) void meta_forward128_kernel(FwdArgs a) {
     constexpr int F128_KC = f128_kc(ST), F128_BUF = f128_buf(F128_KC), F128_XB = f128_xb(F128_KC);
     constexpr bool F16 = ST == 1;
@@ -847,7 +854,7 @@ __global__ __launch_bounds__(256, f128_wgs(ST)) void meta_forward128_kernel(FwdA
     float* W2s = reinterpret_cast<float*>(smem + F128_XB + F128_ROWS * 4 * 4);      // [4][H]
     const int b = a.slide0 + blockIdx.y;
     const int64_t base = a.row_off[b];
-    const int S = a.n_sel[b];
+    const int S = DENSE ? (int)(a.row_off[b + 1] - base) : a.n_sel[b];
     const int row0 = blockIdx.x * F128_ROWS;
     if (row0 >= S) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -860,7 +867,7 @@ __global__ __launch_bounds__(256, f128_wgs(ST)) void meta_forward128_kernel(FwdA
     // ---- the mix's operands: thread -> row tid & 127, classes (tid >> 7) + 2 it.  Requested now, consumed at the end.
     const int er = threadIdx.x & 127, ec0 = threadIdx.x >> 7;
     const bool erow_ok = row0 + er < S;
-    const float* ecd = cand_row(a, base, erow_ok ? row0 + er : row0);
+    const float* ecd = DENSE ? a.stats + base + (erow_ok ? row0 + er : row0) : cand_row(a, base, erow_ok ? row0 + er : row0);
     // (s_p only: s_sigma is re-formed from it with the compact statistics, and loaded at the end otherwise -- the
     // registers of a second array are what the product needs)
     float es2 = 0.f, es3 = 0.f, em1 = 0.f, erd = 0.f, es0[8];
@@ -881,10 +888,12 @@ __global__ __launch_bounds__(256, f128_wgs(ST)) void meta_forward128_kernel(FwdA
     const int KK = (int)(row_bytes / 64), nchunk = KK / F128_KC;      // k-steps of 64 bytes of a row
     // this wave fetches row tiles 2 wave, 2 wave + 1 of the workgroup: lane l = row (l & 15), 16-B piece (l >> 4) of a k-step
     const unsigned char* rp[2];
+    int64_t xbase = 0;
+    if constexpr (DENSE) xbase = a.x_off ? a.x_off[b] : base;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int sr = min(row0 + (wave * 2 + j) * 16 + (lane & 15), S - 1);
-        rp[j] = a.X + a.sel_row[base + sr] * row_bytes + (lane >> 4) * 16;
+        rp[j] = a.X + (DENSE ? xbase + sr : a.sel_row[base + sr]) * row_bytes + (lane >> 4) * 16;
     }
     typedef const __attribute__((address_space(1))) void* gptr_t;
     typedef __attribute__((address_space(3))) void* lptr_t;
@@ -3056,6 +3065,7 @@ int launch_forward(const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws_
     a.tile = TileWs();
     a.n_runs = 0; a.slide_stride = 0; a.par_stride = a.w2_stride = a.img_stride = 0;
     a.S_host = -1;
+    a.x_off = nullptr;
     a.X = (const unsigned char*)B->X; a.row_off = B->row_off; a.sel_row = B->sel_row; a.n_sel = B->n_sel;
     a.cand = B->cand; a.W1 = M->W1; a.b1 = M->b1; a.W2 = M->W2; a.b2 = M->b2;
     a.W1img = (const unsigned char*)M->W1_image;
@@ -3200,6 +3210,44 @@ int launch_forward(const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws_
     else if (B->dtype == MOC_BF16) meta_forward_kernel<true><<<grid, 256, 0, s>>>(a);
     else meta_forward_kernel<false><<<grid, 256, 0, s>>>(a);
     MOC_CHECK_LAUNCH("moc_meta_forward");
+    return MOC_OK;
+}
+
+// moc_meta_forward_dense: the 128-row kernel over every row of slides [slide0, slide0 + n) of an unmasked batch
+int launch_forward_dense(const moc_batch_t* B, const moc_meta_t* M, float* gates, float* mixed, int slide0, int n,
+                         uint32_t use_bits, hipStream_t s) {
+    FwdArgs a = {};
+    a.base_host = -1;
+    a.S_host = -1;
+    a.X = (const unsigned char*)B->X; a.row_off = B->row_off; a.x_off = B->x_off;
+    a.W1 = M->W1; a.b1 = M->b1; a.W2 = M->W2; a.b2 = M->b2;
+    a.W1img = (const unsigned char*)M->W1_image;
+    a.H1 = nullptr; a.gates = gates; a.mixed = mixed; a.stride = B->total_rows;
+    a.D = B->D; a.C = B->C; a.slide0 = slide0; a.use_bits = use_bits & 15u;
+    a.cand_mode = (B->flags & MOC_STATS_COMPACT) ? 2 : 1;
+    a.stats = B->stats;
+    // rows per slide: exact from the host copy of row_off when there is one, else the batch's bound
+    int64_t rows = B->max_rows;
+    if (B->row_off_host) {
+        rows = 0;
+        for (int q = slide0; q < slide0 + n; ++q) {
+            const int64_t nq = B->row_off_host[q + 1] - B->row_off_host[q];
+            rows = nq > rows ? nq : rows;
+        }
+    }
+    if (rows <= 0) return MOC_OK;
+    static bool attr = false;
+    if (!attr) {
+        (void)hipFuncSetAttribute((const void*)meta_forward128_kernel<0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, f128_lds(f128_kc(0)));
+        (void)hipFuncSetAttribute((const void*)meta_forward128_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, f128_lds(f128_kc(1)));
+        (void)hipFuncSetAttribute((const void*)meta_forward128_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, f128_lds(f128_kc(2)));
+        attr = true;
+    }
+    dim3 g(moc_cdiv(rows, F128_ROWS), n);
+    if (B->dtype == MOC_F16) meta_forward128_kernel<1, true><<<g, 256, f128_lds(f128_kc(1)), s>>>(a);
+    else if (B->dtype == MOC_BF16) meta_forward128_kernel<0, true><<<g, 256, f128_lds(f128_kc(0)), s>>>(a);
+    else meta_forward128_kernel<2, true><<<g, 256, f128_lds(f128_kc(2)), s>>>(a);
+    MOC_CHECK_LAUNCH("moc_meta_forward_dense");
     return MOC_OK;
 }
 
@@ -3518,6 +3566,21 @@ extern "C" int moc_meta_forward(const moc_batch_t* B, const moc_meta_t* M, const
     // the parameters may have changed since the image was last written: rebuild it (H*D elements)
     if (int rc = launch_w1_image(B, M, (hipStream_t)stream)) return rc;
     return launch_forward(B, M, ws, slide0, n, use_bits, (hipStream_t)stream);
+}
+
+extern "C" int moc_meta_forward_dense(const moc_batch_t* B, const moc_meta_t* M, float* gates, float* mixed,
+                                      int slide0, int n, uint32_t use_bits, moc_stream_t stream) {
+    if (int rc = moc_check_batch(B, "moc_meta_forward_dense")) return rc;
+    MOC_REQUIRE(M, "moc_meta_forward_dense: null meta");
+    MOC_REQUIRE(M->H == H, "moc_meta_forward_dense: hidden width %d unsupported (must be %d)", M->H, H);
+    MOC_REQUIRE(M->D == B->D, "moc_meta_forward_dense: meta D=%d != batch D=%d", M->D, B->D);
+    MOC_REQUIRE(M->W1 && M->b1 && M->W2 && M->b2, "moc_meta_forward_dense: null parameter");
+    MOC_REQUIRE(mixed, "moc_meta_forward_dense: null mixed");
+    MOC_REQUIRE(!B->mask, "moc_meta_forward_dense: the batch is masked (slots are not rows); run it unmasked");
+    MOC_REQUIRE(B->stats, "moc_meta_forward_dense: the batch has no statistics (run the score pass first)");
+    MOC_REQUIRE(slide0 >= 0 && n >= 1 && slide0 + n <= B->n_slides, "moc_meta_forward_dense: bad slide range");
+    if (int rc = launch_w1_image(B, M, (hipStream_t)stream)) return rc;
+    return launch_forward_dense(B, M, gates, mixed, slide0, n, use_bits, (hipStream_t)stream);
 }
 
 extern "C" int moc_mix_fixed(const moc_batch_t* B, const moc_meta_ws_t* ws, int slide0, int n, int mode,

@@ -156,15 +156,16 @@ def to_resident(split: Generic_Split, device, dtype=None, loader_seed_draw=False
     """Read every slide of `split` once and keep the split packed in HBM.  `loader_seed_draw`: every pass makes the
     base-seed draw the reference's DataLoader makes (main_moc.ResidentBags)."""
     from .main_moc import ResidentBags
-    bags, labels, paths = [], [], []
+    bags, labels, paths, coords_list = [], [], [], []
     n = split.real_len()
     for i in range(n):
         feats, coords, path = read_bag(split.data_dir, split.slide_data["slide_id"][i])
         bags.append(feats.to(torch.float32))
         labels.append(int(split.slide_data["label"][i]))
         paths.append(path)
+        coords_list.append(coords)
     return ResidentBags(bags, labels, device, dtype=dtype, repeat_num=split.repeat_num, paths=paths,
-                        loader_seed_draw=loader_seed_draw)
+                        loader_seed_draw=loader_seed_draw, coords=coords_list)
 
 
 def to_sharded(split: Generic_Split, device, rank: int, world: int, dtype=None, train=False, group=None):

@@ -769,6 +769,20 @@ def meta_forward(batch: SlideBatch, meta: MetaState, slide0: int, n: int, use_bi
           "moc_meta_forward")
 
 
+def meta_forward_dense(batch: SlideBatch, meta: MetaState, slide0: int, n: int, use_bits: int,
+                       gates: torch.Tensor | None, mixed: torch.Tensor):
+    """Patch maps: the gates [total, 4] (nullable) and mixed scores [C, total] of EVERY row of slides slide0 .. +n of an
+    unmasked batch whose score pass has run, into the caller's tensors -- at a selected row the bits meta_forward gives it
+    (moc_meta_forward_dense)."""
+    T = batch.total
+    assert batch.mask is None, "meta_forward_dense: the batch must be unmasked"
+    assert mixed.is_cuda and mixed.dtype == torch.float32 and mixed.is_contiguous() and tuple(mixed.shape) == (batch.C, T)
+    if gates is not None:
+        assert gates.is_cuda and gates.dtype == torch.float32 and gates.is_contiguous() and tuple(gates.shape) == (T, 4)
+    check(lib().moc_meta_forward_dense(C.byref(batch.c), C.byref(meta.c), ptr(gates), ptr(mixed), slide0, n, use_bits,
+                                       _stream()), "moc_meta_forward_dense")
+
+
 def mix_fixed(batch: SlideBatch, slide0: int, n: int, mode: str):
     _, ws = batch.meta_ws()
     code = {"avg": 0, "sum": 1, "max": 2}[mode]

@@ -166,7 +166,8 @@ class ResidentBags:
     items; .dataset.real_len(), .dataset.repeat_num, len()).  train/evaluation
     recognise it and skip the per-epoch re-read + host->device copy."""
 
-    def __init__(self, bags, labels, device, dtype=None, repeat_num=None, paths=None, loader_seed_draw=False, cache_scores=None):
+    def __init__(self, bags, labels, device, dtype=None, repeat_num=None, paths=None, loader_seed_draw=False, cache_scores=None,
+                 coords=None):
         dtype = dtype or bags[0].dtype
         # opt-in: keep the per-row statistics of the split (28 B per row at two classes) from one unmasked score pass and let
         # every train pass copy its kept rows' statistics instead of reading the bags again: the same bits, phase A without
@@ -186,6 +187,15 @@ class ResidentBags:
         self.starts = [0]
         for n in self.sizes:
             self.starts.append(self.starts[-1] + n)
+        # patch coordinates (host int64 [total_rows, 2], rows as in X; zeros for bags without any) and a view per slide --
+        # for the patch maps (moc_amd.patch_maps).  __iter__ does not hand them out.
+        self.coords = np.zeros((self.starts[-1], 2), dtype=np.int64)
+        for k, c in enumerate(coords or ()):
+            if c is not None:
+                c = np.asarray(c, dtype=np.int64).reshape(-1, 2)
+                assert c.shape[0] == self.sizes[k], f"slide {k}: {c.shape[0]} coordinates for {self.sizes[k]} patches"
+                self.coords[self.starts[k]:self.starts[k + 1]] = c
+        self.slide_coords = [self.coords[self.starts[k]:self.starts[k + 1]] for k in range(len(self.sizes))]
         self.dataset = self
         self._plans = {}
         self._last_train_key = None
@@ -271,17 +281,24 @@ class ResidentBags:
                    torch.zeros(1, x.size(0), 2, dtype=torch.int64), [self.paths[k]])
 
 
-def _collect(loader, device, args):
-    """One pass over a loader -> (X, sizes, x_starts|None, labels)."""
+def _collect(loader, device, args, extras=None):
+    """One pass over a loader -> (X, sizes, x_starts|None, labels).  `extras` (a list): gets (coords int64 [N, 2], path)
+    per visit appended (the patch maps)."""
     if isinstance(loader, ResidentBags):
         order = loader.visit_order()
         sizes = [loader.sizes[k] for k in order]
+        if extras is not None:
+            extras.extend((loader.slide_coords[k], loader.paths[k]) for k in order)
         return loader.X, sizes, [loader.starts[k] for k in order], [loader.labels[k] for k in order]
     bags, labels = [], []
     for data in tqdm(loader, bar_format="{l_bar}{bar:10}{r_bar}", disable=args.disable_tqdm):
         feats, lbl, coords, full_path = data
         bags.append(feats.squeeze(0))
         labels.append(int(lbl.reshape(-1)[0]))
+        if extras is not None:
+            c = np.asarray(coords.numpy() if torch.is_tensor(coords) else coords, dtype=np.int64).reshape(-1, 2)
+            p = full_path[0] if isinstance(full_path, (list, tuple)) else full_path
+            extras.append((c, str(p)))
     dtype = _bag_dtype(args, bags[0].dtype if bags[0].dtype in (torch.float32, torch.bfloat16, torch.float16) else torch.float32)
     X, sizes = _pack(bags, device, dtype)
     return X, sizes, None, labels
@@ -626,14 +643,16 @@ def _metrics(pooled_cpu, labels, losses, n_div, real_len, args):
     return {"loss": test_loss, "acc": correct / real_len, "auc": auc}
 
 
-def _eval_batches(loader, device, args, mode):
-    """(batch, device labels, label list) per chunk of an evaluation pass."""
+def _eval_batches(loader, device, args, mode, extras=None):
+    """(batch, device labels, label list) per chunk of an evaluation pass.  `extras`: see _collect."""
     discard = args.discard_classifiers if mode == "eval" else []
     if isinstance(loader, ResidentBags) and loader.X.numel() * loader.X.element_size() <= MAX_BATCH_BYTES:
         bank = _bank_for(loader.X, device, fg_from_ext=(mode == "zs_bottomk"))
         plan = loader.eval_plan(bank.C, bank.Ce, args.topj, args.topk, discard)
+        if extras is not None:
+            extras.extend((loader.slide_coords[k], loader.paths[k]) for k in loader.visit_order())
         return bank, [(plan["batch"], plan["labels"], plan["label_list"])]
-    X, sizes, x_starts, labels = _collect(loader, device, args)
+    X, sizes, x_starts, labels = _collect(loader, device, args, extras)
     bank = _bank_for(X, device, fg_from_ext=(mode == "zs_bottomk"))
     out = []
     for ids in _chunks(sizes, X.size(1), X.element_size()):

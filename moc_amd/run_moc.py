@@ -14,7 +14,8 @@ additive: the dataset branch is table driven (ebrains12 / ebrains30 work like ns
 CONCH text tower is not part of this path, so the zero-shot weights must already be cached under
 `models/classifier_weights/` (the reference caches them there on first run, main_moc.py:149-197);
 `--bag_dtype bf16|fp16` stores bags as bfloat16 / float16; `--resident 0` falls back to per-epoch re-reads;
-`--synthetic N` runs the whole loop on N generated slides per split.
+`--synthetic N` runs the whole loop on N generated slides per split; `--patch_maps SPLIT` writes per-patch maps with the
+best checkpoint after training, `--patch_maps_from best_model_*.pt` only those (moc_amd.patch_maps).
 
 Under a launcher (WORLD_SIZE > 1) every split is spread over the GPUs (each rank reads only its block of slides):
 training is the exact-sequential mode -- phase A where the bags are, the compact results all-gathered, the reference's
@@ -83,7 +84,34 @@ def get_args(argv=None):
                         "what scripts/moc_train.sh starts as one process per fold.  Every fold's numbers and files are those of "
                         "`--fold F` alone (with --seed: bit for bit).  Under a launcher the folds are dealt to the ranks, no "
                         "communication")
+    p.add_argument("--patch_maps", type=str, default=None, choices=list(PATCH_MAP_CHOICES),
+                   help="after main(), write per-patch maps (moc_amd.patch_maps) of these splits with the best checkpoint to "
+                        "{result_dir}/patch_maps_shot_S_fold_F/{split}/ (default: none; test with --patch_maps_from)")
+    p.add_argument("--patch_maps_from", type=str, default=None,
+                   help="inference only: load this saved state dict, skip zero-shot and training, write the patch maps of "
+                        "the --patch_maps splits and patch_maps_results_shot_S_fold_F.json (each split's evaluation())")
     return p.parse_args(argv)
+
+
+PATCH_MAP_CHOICES = ("none", "train", "val", "test", "all")
+
+
+def patch_map_splits(args):
+    """The splits `--patch_maps` / `--patch_maps_from` ask for, in train, val, test order."""
+    want = args.patch_maps or ("test" if args.patch_maps_from else "none")
+    return {"none": [], "all": ["train", "val", "test"]}.get(want, [want])
+
+
+def check_patch_map_args(args):
+    """Refusals of the patch-map flags, from the command line alone (before any GPU work)."""
+    if not patch_map_splits(args) and not args.patch_maps_from:
+        return
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("--patch_maps / --patch_maps_from are one-GPU options: run them without a launcher")
+    if args.folds:
+        raise SystemExit("--patch_maps / --patch_maps_from do not combine with --folds: run one --fold at a time")
+    if args.ablation_study != "none":
+        raise SystemExit("--patch_maps / --patch_maps_from need the meta-learner: the ablation study trains none")
 
 
 # ------------------------------------------------------------------ --summary (main_moc.py:53-127)
@@ -298,6 +326,32 @@ def main(args, model, optimizer, train_loader, val_loader, test_loader, device):
     return results
 
 
+def write_split_maps(args, model, loaders, device):
+    """The patch maps of the `patch_map_splits(args)` splits under {result_dir}/patch_maps_shot_S_fold_F/{split}/.
+    -> {split: evaluation() of that split}."""
+    from . import patch_maps as PM
+    root = os.path.join(args.result_dir, f"patch_maps_shot_{args.shot}_fold_{args.fold}")
+    out = {}
+    for split in patch_map_splits(args):
+        loader = loaders[("train", "val", "test").index(split)]
+        out[split] = M.evaluation(model, loader, device, args)
+        maps = PM.patch_maps(model, loader, device, args)
+        PM.write_patch_maps(maps, os.path.join(root, split))
+        print(f"patch maps: {len(maps)} slides of {split} -> {os.path.join(root, split)}")
+    return out
+
+
+def patch_maps_from(args, model, loaders, device):
+    """--patch_maps_from: inference with a saved meta-learner -- no zero-shot pass, no training."""
+    state = torch.load(args.patch_maps_from, map_location="cpu")
+    model.load_state_dict(state)
+    os.makedirs(args.result_dir, exist_ok=True)
+    res = write_split_maps(args, model, loaders, device)
+    with open(os.path.join(args.result_dir, f"patch_maps_results_shot_{args.shot}_fold_{args.fold}.json"), "w") as f:
+        json.dump(res, f, indent=4)
+    return res
+
+
 def main_runs(args_list, models, optimizers, loaders_list, device, generators=None):
     """main() (main_moc.py:586-644) for several runs at once: the zero-shot evaluations and the per-epoch evaluations run
     per run, the training passes of all runs in lockstep (moc_amd.main_moc.train_runs).  `args_list[r]` carries run r's
@@ -395,6 +449,7 @@ def cli(argv=None):
     if args.summary:
         summary(args)
         return None
+    check_patch_map_args(args)
     if not torch.cuda.is_available():
         raise RuntimeError("moc_amd needs a GPU: there is no CPU fallback")
     if args.folds:
@@ -423,8 +478,16 @@ def cli(argv=None):
         torch.manual_seed(args.seed)
     model = M.senet(512, 4).to(device)                                                   # main_moc.py:315
     optimizer = torch.optim.Adam(model.parameters(), lr=1e-3, weight_decay=1e-4)         # main_moc.py:316
+    loaders = (train_loader, val_loader, test_loader)
+    if args.patch_maps_from:
+        return patch_maps_from(args, model, loaders, device)
     try:
-        return main(args, model, optimizer, train_loader, val_loader, test_loader, device)
+        res = main(args, model, optimizer, train_loader, val_loader, test_loader, device)
+        if patch_map_splits(args):        # the best checkpoint, or the final model when none was written
+            if os.path.exists(res["best_model_path"]):
+                model.load_state_dict(torch.load(res["best_model_path"], map_location="cpu"))
+            write_split_maps(args, model, loaders, device)
+        return res
     finally:
         if world > 1:
             import torch.distributed as dist
