@@ -323,6 +323,19 @@ int moc_train_steps_runs(const moc_batch_t* B, const moc_meta_t* M, const moc_ru
                          const int64_t* labels, int slide0, int n, uint32_t use_bits, moc_stream_t stream);
 int moc_train_runs_mode(const moc_batch_t* B, const moc_meta_ws_t* ws);
 
+/* Prediction with several meta-learners (an ensemble of checkpoints; ABI 20, additive): the evaluation forward of
+ * moc_meta_forward for R->n_runs models (1 .. 16) over the union rows of slides [slide0, slide0 + n) of an UNMASKED batch
+ * whose phase A has run, in one launch: the row ids and candidate scores are read once per tile for all models.  Model r's
+ * parameters lie r * R->par_stride floats behind M's (W1 | b1 | W2 | b2 of a model in one block, as moc_train_steps_runs
+ * lays them out), its W1 image r * R->image_stride bytes behind M->W1_image (rebuilt here for every model).
+ * R->slide_stride must be 0: every model works on the same slides.  mixed: device [n_runs][C][total_rows] fp32, model r's
+ * slab indexed by slot like moc_meta_ws_t.mixed and written at the union slots of the n slides -- bit for bit what
+ * moc_meta_forward gives with model r alone (pool each slab with moc_pool_loss through a ws whose `mixed` points at it).
+ * Errors (not faults), before anything is launched: a masked batch, no phase-A outputs, null mixed, n_runs outside
+ * 1 .. 16, nonzero slide_stride, par_stride / image_stride smaller than one model.  use_bits as for moc_meta_forward. */
+int moc_meta_forward_models(const moc_batch_t* B, const moc_meta_t* M, const moc_runs_t* R, float* mixed,
+                            int slide0, int n, uint32_t use_bits, moc_stream_t stream);
+
 /* a10-a14 for ONE slide without the update: forward, pooling, loss (ws->loss/pooled/pred) and
  * the gradients of that loss w.r.t. the four parameter tensors, written (not accumulated) to
  * M->g_*.  The data-parallel step all-reduces them and calls moc_adam_step. */

@@ -842,8 +842,17 @@ __device__ __forceinline__ void fwd_touch4(fu32x4_t (&v)[4]) {
 // x_off[b] + i (row_off[b] + i without x_off), slot row_off[b] + i, its candidate scores the statistics at that slot
 // (cand_mode 1 / 2 with the identity in place of sel_idx).  Everything after the row addresses is the same code: a row
 // gets the bits it gets when it is selected.
-template <int ST, bool DENSE = false>
-__global__ __launch_bounds__(256, f128_wgs(ST)) void meta_forward128_kernel(FwdArgs a) {
+// MODELS (moc_meta_forward_models, prediction with an ensemble): a.n_runs meta-learners over the same tile, one after the
+// other -- model m's parameters par_stride floats and its W1 image img_stride bytes behind model 0's, its mixed scores
+// C x stride floats behind model 0's.  The prologue (row ids, candidate scores and norms) is paid once per tile; model
+// m >= 1 re-streams the tile's rows by LDS-DMA (from L2 / MALL where they still hold them; bytes not yet measured).  Per model
+// it is the same code: model m gets the bits it gets alone.  The mode is a flag inside the first template argument
+// (F128_MODELS + storage) so that the existing instantiations keep their symbols and their code.
+constexpr int F128_MODELS = 4;
+template <int STM, bool DENSE = false>
+__global__ __launch_bounds__(256, f128_wgs(STM & 3)) void meta_forward128_kernel(FwdArgs a) {
+    constexpr int ST = STM & 3;
+    constexpr bool MODELS = (STM & F128_MODELS) != 0;
     constexpr int F128_KC = f128_kc(ST), F128_BUF = f128_buf(F128_KC), F128_XB = f128_xb(F128_KC);
     constexpr bool F16 = ST == 1;
     constexpr int WPC = 3 * (ST == 2 ? F128_KC / 2 : F128_KC);      // W1 fragments per chunk (three terms per 32 columns)
@@ -881,9 +890,9 @@ __global__ __launch_bounds__(256, f128_wgs(ST)) void meta_forward128_kernel(FwdA
         es0[it] = 0.f;
         if (erow_ok && c < C) es0[it] = ecd[(int64_t)c * a.stride];
     }
-    const float w2_pre = a.W2[threadIdx.x & 255];
-    const float bias = a.b1[wave * 16 + (lane & 15)];
-    const float b2_pre = a.b2[threadIdx.x & 3];
+    float w2_pre = a.W2[threadIdx.x & 255];               // (MODELS: model 0's; the others' at the top of their turn)
+    float bias = a.b1[wave * 16 + (lane & 15)];
+    float b2_pre = a.b2[threadIdx.x & 3];
     const int64_t row_bytes = (int64_t)a.D * ESZ;
     const int KK = (int)(row_bytes / 64), nchunk = KK / F128_KC;      // k-steps of 64 bytes of a row
     // this wave fetches row tiles 2 wave, 2 wave + 1 of the workgroup: lane l = row (l & 15), 16-B piece (l >> 4) of a k-step
@@ -906,7 +915,18 @@ __global__ __launch_bounds__(256, f128_wgs(ST)) void meta_forward128_kernel(FwdA
                 __builtin_amdgcn_global_load_lds((gptr_t)(rp[j] + ((int64_t)c * F128_KC + kl) * 64),
                                                  (lptr_t)(dst + ((wave * 2 + j) * F128_KC + kl) * 1024), 16, 0, 0);
     };
-    const fu32x4_t* wimg = reinterpret_cast<const fu32x4_t*>(a.W1img) + (size_t)wave * (a.D / 32) * 3 * 64 + lane;
+    // model m (MODELS: a backward jump to here, not a loop: the other instantiations keep the code they had before)
+    int m = 0;
+next_model:
+    if (MODELS && m > 0) {                                 // model m's parameters (model 0's were requested above)
+        const int64_t po = (int64_t)m * a.par_stride;
+        w2_pre = a.W2[po + (threadIdx.x & 255)];
+        bias = a.b1[po + wave * 16 + (lane & 15)];
+        b2_pre = a.b2[po + (threadIdx.x & 3)];
+    }
+    const unsigned char* w1img = MODELS ? a.W1img + (int64_t)m * a.img_stride : a.W1img;
+    float* mixed = MODELS ? a.mixed + (int64_t)m * C * a.stride : a.mixed;
+    const fu32x4_t* wimg = reinterpret_cast<const fu32x4_t*>(w1img) + (size_t)wave * (a.D / 32) * 3 * 64 + lane;
     auto load_w = [&](int c, fu32x4_t (&wv)[WPC]) {
 #pragma unroll
         for (int q = 0; q < WPC; ++q) wv[q] = wimg[((size_t)c * WPC + q) * 64];
@@ -1021,7 +1041,8 @@ __global__ __launch_bounds__(256, f128_wgs(ST)) void meta_forward128_kernel(FwdA
     if (erow_ok && !(diag & 8u)) {
         const float g0 = Gs[er][0], g1 = Gs[er][1], g2 = Gs[er][2], g3 = Gs[er][3];
         for (int cb = 0; cb < C; cb += 16) {
-            if (cb > 0) {                                  // beyond the 16 classes requested at the start
+            // beyond the 16 classes requested at the start (MODELS: the model before left the last 16 there)
+            if (cb > 0 || (MODELS && m > 0 && C > 16)) {
 #pragma unroll
                 for (int it = 0; it < 8; ++it) {
                     const int c = cb + ec0 + 2 * it;
@@ -1045,9 +1066,12 @@ __global__ __launch_bounds__(256, f128_wgs(ST)) void meta_forward128_kernel(FwdA
                 if (a.use_bits & 2u) v = moc_fadd(v, moc_fmul(g1, s1));
                 if (a.use_bits & 4u) v = moc_fadd(v, moc_fmul(g2, es2));
                 if (a.use_bits & 8u) v = moc_fadd(v, moc_fmul(g3, es3));
-                a.mixed[(int64_t)c * a.stride + base + row0 + er] = v;
+                mixed[(int64_t)c * a.stride + base + row0 + er] = v;
             }
         }
+    }
+    if constexpr (MODELS) {
+        if (++m < a.n_runs) goto next_model;
     }
 }
 
@@ -3251,6 +3275,37 @@ int launch_forward_dense(const moc_batch_t* B, const moc_meta_t* M, float* gates
     return MOC_OK;
 }
 
+// moc_meta_forward_models: the 128-row kernel for R->n_runs meta-learners over the union rows of slides [slide0, slide0 + n)
+int launch_forward_models(const moc_batch_t* B, const moc_meta_t* M, const moc_runs_t* R, float* mixed, int slide0, int n,
+                          uint32_t use_bits, hipStream_t s) {
+    FwdArgs a = {};
+    a.base_host = -1;
+    a.S_host = -1;
+    a.X = (const unsigned char*)B->X; a.row_off = B->row_off; a.sel_row = B->sel_row; a.n_sel = B->n_sel;
+    a.cand = B->cand; a.W1 = M->W1; a.b1 = M->b1; a.W2 = M->W2; a.b2 = M->b2;
+    a.W1img = (const unsigned char*)M->W1_image;
+    a.H1 = nullptr; a.gates = nullptr; a.mixed = mixed; a.stride = B->total_rows;
+    a.D = B->D; a.C = B->C; a.slide0 = slide0; a.use_bits = use_bits & 15u;
+    if (B->flags & MOC_CAND_FROM_STATS) {
+        a.cand_mode = (B->flags & MOC_STATS_COMPACT) ? 2 : 1;
+        a.stats = B->stats; a.sel_idx = B->sel_idx;
+    }
+    a.n_runs = R->n_runs; a.par_stride = R->par_stride; a.img_stride = R->image_stride;
+    static bool attr = false;
+    if (!attr) {
+        (void)hipFuncSetAttribute((const void*)meta_forward128_kernel<F128_MODELS + 0>, hipFuncAttributeMaxDynamicSharedMemorySize, f128_lds(f128_kc(0)));
+        (void)hipFuncSetAttribute((const void*)meta_forward128_kernel<F128_MODELS + 1>, hipFuncAttributeMaxDynamicSharedMemorySize, f128_lds(f128_kc(1)));
+        (void)hipFuncSetAttribute((const void*)meta_forward128_kernel<F128_MODELS + 2>, hipFuncAttributeMaxDynamicSharedMemorySize, f128_lds(f128_kc(2)));
+        attr = true;
+    }
+    dim3 g(moc_cdiv(s_bound(B), F128_ROWS), n);
+    if (B->dtype == MOC_F16) meta_forward128_kernel<F128_MODELS + 1><<<g, 256, f128_lds(f128_kc(1)), s>>>(a);
+    else if (B->dtype == MOC_BF16) meta_forward128_kernel<F128_MODELS + 0><<<g, 256, f128_lds(f128_kc(0)), s>>>(a);
+    else meta_forward128_kernel<F128_MODELS + 2><<<g, 256, f128_lds(f128_kc(2)), s>>>(a);
+    MOC_CHECK_LAUNCH("moc_meta_forward_models");
+    return MOC_OK;
+}
+
 int launch_pool(const moc_batch_t* B, const moc_meta_ws_t* ws, int slide0, int n, hipStream_t s) {
     return moc_launch_topk_mean(ws->mixed, B->total_rows, ws->mixed, B->total_rows, B->row_off, B->n_sel,
                                 slide0, n, B->C, B->topk, 0, ws->pooled, ws->topk_idx, ws->topk_cnt, s);
@@ -3581,6 +3636,38 @@ extern "C" int moc_meta_forward_dense(const moc_batch_t* B, const moc_meta_t* M,
     MOC_REQUIRE(slide0 >= 0 && n >= 1 && slide0 + n <= B->n_slides, "moc_meta_forward_dense: bad slide range");
     if (int rc = launch_w1_image(B, M, (hipStream_t)stream)) return rc;
     return launch_forward_dense(B, M, gates, mixed, slide0, n, use_bits, (hipStream_t)stream);
+}
+
+extern "C" int moc_meta_forward_models(const moc_batch_t* B, const moc_meta_t* M, const moc_runs_t* R, float* mixed,
+                                       int slide0, int n, uint32_t use_bits, moc_stream_t stream) {
+    if (int rc = moc_check_batch(B, "moc_meta_forward_models")) return rc;
+    MOC_REQUIRE(M, "moc_meta_forward_models: null meta");
+    MOC_REQUIRE(M->H == H, "moc_meta_forward_models: hidden width %d unsupported (must be %d)", M->H, H);
+    MOC_REQUIRE(M->D == B->D, "moc_meta_forward_models: meta D=%d != batch D=%d", M->D, B->D);
+    MOC_REQUIRE(M->W1 && M->b1 && M->W2 && M->b2, "moc_meta_forward_models: null parameter");
+    MOC_REQUIRE(M->W1_image, "moc_meta_forward_models: W1_image buffer is null (n_runs x image_stride bytes)");
+    MOC_REQUIRE(mixed, "moc_meta_forward_models: null mixed");
+    MOC_REQUIRE(R, "moc_meta_forward_models: null runs");
+    MOC_REQUIRE(R->n_runs >= 1 && R->n_runs <= MOC_MAX_RUNS, "moc_meta_forward_models: n_runs=%d outside 1 .. %d", R->n_runs,
+                MOC_MAX_RUNS);
+    MOC_REQUIRE(R->slide_stride == 0, "moc_meta_forward_models: slide_stride=%d must be 0 (every model works on the same slides)",
+                R->slide_stride);
+    MOC_REQUIRE(R->par_stride >= (int64_t)H * B->D + H + 4 * H + 4,
+                "moc_meta_forward_models: par_stride=%lld smaller than one meta-learner", (long long)R->par_stride);
+    MOC_REQUIRE(R->image_stride >= (int64_t)moc_w1_image_bytes(B->D, B->dtype),
+                "moc_meta_forward_models: image_stride=%lld < moc_w1_image_bytes=%lld", (long long)R->image_stride,
+                (long long)moc_w1_image_bytes(B->D, B->dtype));
+    MOC_REQUIRE(!B->mask, "moc_meta_forward_models: the batch is masked; run it unmasked (an evaluation pass)");
+    MOC_REQUIRE(B->stats && B->sel_row && B->n_sel && B->sel_idx,
+                "moc_meta_forward_models: the batch has no phase-A outputs (run moc_phase_a first)");
+    MOC_REQUIRE((B->flags & MOC_CAND_FROM_STATS) || B->cand, "moc_meta_forward_models: the batch has no candidate scores");
+    MOC_REQUIRE(slide0 >= 0 && n >= 1 && slide0 + n <= B->n_slides, "moc_meta_forward_models: bad slide range");
+    hipStream_t s = (hipStream_t)stream;
+    // every model's image, rebuilt from its parameters (grid.y = model)
+    w1_image_kernel<<<dim3(H * B->D / 256, R->n_runs), 256, 0, s>>>(M->W1, B->D, (unsigned char*)M->W1_image, B->dtype, R->par_stride,
+                                                                    R->image_stride);
+    MOC_CHECK_LAUNCH("moc_w1_image(models)");
+    return launch_forward_models(B, M, R, mixed, slide0, n, use_bits, s);
 }
 
 extern "C" int moc_mix_fixed(const moc_batch_t* B, const moc_meta_ws_t* ws, int slide0, int n, int mode,

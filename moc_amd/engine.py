@@ -13,7 +13,7 @@ from typing import Sequence
 import torch
 
 from . import _lib
-from ._lib import MocBatch, MocMeta, MocMetaWs, check, lib, ptr
+from ._lib import MocBatch, MocMeta, MocMetaWs, MocRuns, check, lib, ptr
 
 HIDDEN = 64
 # MOC_STEP_GRAPH=1: a pass of meta-steps as one hipGraph launch (moc_train_steps_graph) instead of 2 n + 1 stream
@@ -781,6 +781,74 @@ def meta_forward_dense(batch: SlideBatch, meta: MetaState, slide0: int, n: int, 
         assert gates.is_cuda and gates.dtype == torch.float32 and gates.is_contiguous() and tuple(gates.shape) == (T, 4)
     check(lib().moc_meta_forward_dense(C.byref(batch.c), C.byref(meta.c), ptr(gates), ptr(mixed), slide0, n, use_bits,
                                        _stream()), "moc_meta_forward_dense")
+
+
+class ModelArena:
+    """R senet state_dicts (`model.<i>.weight` / `.bias` of senet(D, 4)) packed the way moc_meta_forward_models reads them:
+    model r's W1 | b1 | W2 | b2 at row r of one [R, par_stride] fp32 arena, its W1 operand image at row r of an
+    [R, image_stride] byte arena (the entry rebuilds the images).  `c`: the moc_meta_t of model 0, `runs`: the moc_runs_t."""
+
+    def __init__(self, state_dicts, device):
+        R = len(state_dicts)
+        assert 1 <= R <= 16, "ModelArena: 1 .. 16 models"
+        keys = ("model.0.weight", "model.0.bias", "model.2.weight", "model.2.bias")
+        D = int(state_dicts[0]["model.0.weight"].shape[1])
+        shapes = ((HIDDEN, D), (HIDDEN,), (4, HIDDEN), (4,))
+        for sd in state_dicts:
+            assert all(tuple(sd[k].shape) == s for k, s in zip(keys, shapes)), f"ModelArena: every model must be senet({D}, 4)"
+        self.R, self.D, self.device = R, D, device
+        n_par = HIDDEN * D + HIDDEN + 4 * HIDDEN + 4
+        self.par_stride = (n_par + 63) // 64 * 64
+        img_b = max(lib().moc_w1_image_bytes(D, _lib.MOC_BF16), lib().moc_w1_image_bytes(D, _lib.MOC_F32))
+        self.img_stride = (img_b + 255) // 256 * 256
+        self.P = torch.zeros((R, self.par_stride), dtype=torch.float32, device=device)
+        self.images = torch.empty((R, self.img_stride), dtype=torch.uint8, device=device)
+        offs = (0, HIDDEN * D, HIDDEN * D + HIDDEN, HIDDEN * D + HIDDEN + 4 * HIDDEN)
+        for r, sd in enumerate(state_dicts):
+            for k, o in zip(keys, offs):
+                t = sd[k].detach().reshape(-1)
+                self.P[r, o:o + t.numel()].copy_(t.to(device=device, dtype=torch.float32))
+        base = ptr(self.P)
+        self.c = MocMeta(W1=base, b1=base + 4 * offs[1], W2=base + 4 * offs[2], b2=base + 4 * offs[3],
+                         W1_image=ptr(self.images), H=HIDDEN, D=D)
+        self.runs = MocRuns(n_runs=R, slide_stride=0, par_stride=self.par_stride, image_stride=self.img_stride)
+
+
+def meta_forward_models(batch: SlideBatch, params: ModelArena, n_models: int, mixed: torch.Tensor, slide0: int, n: int,
+                        use_bits: int):
+    """The evaluation forward of n_models meta-learners (the first n_models of `params`) over the union rows of slides
+    slide0 .. +n of an unmasked batch whose phase A has run, in one launch: mixed [n_models, C, total] -- slab r is what
+    meta_forward gives with model r alone (moc_meta_forward_models)."""
+    T = batch.total
+    assert batch.mask is None, "meta_forward_models: the batch must be unmasked"
+    assert 1 <= n_models <= params.R and params.D == batch.D, "meta_forward_models: models / width do not match"
+    assert mixed.is_cuda and mixed.dtype == torch.float32 and mixed.is_contiguous() and \
+        tuple(mixed.shape) == (n_models, batch.C, T)
+    runs = MocRuns.from_buffer_copy(params.runs)
+    runs.n_runs = n_models
+    check(lib().moc_meta_forward_models(C.byref(batch.c), C.byref(params.c), C.byref(runs), ptr(mixed), slide0, n, use_bits,
+                                        _stream()), "moc_meta_forward_models")
+
+
+def pool_models(batch: SlideBatch, mixed: torch.Tensor, labels: torch.Tensor, slide0: int, n: int):
+    """moc_pool_loss over every model's slab of `mixed` [R, C, total] -> dict of per-model pooled [R, n_slides, C], pred,
+    loss [R, n_slides] and topk_idx / topk_cnt (labels: device int64 [n_slides]; zeros for unlabeled slides -- the loss
+    is then meaningless)."""
+    t, ws = batch.meta_ws()
+    R, ns, Cc, K = mixed.size(0), batch.n_slides, batch.C, batch.topk
+    dev = mixed.device
+    out = dict(pooled=torch.empty((R, ns, Cc), dtype=torch.float32, device=dev),
+               topk_idx=torch.empty((R, ns, Cc, K), dtype=torch.int32, device=dev),
+               topk_cnt=torch.empty((R, ns, Cc), dtype=torch.int32, device=dev),
+               loss=torch.empty((R, ns), dtype=torch.float32, device=dev),
+               pred=torch.empty((R, ns), dtype=torch.int32, device=dev))
+    for r in range(R):
+        w = type(ws).from_buffer_copy(ws)
+        w.mixed = ptr(mixed[r])
+        for k in ("pooled", "topk_idx", "topk_cnt", "loss", "pred"):
+            setattr(w, k, ptr(out[k][r]))
+        check(lib().moc_pool_loss(C.byref(batch.c), C.byref(w), ptr(labels), slide0, n, _stream()), "moc_pool_loss")
+    return out
 
 
 def mix_fixed(batch: SlideBatch, slide0: int, n: int, mode: str):
