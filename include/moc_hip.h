@@ -336,6 +336,22 @@ int moc_train_runs_mode(const moc_batch_t* B, const moc_meta_ws_t* ws);
 int moc_meta_forward_models(const moc_batch_t* B, const moc_meta_t* M, const moc_runs_t* R, float* mixed,
                             int slide0, int n, uint32_t use_bits, moc_stream_t stream);
 
+/* Ensemble patch maps (ABI 20, additive): the dense forward of moc_meta_forward_dense for R->n_runs models (1 .. 16) over
+ * EVERY row of slides [slide0, slide0 + n) of an UNMASKED batch whose score pass has run, the models reduced on the device.
+ * With p_r = softmax_c(scale * mixed_r) of model r alone (scale: the evaluation temperature, 56.3477):
+ *   prob_mean  [C][total_rows]  (1/R) sum_r p_r                        required
+ *   prob_std   [C][total_rows]  sqrt((1/R) sum_r (p_r - mean)^2)       (population std; may be NULL)
+ *   gates_mean [total_rows][4]  (1/R) sum_r gates_r                    (may be NULL)
+ * indexed by slot like moc_meta_forward_dense's outputs and written at the rows of the n slides only.  fp32, in model order
+ * (a Welford update): the same inputs give the same bits.  The per-model slabs never reach memory.  Parameters and W1 images
+ * as for moc_meta_forward_models (par_stride / image_stride; the images are rebuilt here), R->slide_stride must be 0.
+ * Errors (not faults), before anything is launched: a masked batch, no statistics, null prob_mean, n_runs outside 1 .. 16,
+ * nonzero slide_stride, par_stride / image_stride smaller than one model, meta D != batch D, C > 64, a bad slide range,
+ * a scale that is not finite.  use_bits as for moc_meta_forward. */
+int moc_meta_forward_dense_models(const moc_batch_t* B, const moc_meta_t* M, const moc_runs_t* R, float scale,
+                                  float* prob_mean, float* prob_std, float* gates_mean, int slide0, int n, uint32_t use_bits,
+                                  moc_stream_t stream);
+
 /* a10-a14 for ONE slide without the update: forward, pooling, loss (ws->loss/pooled/pred) and
  * the gradients of that loss w.r.t. the four parameter tensors, written (not accumulated) to
  * M->g_*.  The data-parallel step all-reduces them and calls moc_adam_step. */

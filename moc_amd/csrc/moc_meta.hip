@@ -140,7 +140,11 @@ struct FwdArgs {
     const int32_t* sel_idx;
     // tile records for the step kernel (training step of ONE slide, base_host >= 0): tile_on != 0
     TileWs tile;
-    int tile_on, tile_cap;          // tile_cap = ceil(rows of the slide / 16)
+    int tile_on;
+    union {
+        int tile_cap;               // tile_cap = ceil(rows of the slide / 16)
+        float ens_scale;            // moc_meta_forward_dense_models (no tile records): the softmax's temperature
+    };
     int64_t tile_slot0;             // first slot of the slide's region
     // batched runs (round 4; n_runs > 0): ONE launch serves n_runs independent meta-learners, grid.y = run.  Run r works on
     // slide slide0 + r * slide_stride with its own parameters, par_stride floats (W2: w2_stride; operand image: img_stride
@@ -848,11 +852,22 @@ __device__ __forceinline__ void fwd_touch4(fu32x4_t (&v)[4]) {
 // m >= 1 re-streams the tile's rows by LDS-DMA (from L2 / MALL where they still hold them; bytes not yet measured).  Per model
 // it is the same code: model m gets the bits it gets alone.  The mode is a flag inside the first template argument
 // (F128_MODELS + storage) so that the existing instantiations keep their symbols and their code.
+// ENSEMBLE (moc_meta_forward_dense_models, ensemble patch maps; always with MODELS and DENSE): the model loop over every row,
+// the models reduced on chip.  Model m's mix goes to LDS ([128][C] over the free row tile, C <= 64), not to HBM; each row's
+// softmax(scale * mixed) then updates a Welford mean / M2 per (class, row) kept in the output slots themselves (a.mixed =
+// prob_mean, a.H1 = prob_std or NULL; a.gates = gates_mean or NULL, a running sum), by the thread that owns the slot for
+// every model, in model order: deterministic.  The last model writes mean, sqrt(M2 / R) and sum / R.  Launch bounds of
+// its own: one workgroup per CU fewer than the others (f128_bound), the registers the model loop keeps live.
 constexpr int F128_MODELS = 4;
+constexpr int F128_ENSEMBLE = 8;
+constexpr int F128_ENS_MAX_C = 64;
+constexpr int f128_bound(int stm) { return (stm & F128_ENSEMBLE) ? f128_wgs(stm & 3) - 1 : f128_wgs(stm & 3); }
 template <int STM, bool DENSE = false>
-__global__ __launch_bounds__(256, f128_wgs(STM & 3)) void meta_forward128_kernel(FwdArgs a) {
+__global__ __launch_bounds__(256, f128_bound(STM)) void meta_forward128_kernel(FwdArgs a) {
     constexpr int ST = STM & 3;
     constexpr bool MODELS = (STM & F128_MODELS) != 0;
+    constexpr bool ENS = (STM & F128_ENSEMBLE) != 0;
+    static_assert(!ENS || (MODELS && DENSE), "the ensemble mode is a dense models mode");
     constexpr int F128_KC = f128_kc(ST), F128_BUF = f128_buf(F128_KC), F128_XB = f128_xb(F128_KC);
     constexpr bool F16 = ST == 1;
     constexpr int WPC = 3 * (ST == 2 ? F128_KC / 2 : F128_KC);      // W1 fragments per chunk (three terms per 32 columns)
@@ -920,9 +935,17 @@ __global__ __launch_bounds__(256, f128_wgs(STM & 3)) void meta_forward128_kernel
 next_model:
     if (MODELS && m > 0) {                                 // model m's parameters (model 0's were requested above)
         const int64_t po = (int64_t)m * a.par_stride;
-        w2_pre = a.W2[po + (threadIdx.x & 255)];
-        bias = a.b1[po + wave * 16 + (lane & 15)];
-        b2_pre = a.b2[po + (threadIdx.x & 3)];
+        const float *W2m = a.W2, *b1m = a.b1, *b2m = a.b2;
+        if constexpr (ENS) asm volatile("" : "+s"(W2m), "+s"(b1m), "+s"(b2m));     // (not hoisted: see below)
+        w2_pre = W2m[po + (threadIdx.x & 255)];
+        bias = b1m[po + wave * 16 + (lane & 15)];
+        b2_pre = b2m[po + (threadIdx.x & 3)];
+    }
+    int64_t cstride = a.stride;                            // (the class stride of stats and outputs)
+    if constexpr (ENS) {
+        // what the model loop would otherwise hoist out of it and keep live across the product (the 64-bit addresses of
+        // every class of the row, of the rows): recomputed per model
+        asm volatile("" : "+s"(cstride), "+v"(rp[0]), "+v"(rp[1]), "+v"(ecd));
     }
     const unsigned char* w1img = MODELS ? a.W1img + (int64_t)m * a.img_stride : a.W1img;
     float* mixed = MODELS ? a.mixed + (int64_t)m * C * a.stride : a.mixed;
@@ -1021,7 +1044,7 @@ next_model:
         W2s[threadIdx.x] = w2_pre;
     }
     __syncthreads();
-    if (a.H1) {                          // needed by the backward pass only: evaluation passes NULL
+    if (!ENS && a.H1) {                  // needed by the backward pass only: evaluation passes NULL
         for (int e = threadIdx.x; e < F128_ROWS * H; e += 256) {
             const int r = e >> 6, h = e & 63;
             if (row0 + r < S) a.H1[(base + row0 + r) * H + h] = Hs[r][h];
@@ -1035,9 +1058,20 @@ next_model:
         z += b2_pre;
         const float g = 1.f / (1.f + expf(-z));
         Gs[r][i] = g;
-        if (a.gates && row0 + r < S) a.gates[(base + row0 + r) * 4 + i] = g;
+        if constexpr (ENS) {                               // the running sum over the models; the mean at the last one
+            float* gts = a.gates;
+            asm volatile("" : "+s"(gts));                  // (not hoisted out of the model loop)
+            if (gts && row0 + r < S) {
+                float* gp = gts + (base + row0 + r) * 4 + i;
+                const float sg = m > 0 ? *gp + g : g;
+                *gp = m + 1 == a.n_runs ? sg / (float)a.n_runs : sg;
+            }
+        } else {
+            if (a.gates && row0 + r < S) a.gates[(base + row0 + r) * 4 + i] = g;
+        }
     }
     __syncthreads();
+    float* Ms = reinterpret_cast<float*>(smem);            // ENS: [128][C] mixed scores of this model (over the row tile)
     if (erow_ok && !(diag & 8u)) {
         const float g0 = Gs[er][0], g1 = Gs[er][1], g2 = Gs[er][2], g3 = Gs[er][3];
         for (int cb = 0; cb < C; cb += 16) {
@@ -1046,7 +1080,7 @@ next_model:
 #pragma unroll
                 for (int it = 0; it < 8; ++it) {
                     const int c = cb + ec0 + 2 * it;
-                    if (c < C) es0[it] = ecd[(int64_t)c * a.stride];
+                    if (c < C) es0[it] = ecd[(int64_t)c * cstride];
                 }
             }
             float es1[8];
@@ -1054,7 +1088,7 @@ next_model:
             for (int it = 0; it < 8; ++it) {
                 const int c = cb + ec0 + 2 * it;
                 es1[it] = 0.f;
-                if (c < C) es1[it] = a.cand_mode == 2 ? moc_softmax_from(es0[it], em1, erd) : ecd[(int64_t)(C + c) * a.stride];
+                if (c < C) es1[it] = a.cand_mode == 2 ? moc_softmax_from(es0[it], em1, erd) : ecd[(int64_t)(C + c) * cstride];
             }
 #pragma unroll
             for (int it = 0; it < 8; ++it) {
@@ -1066,9 +1100,51 @@ next_model:
                 if (a.use_bits & 2u) v = moc_fadd(v, moc_fmul(g1, s1));
                 if (a.use_bits & 4u) v = moc_fadd(v, moc_fmul(g2, es2));
                 if (a.use_bits & 8u) v = moc_fadd(v, moc_fmul(g3, es3));
-                mixed[(int64_t)c * a.stride + base + row0 + er] = v;
+                if constexpr (ENS) Ms[er * C + c] = v;
+                else mixed[(int64_t)c * cstride + base + row0 + er] = v;
             }
         }
+    }
+    if constexpr (ENS) {
+        __syncthreads();                                   // the tile's mixed scores are in Ms
+        if (erow_ok) {
+            // softmax(scale * mixed) of row er: both threads of the row form max and sum over all C classes in the same
+            // order (the same bits), then each updates its own classes' Welford state in the output slots
+            const float* mr = Ms + er * C;
+            const float scale = a.ens_scale;
+            float mx = -INFINITY, se = 0.f;
+            for (int c = 0; c < C; ++c) mx = fmaxf(mx, scale * mr[c]);
+            for (int c = 0; c < C; ++c) se += expf(scale * mr[c] - mx);
+            float* __restrict__ pmean = a.mixed + base + row0 + er;
+            float* __restrict__ pm2 = a.H1 ? a.H1 + base + row0 + er : nullptr;
+            const bool last = m + 1 == a.n_runs;
+            const float kf = (float)(m + 1);
+            for (int cb = 0; cb < C; cb += 16) {
+                float mu[8], m2[8];                        // the state of classes cb + ec0 + 2 it, requested together
+#pragma unroll
+                for (int it = 0; it < 8; ++it) {
+                    const int c = cb + ec0 + 2 * it;
+                    mu[it] = 0.f;
+                    m2[it] = 0.f;
+                    if (m > 0 && c < C) {
+                        mu[it] = pmean[(int64_t)c * cstride];
+                        if (pm2) m2[it] = pm2[(int64_t)c * cstride];
+                    }
+                }
+#pragma unroll
+                for (int it = 0; it < 8; ++it) {
+                    const int c = cb + ec0 + 2 * it;
+                    if (c >= C) continue;
+                    const float p = expf(scale * mr[c] - mx) / se;
+                    const float d = p - mu[it];
+                    const float mu1 = m > 0 ? mu[it] + d / kf : p;      // Welford: model 0 sets, M2 stays 0
+                    const float m21 = m > 0 ? m2[it] + d * (p - mu1) : 0.f;
+                    pmean[(int64_t)c * cstride] = mu1;
+                    if (pm2) pm2[(int64_t)c * cstride] = last ? sqrtf(m21 / (float)a.n_runs) : m21;
+                }
+            }
+        }
+        __syncthreads();                                   // Ms read by all: the next model's rows may land over it
     }
     if constexpr (MODELS) {
         if (++m < a.n_runs) goto next_model;
@@ -3306,6 +3382,47 @@ int launch_forward_models(const moc_batch_t* B, const moc_meta_t* M, const moc_r
     return MOC_OK;
 }
 
+// moc_meta_forward_dense_models: the 128-row kernel for R->n_runs meta-learners over every row of slides [slide0, slide0 + n),
+// the models reduced on chip into prob_mean / prob_std / gates_mean
+int launch_forward_dense_models(const moc_batch_t* B, const moc_meta_t* M, const moc_runs_t* R, float scale, float* prob_mean,
+                                float* prob_std, float* gates_mean, int slide0, int n, uint32_t use_bits, hipStream_t s) {
+    FwdArgs a = {};
+    a.base_host = -1;
+    a.S_host = -1;
+    a.X = (const unsigned char*)B->X; a.row_off = B->row_off; a.x_off = B->x_off;
+    a.W1 = M->W1; a.b1 = M->b1; a.W2 = M->W2; a.b2 = M->b2;
+    a.W1img = (const unsigned char*)M->W1_image;
+    a.H1 = prob_std; a.gates = gates_mean; a.mixed = prob_mean; a.stride = B->total_rows;
+    a.D = B->D; a.C = B->C; a.slide0 = slide0; a.use_bits = use_bits & 15u;
+    a.cand_mode = (B->flags & MOC_STATS_COMPACT) ? 2 : 1;
+    a.stats = B->stats;
+    a.n_runs = R->n_runs; a.par_stride = R->par_stride; a.img_stride = R->image_stride;
+    a.ens_scale = scale;
+    int64_t rows = B->max_rows;                            // as launch_forward_dense
+    if (B->row_off_host) {
+        rows = 0;
+        for (int q = slide0; q < slide0 + n; ++q) {
+            const int64_t nq = B->row_off_host[q + 1] - B->row_off_host[q];
+            rows = nq > rows ? nq : rows;
+        }
+    }
+    if (rows <= 0) return MOC_OK;
+    constexpr int E = F128_MODELS + F128_ENSEMBLE;
+    static bool attr = false;
+    if (!attr) {
+        (void)hipFuncSetAttribute((const void*)meta_forward128_kernel<E + 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, f128_lds(f128_kc(0)));
+        (void)hipFuncSetAttribute((const void*)meta_forward128_kernel<E + 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, f128_lds(f128_kc(1)));
+        (void)hipFuncSetAttribute((const void*)meta_forward128_kernel<E + 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, f128_lds(f128_kc(2)));
+        attr = true;
+    }
+    dim3 g(moc_cdiv(rows, F128_ROWS), n);
+    if (B->dtype == MOC_F16) meta_forward128_kernel<E + 1, true><<<g, 256, f128_lds(f128_kc(1)), s>>>(a);
+    else if (B->dtype == MOC_BF16) meta_forward128_kernel<E + 0, true><<<g, 256, f128_lds(f128_kc(0)), s>>>(a);
+    else meta_forward128_kernel<E + 2, true><<<g, 256, f128_lds(f128_kc(2)), s>>>(a);
+    MOC_CHECK_LAUNCH("moc_meta_forward_dense_models");
+    return MOC_OK;
+}
+
 int launch_pool(const moc_batch_t* B, const moc_meta_ws_t* ws, int slide0, int n, hipStream_t s) {
     return moc_launch_topk_mean(ws->mixed, B->total_rows, ws->mixed, B->total_rows, B->row_off, B->n_sel,
                                 slide0, n, B->C, B->topk, 0, ws->pooled, ws->topk_idx, ws->topk_cnt, s);
@@ -3668,6 +3785,38 @@ extern "C" int moc_meta_forward_models(const moc_batch_t* B, const moc_meta_t* M
                                                                     R->image_stride);
     MOC_CHECK_LAUNCH("moc_w1_image(models)");
     return launch_forward_models(B, M, R, mixed, slide0, n, use_bits, s);
+}
+
+extern "C" int moc_meta_forward_dense_models(const moc_batch_t* B, const moc_meta_t* M, const moc_runs_t* R, float scale,
+                                             float* prob_mean, float* prob_std, float* gates_mean, int slide0, int n,
+                                             uint32_t use_bits, moc_stream_t stream) {
+    const char* who = "moc_meta_forward_dense_models";
+    if (int rc = moc_check_batch(B, who)) return rc;
+    MOC_REQUIRE(M, "%s: null meta", who);
+    MOC_REQUIRE(M->H == H, "%s: hidden width %d unsupported (must be %d)", who, M->H, H);
+    MOC_REQUIRE(M->D == B->D, "%s: meta D=%d != batch D=%d", who, M->D, B->D);
+    MOC_REQUIRE(M->W1 && M->b1 && M->W2 && M->b2, "%s: null parameter", who);
+    MOC_REQUIRE(M->W1_image, "%s: W1_image buffer is null (n_runs x image_stride bytes)", who);
+    MOC_REQUIRE(prob_mean, "%s: null prob_mean", who);
+    MOC_REQUIRE(R, "%s: null runs", who);
+    MOC_REQUIRE(R->n_runs >= 1 && R->n_runs <= MOC_MAX_RUNS, "%s: n_runs=%d outside 1 .. %d", who, R->n_runs, MOC_MAX_RUNS);
+    MOC_REQUIRE(R->slide_stride == 0, "%s: slide_stride=%d must be 0 (every model works on the same slides)", who,
+                R->slide_stride);
+    MOC_REQUIRE(R->par_stride >= (int64_t)H * B->D + H + 4 * H + 4, "%s: par_stride=%lld smaller than one meta-learner", who,
+                (long long)R->par_stride);
+    MOC_REQUIRE(R->image_stride >= (int64_t)moc_w1_image_bytes(B->D, B->dtype), "%s: image_stride=%lld < moc_w1_image_bytes=%lld",
+                who, (long long)R->image_stride, (long long)moc_w1_image_bytes(B->D, B->dtype));
+    MOC_REQUIRE(B->C <= F128_ENS_MAX_C, "%s: C=%d > %d (a tile's mixed scores are reduced in LDS)", who, B->C, F128_ENS_MAX_C);
+    MOC_REQUIRE(std::isfinite(scale), "%s: scale=%g is not finite", who, (double)scale);
+    MOC_REQUIRE(!B->mask, "%s: the batch is masked (slots are not rows); run it unmasked", who);
+    MOC_REQUIRE(B->stats, "%s: the batch has no statistics (run the score pass first)", who);
+    MOC_REQUIRE(slide0 >= 0 && n >= 1 && slide0 + n <= B->n_slides, "%s: bad slide range", who);
+    hipStream_t s = (hipStream_t)stream;
+    // every model's image, rebuilt from its parameters (grid.y = model)
+    w1_image_kernel<<<dim3(H * B->D / 256, R->n_runs), 256, 0, s>>>(M->W1, B->D, (unsigned char*)M->W1_image, B->dtype, R->par_stride,
+                                                                    R->image_stride);
+    MOC_CHECK_LAUNCH("moc_w1_image(dense models)");
+    return launch_forward_dense_models(B, M, R, scale, prob_mean, prob_std, gates_mean, slide0, n, use_bits, s);
 }
 
 extern "C" int moc_mix_fixed(const moc_batch_t* B, const moc_meta_ws_t* ws, int slide0, int n, int mode,

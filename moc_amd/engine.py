@@ -830,6 +830,27 @@ def meta_forward_models(batch: SlideBatch, params: ModelArena, n_models: int, mi
                                         _stream()), "moc_meta_forward_models")
 
 
+def meta_forward_dense_models(batch: SlideBatch, params: ModelArena, n_models: int, scale: float, prob_mean: torch.Tensor,
+                              prob_std: torch.Tensor | None, gates_mean: torch.Tensor | None, slide0: int, n: int,
+                              use_bits: int):
+    """Ensemble patch maps: the dense forward of n_models meta-learners (the first n_models of `params`) over EVERY row of
+    slides slide0 .. +n of an unmasked batch whose score pass has run, reduced over the models on the device --
+    prob_mean / prob_std [C, total]: mean and population std of softmax(scale * mixed_r); gates_mean [total, 4]: the mean
+    gates (moc_meta_forward_dense_models).  prob_std and gates_mean may be None."""
+    T = batch.total
+    assert batch.mask is None, "meta_forward_dense_models: the batch must be unmasked"
+    assert 1 <= n_models <= params.R and params.D == batch.D, "meta_forward_dense_models: models / width do not match"
+    assert prob_mean is not None, "meta_forward_dense_models: prob_mean is required"
+    for t, shape in ((prob_mean, (batch.C, T)), (prob_std, (batch.C, T)), (gates_mean, (T, 4))):
+        if t is not None:
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape
+    runs = MocRuns.from_buffer_copy(params.runs)
+    runs.n_runs = n_models
+    check(lib().moc_meta_forward_dense_models(C.byref(batch.c), C.byref(params.c), C.byref(runs), float(scale),
+                                              ptr(prob_mean), ptr(prob_std), ptr(gates_mean), slide0, n, use_bits,
+                                              _stream()), "moc_meta_forward_dense_models")
+
+
 def pool_models(batch: SlideBatch, mixed: torch.Tensor, labels: torch.Tensor, slide0: int, n: int):
     """moc_pool_loss over every model's slab of `mixed` [R, C, total] -> dict of per-model pooled [R, n_slides, C], pred,
     loss [R, n_slides] and topk_idx / topk_cnt (labels: device int64 [n_slides]; zeros for unlabeled slides -- the loss

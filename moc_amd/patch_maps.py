@@ -115,13 +115,51 @@ def slide_id_of(path: str) -> str:
 def write_patch_maps(maps, out_dir, slide_ids=None):
     """One `<slide_id>.npz` per map (its fields, plus evidence_coords [C, k, 2] = coords of the evidence rows) and
     `index.json`: slide id -> label, pred, probabilities, file.  slide_ids default to the bag file names."""
+    return _write_maps(maps, PatchMap, out_dir, slide_ids, lambda m: probabilities(m.pooled))
+
+
+def load_patch_map(path) -> PatchMap:
+    """A PatchMap back from a `<slide_id>.npz` of write_patch_maps (fields absent from the file: None)."""
+    return _load_map(path, PatchMap)
+
+
+@dataclass
+class EnsembleMap:
+    """One slide's map of an ensemble of R meta-learners (moc_amd.predict --patch_maps); host numpy arrays, N = patches of
+    the slide, k = min(topk, N) (evidence: min(topk, S))."""
+    path: str
+    label: int                           # -1: unlabeled
+    pred: int                            # argmax of `probabilities`
+    probabilities: np.ndarray            # [C] float32: the ensemble's slide probabilities (predictions.csv's row)
+    pooled: np.ndarray                   # [R, C] float32: each model's pooled logits
+    coords: np.ndarray                   # [N, 2] int64
+    logits: np.ndarray                   # [N, C] float32 zero-shot scores
+    selected: np.ndarray                 # [N] bool: union membership
+    zs_evidence: np.ndarray              # [C, k] int64: top-K rows by zero-shot logit
+    prob_mean: np.ndarray                # [N, C] float32: mean over models of softmax(56.3477 * meta score)
+    prob_std: np.ndarray                 # [N, C] float32: their population std -- where the models disagree
+    gates_mean: np.ndarray               # [N, 4] float32: mean gates
+    evidence: np.ndarray                 # [R, C, k] int64: bag rows of each model's pooled top-K (ranked as in PatchMap)
+
+
+def write_ensemble_maps(maps, out_dir, slide_ids=None):
+    """write_patch_maps for EnsembleMaps: `<slide_id>.npz` (fields, evidence_coords [R, C, k, 2], zs_evidence_coords) and
+    index.json with the ensemble's probabilities."""
+    return _write_maps(maps, EnsembleMap, out_dir, slide_ids, lambda m: m.probabilities)
+
+
+def load_ensemble_map(path) -> EnsembleMap:
+    return _load_map(path, EnsembleMap)
+
+
+def _write_maps(maps, cls, out_dir, slide_ids, probs_of):
     os.makedirs(out_dir, exist_ok=True)
     slide_ids = [slide_id_of(m.path) for m in maps] if slide_ids is None else list(slide_ids)
     assert len(slide_ids) == len(maps) and len(set(slide_ids)) == len(slide_ids), "one distinct slide id per map"
     index = {}
     for sid, m in zip(slide_ids, maps):
         arrays = {}
-        for f in fields(PatchMap):
+        for f in fields(cls):
             val = getattr(m, f.name)
             if val is None:
                 continue
@@ -132,17 +170,16 @@ def write_patch_maps(maps, out_dir, slide_ids=None):
         fname = f"{sid}.npz"
         np.savez(os.path.join(out_dir, fname), **arrays)
         index[sid] = {"label": int(m.label), "pred": int(m.pred),
-                      "probabilities": [float(p) for p in probabilities(m.pooled)], "file": fname}
+                      "probabilities": [float(p) for p in probs_of(m)], "file": fname}
     with open(os.path.join(out_dir, "index.json"), "w") as f:
         json.dump(index, f, indent=2)
     return index
 
 
-def load_patch_map(path) -> PatchMap:
-    """A PatchMap back from a `<slide_id>.npz` of write_patch_maps (fields absent from the file: None)."""
+def _load_map(path, cls):
     with np.load(path, allow_pickle=False) as z:
         kw = {}
-        for f in fields(PatchMap):
+        for f in fields(cls):
             if f.name not in z.files:
                 continue
             a = z[f.name]
@@ -151,4 +188,4 @@ def load_patch_map(path) -> PatchMap:
             elif f.name in ("label", "pred"):
                 a = int(a)
             kw[f.name] = a
-    return PatchMap(**kw)
+    return cls(**kw)

@@ -18,6 +18,10 @@ probabilities (main_moc.py:505, patch_maps.probabilities).
 --data_dir (h5_files/, pt_files/ or npy_files/).  The zero-shot bank is the --dataset's, from --root as run_moc loads it.
 Writes DIR/predictions.csv (one row per slide) and DIR/predictions.json (arguments, checkpoints, and with labels the
 per-model and ensemble loss / acc / AUC).
+
+--patch_maps adds DIR/patch_maps/<slide_id>.npz and index.json (patch_maps.EnsembleMap) from the same pass: after the pooling,
+moc_meta_forward_dense_models gives every patch the mean and population std over the models of softmax(56.3477 * meta
+score) and the mean gates, the per-model slabs never leaving the device; the zero-shot half is patch_maps' (moc_topk_mean).
 """
 from __future__ import annotations
 
@@ -46,6 +50,7 @@ class Predictions:
     pred: np.ndarray                     # [N] int64: argmax of the ensemble
     labels: np.ndarray | None = None     # [N] int64 when known
     loss: np.ndarray | None = None       # [R, N] float32: per-model cross entropy (moc_pool_loss) when labels are known
+    maps: list | None = None             # N patch_maps.EnsembleMap (predict(..., maps=True))
 
 
 def _probs(pooled: np.ndarray) -> np.ndarray:
@@ -54,18 +59,20 @@ def _probs(pooled: np.ndarray) -> np.ndarray:
     return torch.softmax(t * CONCH_TEMPERATURE, dim=-1).numpy()
 
 
-def predict(state_dicts, loader, device, args, labeled: bool = True, slide_ids=None) -> Predictions:
+def predict(state_dicts, loader, device, args, labeled: bool = True, slide_ids=None, maps: bool = False) -> Predictions:
     """Predictions of the R = len(state_dicts) meta-learners (senet(D, 4) state_dicts) over `loader` (a ResidentBags
     split or a loader of (features, label, coords, path) items), in one pass.  labeled=False: the loader's labels are
-    placeholders (zeros) and are neither reported nor used."""
+    placeholders (zeros) and are neither reported nor used.  maps=True: also the ensemble patch map of every slide
+    (Predictions.maps), from the same pass."""
     from . import engine
     from . import main_moc as M
-    from .patch_maps import slide_id_of
+    from .patch_maps import EnsembleMap, slide_id_of
     R = len(state_dicts)
     assert 1 <= R <= MAX_MODELS, f"predict: 1 .. {MAX_MODELS} checkpoints"
     ds = loader.dataset
     set_len = len(ds)
     pooled, losses, labels = [], [], []
+    parts = []                                             # maps: per slide, everything but the ensemble's probabilities
     with torch.no_grad():
         ds.repeat_num = ds.real_len()
         try:
@@ -74,6 +81,10 @@ def predict(state_dicts, loader, device, args, labeled: bool = True, slide_ids=N
             bank, batches = M._eval_batches(loader, device, args, "eval", extras=extras)
             arena = engine.ModelArena(state_dicts, device)
             use_bits = engine.eval_use_bits(args.discard_classifiers)
+            if maps and bank.C > 64:
+                raise SystemExit(f"--patch_maps: {bank.C} classes; the ensemble maps take at most 64")
+            K = int(args.topk)
+            v = 0
             for batch, lab, lab_list in batches:
                 n = batch.n_slides
                 batch.phase_a(bank, for_eval=True)
@@ -81,8 +92,38 @@ def predict(state_dicts, loader, device, args, labeled: bool = True, slide_ids=N
                 engine.meta_forward_models(batch, arena, R, mixed, 0, n, use_bits)
                 lab_d = lab if labeled else torch.zeros_like(lab)
                 out = engine.pool_models(batch, mixed, lab_d, 0, n)
-                pooled.append(out["pooled"].cpu().numpy())
-                losses.append(out["loss"].cpu().numpy())
+                if maps:
+                    T = batch.total
+                    pm = torch.empty((batch.C, T), dtype=torch.float32, device=batch.device)
+                    ps = torch.empty((batch.C, T), dtype=torch.float32, device=batch.device)
+                    gm = torch.empty((T, 4), dtype=torch.float32, device=batch.device)
+                    engine.meta_forward_dense_models(batch, arena, R, M.CONCH_TEMPERATURE, pm, ps, gm, 0, n, use_bits)
+                    logits_d = batch.stats[:batch.C]
+                    _, zs_idx, zs_cnt = engine.topk_mean(logits_d, logits_d, K, want_idx=True, seg_off=batch.row_off)
+                    dev_arrays = {"logits": logits_d, "sel_flag": batch.sel_flag, "zs_idx": zs_idx, "zs_cnt": zs_cnt,
+                                  "prob_mean": pm, "prob_std": ps, "gates_mean": gm, "sel_idx": batch.sel_idx,
+                                  "topk_idx": out["topk_idx"], "topk_cnt": out["topk_cnt"], "pooled": out["pooled"]}
+                    h = {k: t.cpu().numpy() for k, t in dev_arrays.items()}     # one copy of each array per chunk
+                    for b in range(n):
+                        o, N = batch.row_off_host[b], batch.sizes[b]
+                        coords, path = extras[v]
+                        v += 1
+                        kz, kk = int(h["zs_cnt"][b, 0]), int(h["topk_cnt"][0, b, 0])
+                        parts.append(dict(
+                            path=path, label=int(lab_list[b]) if labeled else -1, pooled=h["pooled"][:, b].copy(),
+                            coords=np.asarray(coords, dtype=np.int64).reshape(N, 2).copy(),
+                            logits=np.ascontiguousarray(h["logits"][:, o:o + N].T),
+                            selected=h["sel_flag"][o:o + N].astype(bool),
+                            zs_evidence=h["zs_idx"][b, :, :kz].astype(np.int64),
+                            prob_mean=np.ascontiguousarray(h["prob_mean"][:, o:o + N].T),
+                            prob_std=np.ascontiguousarray(h["prob_std"][:, o:o + N].T),
+                            gates_mean=h["gates_mean"][o:o + N].copy(),
+                            evidence=h["sel_idx"][o + h["topk_idx"][:, b, :, :kk]].astype(np.int64)))
+                    pooled.append(h["pooled"])
+                    losses.append(out["loss"].cpu().numpy())
+                else:
+                    pooled.append(out["pooled"].cpu().numpy())
+                    losses.append(out["loss"].cpu().numpy())
                 labels.extend(lab_list)
         finally:
             ds.repeat_num = set_len
@@ -92,11 +133,12 @@ def predict(state_dicts, loader, device, args, labeled: bool = True, slide_ids=N
     ens = probs.mean(axis=0, dtype=np.float64).astype(np.float32)
     C = pooled.shape[2]
     names = list(getattr(args, "class_names", None) or [str(c) for c in range(C)])
+    pred = ens.argmax(axis=1).astype(np.int64)
+    emaps = [EnsembleMap(pred=int(pred[i]), probabilities=ens[i].copy(), **d) for i, d in enumerate(parts)] if maps else None
     return Predictions(slide_ids=list(slide_ids) if slide_ids is not None else [slide_id_of(p) for p in paths],
                        paths=paths, classes=names, pooled=pooled, probs=probs, ensemble=ens,
-                       pred=ens.argmax(axis=1).astype(np.int64),
-                       labels=np.asarray(labels, dtype=np.int64) if labeled else None,
-                       loss=np.concatenate(losses, axis=1) if labeled else None)
+                       pred=pred, labels=np.asarray(labels, dtype=np.int64) if labeled else None,
+                       loss=np.concatenate(losses, axis=1) if labeled else None, maps=emaps)
 
 
 def metrics(p: Predictions, args, n_div=None) -> dict:
@@ -179,6 +221,9 @@ def get_args(argv=None):
     p.add_argument("--discard_classifiers", nargs="+", default=[])
     p.add_argument("--bag_dtype", default="fp32", choices=["fp32", "bf16", "fp16"])
     p.add_argument("--disable_tqdm", action="store_true")
+    p.add_argument("--patch_maps", action="store_true",
+                   help="also write OUT/patch_maps/<slide_id>.npz + index.json: the ensemble's per-patch probabilities "
+                        "(mean, std over the models), mean gates and each model's evidence, from the same pass")
     a = p.parse_args(argv)
     a.pretrain = "conch"
     return a
@@ -289,12 +334,15 @@ def cli(argv=None):
         loader = run_moc.prepare(ra, device)[SPLITS.index(a.split)]
         a.n_classes, labeled, ids = ra.n_classes, True, None
     a.class_names = _class_names(a, a.n_classes)
-    p = predict(sds, loader, device, a, labeled=labeled, slide_ids=ids)
+    p = predict(sds, loader, device, a, labeled=labeled, slide_ids=ids, maps=a.patch_maps)
     info = {"args": {k: getattr(a, k) for k in ("slides", "data_dir", "synthetic", "dataset", "shot", "fold", "split", "root",
                                                 "topj", "topk", "discard_classifiers", "bag_dtype")},
             "checkpoints": [os.path.abspath(c) for c in a.ckpt]}
     m = metrics(p, a, n_div=len(loader.dataset)) if labeled else None
     write_predictions(p, a.out, info, m)
+    if a.patch_maps:
+        from .patch_maps import write_ensemble_maps
+        write_ensemble_maps(p.maps, os.path.join(a.out, "patch_maps"), p.slide_ids)
     print(f"predict: {len(p.slide_ids)} slides x {len(sds)} model(s) -> {a.out}" + (f"; ensemble {m['ensemble']}" if m else ""))
     return p, m
 
