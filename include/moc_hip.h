@@ -336,6 +336,24 @@ int moc_train_runs_mode(const moc_batch_t* B, const moc_meta_ws_t* ws);
 int moc_meta_forward_models(const moc_batch_t* B, const moc_meta_t* M, const moc_runs_t* R, float* mixed,
                             int slide0, int n, uint32_t use_bits, moc_stream_t stream);
 
+/* Evaluation of several runs in one pass (ABI 20, additive): the evaluation forward of moc_meta_forward over the union rows
+ * of slides [slide0, slide0 + n) of an UNMASKED batch whose phase A has run, in ONE launch, in which every slide names the
+ * meta-learner that scores it: slide b is scored by model model_of_slide[b] (device int32 [B->n_slides], indexed by the
+ * slide's position in the batch, values 0 .. R->n_runs - 1).  Model r's parameters lie r * R->par_stride floats behind M's,
+ * its W1 image r * R->image_stride bytes behind M->W1_image (the arena layout of moc_train_steps_runs and
+ * moc_meta_forward_models; the images of all n_runs models are rebuilt here).  R->slide_stride must be 0.  ws->mixed is
+ * written at the union slots of the n slides exactly as moc_meta_forward writes it (ws->H1 / ws->gates too when they are not
+ * NULL), so one moc_pool_loss then pools all slides: for a slide of model r the mixed scores are, bit for bit, what
+ * moc_meta_forward gives with model r alone.  Always the 128-row evaluation kernel, whatever the shape (the smaller
+ * evaluation kernels give the same bits).  An index outside 0 .. n_runs - 1 is CLAMPED into that range on the device (the
+ * slide is then scored by model 0 or n_runs - 1): nothing is read outside the arenas.
+ * Errors (not faults), before anything is launched: a masked batch, no phase-A outputs, null model_of_slide, null ws or
+ * ws->mixed, n_runs outside 1 .. 16, nonzero slide_stride, par_stride / image_stride smaller than one model, meta D != batch
+ * D, a bad slide range.  use_bits as for moc_meta_forward. */
+int moc_meta_forward_by_slide(const moc_batch_t* B, const moc_meta_t* M, const moc_runs_t* R,
+                              const int32_t* model_of_slide, const moc_meta_ws_t* ws, int slide0, int n, uint32_t use_bits,
+                              moc_stream_t stream);
+
 /* Ensemble patch maps (ABI 20, additive): the dense forward of moc_meta_forward_dense for R->n_runs models (1 .. 16) over
  * EVERY row of slides [slide0, slide0 + n) of an UNMASKED batch whose score pass has run, the models reduced on the device.
  * With p_r = softmax_c(scale * mixed_r) of model r alone (scale: the evaluation temperature, 56.3477):

@@ -84,6 +84,7 @@ SIGNATURES = {
     "moc_meta_forward": (C.c_int, [_BP, _MP, _WP, C.c_int, C.c_int, C.c_uint32, _p]),
     "moc_meta_forward_dense": (C.c_int, [_BP, _MP, _p, _p, C.c_int, C.c_int, C.c_uint32, _p]),
     "moc_meta_forward_models": (C.c_int, [_BP, _MP, C.POINTER(MocRuns), _p, C.c_int, C.c_int, C.c_uint32, _p]),
+    "moc_meta_forward_by_slide": (C.c_int, [_BP, _MP, C.POINTER(MocRuns), _p, _WP, C.c_int, C.c_int, C.c_uint32, _p]),
     "moc_meta_forward_dense_models": (C.c_int, [_BP, _MP, C.POINTER(MocRuns), C.c_float, _p, _p, _p, C.c_int, C.c_int,
                                                 C.c_uint32, _p]),
     "moc_mix_fixed": (C.c_int, [_BP, _WP, C.c_int, C.c_int, C.c_int, _p]),

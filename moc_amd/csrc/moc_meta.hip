@@ -159,7 +159,11 @@ struct FwdArgs {
     int32_t S_r[MOC_MAX_RUNS];
     // the dense forward (moc_meta_forward_dense: every row of a slide, no sel_row gather): first row of each slide in X,
     // or NULL = row_off.  Unread by every other launch.
-    const int64_t* x_off;
+    union {
+        const int64_t* x_off;
+        // moc_meta_forward_by_slide (never dense): the model that scores each slide of the batch, device [n_slides]
+        const int32_t* model_of_slide;
+    };
 };
 
 // An entry of an array inside the kernel's (single, by-value) argument struct, read straight from the kernel-argument
@@ -858,8 +862,14 @@ __device__ __forceinline__ void fwd_touch4(fu32x4_t (&v)[4]) {
 // prob_mean, a.H1 = prob_std or NULL; a.gates = gates_mean or NULL, a running sum), by the thread that owns the slot for
 // every model, in model order: deterministic.  The last model writes mean, sqrt(M2 / R) and sum / R.  Launch bounds of
 // its own: one workgroup per CU fewer than the others (f128_bound), the registers the model loop keeps live.
+// BY_SLIDE (moc_meta_forward_by_slide, the evaluation of several runs in one pass; never with MODELS or DENSE): ONE model per
+// slide -- a workgroup works on one slide, so its model a.model_of_slide[b] is uniform: one scalar load, clamped into
+// 0 .. a.n_runs - 1.  Only the bases differ (the parameters par_stride floats, the W1 image img_stride bytes behind model
+// 0's); the outputs are where moc_meta_forward puts them.  Everything after the bases is the same code: a slide of model r
+// gets the bits it gets from moc_meta_forward with model r alone.
 constexpr int F128_MODELS = 4;
 constexpr int F128_ENSEMBLE = 8;
+constexpr int F128_BY_SLIDE = 16;
 constexpr int F128_ENS_MAX_C = 64;
 constexpr int f128_bound(int stm) { return (stm & F128_ENSEMBLE) ? f128_wgs(stm & 3) - 1 : f128_wgs(stm & 3); }
 template <int STM, bool DENSE = false>
@@ -867,7 +877,9 @@ __global__ __launch_bounds__(256, f128_bound(STM)) void meta_forward128_kernel(F
     constexpr int ST = STM & 3;
     constexpr bool MODELS = (STM & F128_MODELS) != 0;
     constexpr bool ENS = (STM & F128_ENSEMBLE) != 0;
+    constexpr bool BYS = (STM & F128_BY_SLIDE) != 0;
     static_assert(!ENS || (MODELS && DENSE), "the ensemble mode is a dense models mode");
+    static_assert(!BYS || (!MODELS && !DENSE), "a model per slide: the union rows, one model each");
     constexpr int F128_KC = f128_kc(ST), F128_BUF = f128_buf(F128_KC), F128_XB = f128_xb(F128_KC);
     constexpr bool F16 = ST == 1;
     constexpr int WPC = 3 * (ST == 2 ? F128_KC / 2 : F128_KC);      // W1 fragments per chunk (three terms per 32 columns)
@@ -908,6 +920,17 @@ __global__ __launch_bounds__(256, f128_bound(STM)) void meta_forward128_kernel(F
     float w2_pre = a.W2[threadIdx.x & 255];               // (MODELS: model 0's; the others' at the top of their turn)
     float bias = a.b1[wave * 16 + (lane & 15)];
     float b2_pre = a.b2[threadIdx.x & 3];
+    int bys_m = 0;
+    if constexpr (BYS) {
+        // this slide's model, uniform over the workgroup (one scalar load), clamped: nothing is read outside the arenas.
+        // (Statements of this mode alone, not an offset folded into the lines above: a zero offset there changed the
+        // register allocation of the existing instantiations.)
+        bys_m = min(max(a.model_of_slide[b], 0), a.n_runs - 1);
+        const int64_t po = (int64_t)bys_m * a.par_stride;
+        w2_pre = a.W2[po + (threadIdx.x & 255)];
+        bias = a.b1[po + wave * 16 + (lane & 15)];
+        b2_pre = a.b2[po + (threadIdx.x & 3)];
+    }
     const int64_t row_bytes = (int64_t)a.D * ESZ;
     const int KK = (int)(row_bytes / 64), nchunk = KK / F128_KC;      // k-steps of 64 bytes of a row
     // this wave fetches row tiles 2 wave, 2 wave + 1 of the workgroup: lane l = row (l & 15), 16-B piece (l >> 4) of a k-step
@@ -948,6 +971,7 @@ next_model:
         asm volatile("" : "+s"(cstride), "+v"(rp[0]), "+v"(rp[1]), "+v"(ecd));
     }
     const unsigned char* w1img = MODELS ? a.W1img + (int64_t)m * a.img_stride : a.W1img;
+    if constexpr (BYS) w1img += (int64_t)bys_m * a.img_stride;
     float* mixed = MODELS ? a.mixed + (int64_t)m * C * a.stride : a.mixed;
     const fu32x4_t* wimg = reinterpret_cast<const fu32x4_t*>(w1img) + (size_t)wave * (a.D / 32) * 3 * 64 + lane;
     auto load_w = [&](int c, fu32x4_t (&wv)[WPC]) {
@@ -3382,6 +3406,41 @@ int launch_forward_models(const moc_batch_t* B, const moc_meta_t* M, const moc_r
     return MOC_OK;
 }
 
+// moc_meta_forward_by_slide: the 128-row kernel over the union rows of slides [slide0, slide0 + n), every slide with the
+// meta-learner model_of_slide names for it.  Always this kernel (launch_forward would take the 64-row, 16-row or column-split
+// kernels for few slides or few selectable rows; they give the same bits, so only this one has the mode)
+int launch_forward_by_slide(const moc_batch_t* B, const moc_meta_t* M, const moc_runs_t* R, const int32_t* model_of_slide,
+                            const moc_meta_ws_t* ws, int slide0, int n, uint32_t use_bits, hipStream_t s) {
+    FwdArgs a = {};
+    a.base_host = -1;
+    a.S_host = -1;
+    a.X = (const unsigned char*)B->X; a.row_off = B->row_off; a.sel_row = B->sel_row; a.n_sel = B->n_sel;
+    a.cand = B->cand; a.W1 = M->W1; a.b1 = M->b1; a.W2 = M->W2; a.b2 = M->b2;
+    a.W1img = (const unsigned char*)M->W1_image;
+    a.H1 = ws->H1; a.gates = ws->gates; a.mixed = ws->mixed; a.stride = B->total_rows;
+    a.D = B->D; a.C = B->C; a.slide0 = slide0; a.use_bits = use_bits & 15u;
+    if (B->flags & MOC_CAND_FROM_STATS) {
+        a.cand_mode = (B->flags & MOC_STATS_COMPACT) ? 2 : 1;
+        a.stats = B->stats; a.sel_idx = B->sel_idx;
+    }
+    a.n_runs = R->n_runs; a.par_stride = R->par_stride; a.img_stride = R->image_stride;
+    a.model_of_slide = model_of_slide;
+    constexpr int Y = F128_BY_SLIDE;
+    static bool attr = false;
+    if (!attr) {
+        (void)hipFuncSetAttribute((const void*)meta_forward128_kernel<Y + 0>, hipFuncAttributeMaxDynamicSharedMemorySize, f128_lds(f128_kc(0)));
+        (void)hipFuncSetAttribute((const void*)meta_forward128_kernel<Y + 1>, hipFuncAttributeMaxDynamicSharedMemorySize, f128_lds(f128_kc(1)));
+        (void)hipFuncSetAttribute((const void*)meta_forward128_kernel<Y + 2>, hipFuncAttributeMaxDynamicSharedMemorySize, f128_lds(f128_kc(2)));
+        attr = true;
+    }
+    dim3 g(moc_cdiv(s_bound(B), F128_ROWS), n);
+    if (B->dtype == MOC_F16) meta_forward128_kernel<Y + 1><<<g, 256, f128_lds(f128_kc(1)), s>>>(a);
+    else if (B->dtype == MOC_BF16) meta_forward128_kernel<Y + 0><<<g, 256, f128_lds(f128_kc(0)), s>>>(a);
+    else meta_forward128_kernel<Y + 2><<<g, 256, f128_lds(f128_kc(2)), s>>>(a);
+    MOC_CHECK_LAUNCH("moc_meta_forward_by_slide");
+    return MOC_OK;
+}
+
 // moc_meta_forward_dense_models: the 128-row kernel for R->n_runs meta-learners over every row of slides [slide0, slide0 + n),
 // the models reduced on chip into prob_mean / prob_std / gates_mean
 int launch_forward_dense_models(const moc_batch_t* B, const moc_meta_t* M, const moc_runs_t* R, float scale, float* prob_mean,
@@ -3785,6 +3844,38 @@ extern "C" int moc_meta_forward_models(const moc_batch_t* B, const moc_meta_t* M
                                                                     R->image_stride);
     MOC_CHECK_LAUNCH("moc_w1_image(models)");
     return launch_forward_models(B, M, R, mixed, slide0, n, use_bits, s);
+}
+
+extern "C" int moc_meta_forward_by_slide(const moc_batch_t* B, const moc_meta_t* M, const moc_runs_t* R,
+                                         const int32_t* model_of_slide, const moc_meta_ws_t* ws, int slide0, int n,
+                                         uint32_t use_bits, moc_stream_t stream) {
+    const char* who = "moc_meta_forward_by_slide";
+    if (int rc = moc_check_batch(B, who)) return rc;
+    MOC_REQUIRE(M, "%s: null meta", who);
+    MOC_REQUIRE(M->H == H, "%s: hidden width %d unsupported (must be %d)", who, M->H, H);
+    MOC_REQUIRE(M->D == B->D, "%s: meta D=%d != batch D=%d", who, M->D, B->D);
+    MOC_REQUIRE(M->W1 && M->b1 && M->W2 && M->b2, "%s: null parameter", who);
+    MOC_REQUIRE(M->W1_image, "%s: W1_image buffer is null (n_runs x image_stride bytes)", who);
+    MOC_REQUIRE(model_of_slide, "%s: null model_of_slide", who);
+    MOC_REQUIRE(ws && ws->mixed, "%s: null work arrays / mixed", who);
+    MOC_REQUIRE(R, "%s: null runs", who);
+    MOC_REQUIRE(R->n_runs >= 1 && R->n_runs <= MOC_MAX_RUNS, "%s: n_runs=%d outside 1 .. %d", who, R->n_runs, MOC_MAX_RUNS);
+    MOC_REQUIRE(R->slide_stride == 0, "%s: slide_stride=%d must be 0 (model_of_slide says which slide is whose)", who,
+                R->slide_stride);
+    MOC_REQUIRE(R->par_stride >= (int64_t)H * B->D + H + 4 * H + 4, "%s: par_stride=%lld smaller than one meta-learner", who,
+                (long long)R->par_stride);
+    MOC_REQUIRE(R->image_stride >= (int64_t)moc_w1_image_bytes(B->D, B->dtype), "%s: image_stride=%lld < moc_w1_image_bytes=%lld",
+                who, (long long)R->image_stride, (long long)moc_w1_image_bytes(B->D, B->dtype));
+    MOC_REQUIRE(!B->mask, "%s: the batch is masked; run it unmasked (an evaluation pass)", who);
+    MOC_REQUIRE(B->stats && B->sel_row && B->n_sel && B->sel_idx, "%s: the batch has no phase-A outputs (run moc_phase_a first)", who);
+    MOC_REQUIRE((B->flags & MOC_CAND_FROM_STATS) || B->cand, "%s: the batch has no candidate scores", who);
+    MOC_REQUIRE(slide0 >= 0 && n >= 1 && slide0 + n <= B->n_slides, "%s: bad slide range", who);
+    hipStream_t s = (hipStream_t)stream;
+    // every model's image, rebuilt from its parameters (grid.y = model)
+    w1_image_kernel<<<dim3(H * B->D / 256, R->n_runs), 256, 0, s>>>(M->W1, B->D, (unsigned char*)M->W1_image, B->dtype, R->par_stride,
+                                                                    R->image_stride);
+    MOC_CHECK_LAUNCH("moc_w1_image(by slide)");
+    return launch_forward_by_slide(B, M, R, model_of_slide, ws, slide0, n, use_bits, s);
 }
 
 extern "C" int moc_meta_forward_dense_models(const moc_batch_t* B, const moc_meta_t* M, const moc_runs_t* R, float scale,

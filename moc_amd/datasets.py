@@ -52,6 +52,22 @@ def read_bag(data_dir: str, slide_id: str):
     raise FileNotFoundError(f"no bag for slide {slide_id!r} under {data_dir} (h5_files/, pt_files/, npy_files/)")
 
 
+def bag_rows(data_dir: str, slide_id: str, D: int = 512) -> int:
+    """Patches of a slide WITHOUT reading its features (for a memory estimate before anything is loaded): the shape of the
+    h5 / npy array; for a .pt file an upper bound from its size on disk (fp32 rows of D values)."""
+    h5p = os.path.join(data_dir, "h5_files", f"{slide_id}.h5")
+    if h5py is not None and os.path.exists(h5p):
+        with h5py.File(h5p, "r") as f:
+            return int(f["features"].shape[0])
+    ptp = os.path.join(data_dir, "pt_files", f"{slide_id}.pt")
+    if os.path.exists(ptp):
+        return max(1, os.path.getsize(ptp) // (4 * D))
+    npp = os.path.join(data_dir, "npy_files", f"{slide_id}.npy")
+    if os.path.exists(npp):
+        return int(np.load(npp, mmap_mode="r").shape[0])
+    raise FileNotFoundError(f"no bag for slide {slide_id!r} under {data_dir} (h5_files/, pt_files/, npy_files/)")
+
+
 class Generic_Split:
     """One of train/val/test (dataset_generic.py:484-504 + the inherited item access)."""
 

@@ -410,8 +410,11 @@ class SlideBatch:
             dev, T, n, Cc, K = self.device, self.total, self.n_slides, self.C, self.topk
             f32 = dict(dtype=torch.float32, device=dev)
             i32 = dict(dtype=torch.int32, device=dev)
+            # (eval_only: a batch that only ever runs the evaluation forward -- H1 and the gates, 272 bytes per row that only
+            # the backward pass reads, are not allocated; the forward is then always called without them)
+            hidden = not getattr(self, "eval_only", False)
             t = dict(
-                H1=torch.empty((T, HIDDEN), **f32), gates=torch.empty((T, 4), **f32),
+                H1=torch.empty((T, HIDDEN), **f32) if hidden else None, gates=torch.empty((T, 4), **f32) if hidden else None,
                 mixed=torch.empty((Cc, T), **f32), pooled=torch.empty((n, Cc), **f32),
                 topk_idx=torch.empty((n, Cc, K), **i32), topk_cnt=torch.empty((n, Cc), **i32),
                 loss=torch.empty(n, **f32), pred=torch.empty(n, **i32),
@@ -788,30 +791,84 @@ class ModelArena:
     model r's W1 | b1 | W2 | b2 at row r of one [R, par_stride] fp32 arena, its W1 operand image at row r of an
     [R, image_stride] byte arena (the entry rebuilds the images).  `c`: the moc_meta_t of model 0, `runs`: the moc_runs_t."""
 
+    KEYS = ("model.0.weight", "model.0.bias", "model.2.weight", "model.2.bias")
+    MAX_MODELS = 64          # of_models (an entry point takes sixteen of them per call: `group`)
+
+    @staticmethod
+    def layout(D):
+        """(offsets of W1 | b1 | W2 | b2 inside a model's block, floats of one model, shapes)."""
+        offs = (0, HIDDEN * D, HIDDEN * D + HIDDEN, HIDDEN * D + HIDDEN + 4 * HIDDEN)
+        return offs, offs[3] + 4, ((HIDDEN, D), (HIDDEN,), (4, HIDDEN), (4,))
+
     def __init__(self, state_dicts, device):
         R = len(state_dicts)
         assert 1 <= R <= 16, "ModelArena: 1 .. 16 models"
-        keys = ("model.0.weight", "model.0.bias", "model.2.weight", "model.2.bias")
-        D = int(state_dicts[0]["model.0.weight"].shape[1])
-        shapes = ((HIDDEN, D), (HIDDEN,), (4, HIDDEN), (4,))
-        for sd in state_dicts:
-            assert all(tuple(sd[k].shape) == s for k, s in zip(keys, shapes)), f"ModelArena: every model must be senet({D}, 4)"
-        self.R, self.D, self.device = R, D, device
-        n_par = HIDDEN * D + HIDDEN + 4 * HIDDEN + 4
-        self.par_stride = (n_par + 63) // 64 * 64
+        self._copy(state_dicts, device)
+
+    def _seat(self, base, R, D, par_stride, device):
+        """The object over R models whose blocks start `par_stride` floats apart from address `base` on: the operand-image
+        scratch, `c` (model 0's moc_meta_t) and `runs` (the first sixteen models at most; `group` for the others)."""
+        offs, _, _ = self.layout(D)
+        self.R, self.D, self.device, self.par_stride = R, D, device, int(par_stride)
         img_b = max(lib().moc_w1_image_bytes(D, _lib.MOC_BF16), lib().moc_w1_image_bytes(D, _lib.MOC_F32))
         self.img_stride = (img_b + 255) // 256 * 256
-        self.P = torch.zeros((R, self.par_stride), dtype=torch.float32, device=device)
         self.images = torch.empty((R, self.img_stride), dtype=torch.uint8, device=device)
-        offs = (0, HIDDEN * D, HIDDEN * D + HIDDEN, HIDDEN * D + HIDDEN + 4 * HIDDEN)
-        for r, sd in enumerate(state_dicts):
-            for k, o in zip(keys, offs):
-                t = sd[k].detach().reshape(-1)
-                self.P[r, o:o + t.numel()].copy_(t.to(device=device, dtype=torch.float32))
-        base = ptr(self.P)
         self.c = MocMeta(W1=base, b1=base + 4 * offs[1], W2=base + 4 * offs[2], b2=base + 4 * offs[3],
                          W1_image=ptr(self.images), H=HIDDEN, D=D)
-        self.runs = MocRuns(n_runs=R, slide_stride=0, par_stride=self.par_stride, image_stride=self.img_stride)
+        self.runs = MocRuns(n_runs=min(R, 16), slide_stride=0, par_stride=self.par_stride, image_stride=self.img_stride)
+
+    def _copy(self, state_dicts, device):
+        """A scratch arena `P` [R, par_stride] holding copies of the state dicts' tensors."""
+        R = len(state_dicts)
+        D = int(state_dicts[0]["model.0.weight"].shape[1])
+        offs, n_par, shapes = self.layout(D)
+        for sd in state_dicts:
+            assert all(tuple(sd[k].shape) == s for k, s in zip(self.KEYS, shapes)), f"ModelArena: every model must be senet({D}, 4)"
+        self.P = torch.zeros((R, (n_par + 63) // 64 * 64), dtype=torch.float32, device=device)
+        for r, sd in enumerate(state_dicts):
+            for k, o in zip(self.KEYS, offs):
+                t = sd[k].detach().reshape(-1)
+                self.P[r, o:o + t.numel()].copy_(t.to(device=device, dtype=torch.float32))
+        self._seat(ptr(self.P), R, D, self.P.size(1), device)
+
+    @classmethod
+    def of_models(cls, models):
+        """The arena of R live senets (any R up to MAX_MODELS), for the evaluation of several runs in one pass
+        (meta_forward_by_slide).  Where the models' parameter tensors already lie in one arena -- after runs.TrainRuns they
+        are views of TrainRuns.P, W1 | b1 | W2 | b2 of a run in one block, the runs a constant stride apart -- the arena is
+        used IN PLACE: no copy, `P` is None (the storage is the models' own, kept alive through `_keep`), only the operand
+        images are scratch of this object; `c`, `runs` and `group` are as for a copied arena, so every entry that takes a
+        ModelArena takes this one.  Otherwise the parameters are copied into a scratch arena.  Either way the values are
+        those of the models at the time of the call."""
+        R = len(models)
+        assert 1 <= R <= cls.MAX_MODELS, f"ModelArena.of_models: 1 .. {cls.MAX_MODELS} models"
+        quads = [[m.model[0].weight, m.model[0].bias, m.model[2].weight, m.model[2].bias] for m in models]
+        D = int(quads[0][0].shape[1])
+        offs, n_par, shapes = cls.layout(D)
+        assert all(tuple(p.shape) == sh for q in quads for p, sh in zip(q, shapes)), \
+            f"evaluation of several runs: every model must be senet({D}, 4) (models of different width are not batched)"
+        dev = quads[0][0].device
+        ok = all(p.is_cuda and p.device == dev and p.dtype == torch.float32 and p.data.is_contiguous() for q in quads for p in q)
+        base = quads[0][0].data_ptr()
+        step = (quads[1][0].data_ptr() - base) if R > 1 else 4 * n_par
+        ok = ok and step % 4 == 0 and step >= 4 * n_par
+        ok = ok and all(p.data_ptr() == base + r * step + 4 * o for r, q in enumerate(quads) for p, o in zip(q, offs))
+        self = cls.__new__(cls)
+        if ok:
+            self.P, self._keep = None, quads
+            self._seat(base, R, D, step // 4, dev)
+        else:
+            self._copy([{k: p.detach() for k, p in zip(cls.KEYS, q)} for q in quads], dev)
+        return self
+
+    def group(self, r0: int, n_models: int):
+        """(moc_meta_t, moc_runs_t) of models r0 .. r0 + n_models - 1 (at most sixteen: what one call serves)."""
+        assert 0 <= r0 and 1 <= n_models <= 16 and r0 + n_models <= self.R
+        mc = MocMeta.from_buffer_copy(self.c)
+        for name in ("W1", "b1", "W2", "b2"):
+            setattr(mc, name, getattr(self.c, name) + 4 * r0 * self.par_stride)
+        mc.W1_image = ptr(self.images) + r0 * self.img_stride
+        return mc, MocRuns(n_runs=n_models, slide_stride=0, par_stride=self.par_stride, image_stride=self.img_stride)
 
 
 def meta_forward_models(batch: SlideBatch, params: ModelArena, n_models: int, mixed: torch.Tensor, slide0: int, n: int,
@@ -828,6 +885,28 @@ def meta_forward_models(batch: SlideBatch, params: ModelArena, n_models: int, mi
     runs.n_runs = n_models
     check(lib().moc_meta_forward_models(C.byref(batch.c), C.byref(params.c), C.byref(runs), ptr(mixed), slide0, n, use_bits,
                                         _stream()), "moc_meta_forward_models")
+
+
+def meta_forward_by_slide(batch: SlideBatch, params: ModelArena, r0: int, n_models: int, model_of_slide: torch.Tensor,
+                          slide0: int, n: int, use_bits: int, keep_hidden: bool = False):
+    """The evaluation forward over the union rows of slides slide0 .. +n of an unmasked batch whose phase A has run, in one
+    launch, every slide with a model of its own: slide b of the batch is scored by model r0 + model_of_slide[b] of `params`
+    (device int32 [batch.n_slides], values 0 .. n_models - 1, n_models <= 16).  Writes the batch's own `mixed` as meta_forward
+    does -- for a slide of model r the bits meta_forward gives with model r alone -- so that one pool_loss pools all slides
+    (moc_meta_forward_by_slide)."""
+    assert batch.mask is None, "meta_forward_by_slide: the batch must be unmasked"
+    assert params.D == batch.D, "meta_forward_by_slide: models / width do not match"
+    assert model_of_slide.is_cuda and model_of_slide.dtype == torch.int32 and model_of_slide.is_contiguous() and \
+        model_of_slide.numel() == batch.n_slides, "meta_forward_by_slide: model_of_slide is device int32 [n_slides]"
+    assert not (keep_hidden and getattr(batch, "eval_only", False)), "meta_forward_by_slide: this batch keeps no H1 / gates"
+    mc, runs = params.group(r0, n_models)
+    _, ws = batch.meta_ws()
+    if not keep_hidden:
+        ws = type(ws).from_buffer_copy(ws)
+        ws.H1 = None
+        ws.gates = None
+    check(lib().moc_meta_forward_by_slide(C.byref(batch.c), C.byref(mc), C.byref(runs), ptr(model_of_slide), C.byref(ws),
+                                          slide0, n, use_bits, _stream()), "moc_meta_forward_by_slide")
 
 
 def meta_forward_dense_models(batch: SlideBatch, params: ModelArena, n_models: int, scale: float, prob_mean: torch.Tensor,

@@ -551,8 +551,8 @@ def train_runs(models, train_loaders, optimizers, device, args, generators=None)
     (fold, shot): `train(models[r], train_loaders[r], optimizers[r], device, args)` for every r, stepped in lockstep by one
     launch pair per meta-step (moc_amd.runs.TrainRuns; include/moc_hip.h moc_train_steps_runs).  Per run bit-identical to
     `train` from the same mask stream; run r's masks come from `generators[r]` (a private CPU torch.Generator each; by
-    default seeded from the default generator on the first call).  The loaders are resident splits (ResidentBags) of equal
-    length.  -> the TrainRuns object (kept for the next pass: call again with the same lists)."""
+    default seeded from the default generator on the first call).  The loaders are resident splits (ResidentBags); their
+    passes may differ in length (runs.group_runs: one lockstep chain per length).  -> the TrainRuns object (kept for the next pass: call again with the same lists)."""
     from .runs import TrainRuns
     key = (tuple(id(m) for m in models), tuple(id(o) for o in optimizers), tuple(id(l) for l in train_loaders),
            args.topj, args.topk, tuple(sorted(args.discard_classifiers or ())), tuple(len(l) for l in train_loaders))
@@ -782,6 +782,152 @@ def evaluation(model, loader, device, args):
         finally:
             loader.dataset.repeat_num = set_len
     return _metrics(pooled, labels, losses, len(loader.dataset), real_len, args)
+
+
+# plans of evaluation_runs, least recently used first.  A caller that evaluates one fixed set every epoch and a varying
+# subset of another (run_moc.main_runs: all train + validation splits, then the test splits of the runs that improved)
+# keeps its fixed plan for good: it is used between any two subset plans, so it is never the least recently used.  A new
+# plan is built AFTER the oldest ones are dropped, so its work arrays come out of the blocks those gave back.
+_eval_run_plans = {}
+EVAL_RUN_PLANS = 3
+
+
+def pack_splits(loaders):
+    """Pack resident splits side by side now (what evaluation_runs does on its first call with them): a caller that will
+    evaluate varying subsets of them (the test splits of the runs that improved) packs all of them once."""
+    assert all(isinstance(ld, ResidentBags) for ld in loaders), "pack_splits: resident splits only"
+    _pack_loaders(list(loaders))
+
+
+def _pack_loaders(loaders):
+    """The resident arrays of the distinct splits side by side in ONE array (as runs.TrainRuns lays out its runs): a one-time
+    copy, after which every split's `X` is a view of the packed array (its own allocation is released; the split's plans,
+    which held the old array, are dropped).  Splits that share an array already (the same slides loaded once) stay shared.
+    -> (X, first row of every loader's split in X)."""
+    distinct = {}
+    for ld in loaders:
+        distinct.setdefault((ld.X.data_ptr(), ld.X.size(0)), ld.X)
+    views = list(distinct.values())
+    base = views[0]._base if views[0]._base is not None else views[0]
+    packed = all((v._base if v._base is not None else v) is base for v in views) and base.dim() == 2 and base.is_contiguous()
+    if not packed:
+        base = torch.cat(views, 0) if len(views) > 1 else views[0]
+        row0 = {}
+        o = 0
+        for key, v in distinct.items():
+            row0[key] = o
+            o += v.size(0)
+        keys = {id(ld): (ld, (ld.X.data_ptr(), ld.X.size(0))) for ld in loaders}      # (a split may be named twice)
+        for ld, key in keys.values():
+            if len(views) > 1:
+                ld.X = base[row0[key]:row0[key] + key[1]]
+                ld._plans.clear()
+                ld._stats_caches.clear()
+        del views, distinct
+    rb = base.size(1) * base.element_size()
+    return base, [(ld.X.data_ptr() - base.data_ptr()) // rb for ld in loaders]
+
+
+def _eval_runs_plan(loaders, model_of_run, device, args):
+    """Batches over the visits of ALL loaders (an unmasked pass over every split, run after run), chunked by slides under
+    MAX_BATCH_BYTES: per chunk (batch, device labels, device int32 model of each slide relative to its group's first model,
+    [(first model, models, first slide, slides)] per group of at most sixteen models)."""
+    discard = tuple(sorted(args.discard_classifiers or ()))
+    X, row0 = _pack_loaders(loaders)                      # (first: packing moves the splits' arrays, which the key names)
+    key = (tuple(id(ld) for ld in loaders), tuple(ld.X.data_ptr() for ld in loaders), tuple(len(ld) for ld in loaders),
+           tuple(model_of_run), args.n_classes, args.topj, args.topk, discard, MAX_BATCH_BYTES,
+           id(zeroshot_weights), id(zeroshot_weights_ext))
+    plan = _eval_run_plans.pop(key, None)
+    if plan is not None:
+        _eval_run_plans[key] = plan                       # (most recently used: last)
+        return plan
+    while len(_eval_run_plans) >= EVAL_RUN_PLANS:         # (a plan owns the work arrays of all its rows)
+        del _eval_run_plans[next(iter(_eval_run_plans))]
+    bank = _bank_for(X, device)
+    assert bank.C == args.n_classes
+    sizes, starts, labels, run_of = [], [], [], []
+    for r, ld in enumerate(loaders):
+        for k in ld.visit_order():
+            sizes.append(ld.sizes[k])
+            starts.append(row0[r] + ld.starts[k])
+            labels.append(ld.labels[k])
+            run_of.append(r)
+    chunks = []
+    for ids in _chunks(sizes, X.size(1), X.element_size()):
+        batch = SlideBatch(X, [sizes[i] for i in ids], bank.C, bank.Ce, args.topj, args.topk, list(discard),
+                           x_starts=[starts[i] for i in ids])
+        batch.eval_only = True                            # (no H1 / gates: 272 of ~350 work-array bytes per row)
+        lab = torch.tensor([labels[i] for i in ids], dtype=torch.int64).to(device)
+        groups, rel = [], []
+        for j, i in enumerate(ids):                       # (consecutive slides whose models lie in one block of sixteen)
+            mi = model_of_run[run_of[i]]
+            g0 = mi // 16 * 16
+            if not groups or groups[-1][0] != g0:
+                groups.append([g0, 0, j, 0])
+            groups[-1][1] = max(groups[-1][1], mi - g0 + 1)
+            groups[-1][3] += 1
+            rel.append(mi - g0)
+        chunks.append((batch, lab, torch.tensor(rel, dtype=torch.int32).to(device), [tuple(g) for g in groups]))
+    plan = _eval_run_plans[key] = {"bank": bank, "chunks": chunks, "labels": labels, "run_of": run_of, "keep": list(loaders)}
+    return plan
+
+
+def evaluation_runs(models, loaders, device, args):
+    """`[evaluation(models[r], loaders[r], device, args) for r in range(R)]` in ONE pass: one batch of visits over all
+    loaders' slides, phase A once, one forward in which every slide is scored by its run's meta-learner
+    (moc_meta_forward_by_slide), one pooling launch, one device-to-host copy -- per chunk of MAX_BATCH_BYTES of bag rows,
+    which may hold slides of several runs -- then the metrics per run on that run's rows.  Entry r equals evaluation() of run
+    r exactly (the same floats).  A model may be named more than once (its train and its validation split in one call).
+    The models' parameters are read where they are when they already lie in one arena (after
+    train_runs), from a scratch copy otherwise (engine.ModelArena.of_models).
+    Refused (an AssertionError; evaluate such runs one by one): loaders that are not ResidentBags, `loader_seed_draw`
+    splits, splits of different storage type or width, models of different width.  The resident arrays of distinct splits
+    are packed side by side on the first call (a one-time copy; the splits' `X` become views of the packed array)."""
+    R = len(models)
+    assert R >= 1 and len(loaders) == R, "evaluation_runs: one loader per model"
+    assert all(isinstance(ld, ResidentBags) for ld in loaders), "evaluation_runs: resident splits only (main_moc.ResidentBags)"
+    assert not any(ld.loader_seed_draw for ld in loaders), "evaluation_runs: loader_seed_draw splits are not batched"
+    dt, D = loaders[0].X.dtype, loaders[0].X.size(1)
+    assert all(ld.X.dtype == dt and ld.X.size(1) == D for ld in loaders), "evaluation_runs: one storage type and width"
+    for m in models:
+        if m.training:
+            m.eval()
+    with torch.no_grad():
+        uniq = {}
+        for m in models:
+            uniq.setdefault(id(m), (len(uniq), m))
+        arena = engine.ModelArena.of_models([m for _, m in uniq.values()])
+        model_of_run = [uniq[id(m)][0] for m in models]
+        assert arena.D == D, "evaluation_runs: the models' width is not the bags'"
+        restore = []
+        for ld in loaders:
+            restore.append((ld.dataset, len(ld.dataset)))
+            ld.dataset.repeat_num = ld.dataset.real_len()
+        try:
+            plan = _eval_runs_plan(loaders, model_of_run, device, args)
+            use = engine.eval_use_bits(args.discard_classifiers)
+            outs = []
+            for batch, lab, rel, groups in plan["chunks"]:
+                tensors, _ = batch.meta_ws()
+                batch.phase_a(plan["bank"], for_eval=True)
+                for g0, gm, s0, sn in groups:
+                    engine.meta_forward_by_slide(batch, arena, g0, gm, rel, s0, sn, use)
+                engine.pool_loss(batch, lab, 0, batch.n_slides)
+                outs.append(torch.cat([tensors["pooled"], tensors["loss"].unsqueeze(1)], 1).cpu())
+        finally:
+            for ds, set_len in reversed(restore):
+                ds.repeat_num = set_len
+    allv = torch.cat(outs, 0)
+    run_of = torch.tensor(plan["run_of"])
+    evaluation_runs.last_pooled = []
+    res = []
+    for r, ld in enumerate(loaders):
+        rows = (run_of == r).nonzero().flatten()
+        pooled = allv[rows, :-1].contiguous()
+        evaluation_runs.last_pooled.append(pooled)
+        res.append(_metrics(pooled, [plan["labels"][i] for i in rows.tolist()], allv[rows, -1].tolist(), len(ld.dataset),
+                            ld.dataset.real_len(), args))
+    return res
 
 
 def ablation_evaluation(loader, device, args):

@@ -7,6 +7,7 @@ around the GPU callables of moc_amd.main_moc.
     python -m moc_amd.run_moc --synthetic 24 --shot 4 --disable_tqdm        # no data needed
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 -m moc_amd.run_moc ...   # 8 GPUs
     python -m moc_amd.run_moc --folds 0,1,2,3,4 --shot 16 --seed 1 ...      # five folds in ONE process, stepped in lockstep
+    python -m moc_amd.run_moc --shots 1,2,4,8,16 --folds 0,1,2,3,4 --seed 1 ...   # the launcher's whole grid in one process
 
 Same flags and defaults as the reference, same result files (`zs_results_*`, `best_results_*`,
 `ablation_results_*`, `best_model_*.pt`, `summary_*.csv`) with the same keys.  Differences, all
@@ -84,6 +85,11 @@ def get_args(argv=None):
                         "what scripts/moc_train.sh starts as one process per fold.  Every fold's numbers and files are those of "
                         "`--fold F` alone (with --seed: bit for bit).  Under a launcher the folds are dealt to the ranks, no "
                         "communication")
+    p.add_argument("--shots", type=str, default="",
+                   help="comma-separated shot counts: train every (shot, fold) pair of --shots x --folds (without --folds: the one "
+                        "--fold) in this process -- scripts/moc_train.sh's whole grid.  Run (S, F) writes into "
+                        "{result_dir}/{S}_shot/ what `--fold F --shot S --result_dir {result_dir}/{S}_shot` writes alone, so that "
+                        "`--summary --summary_dir {result_dir}` reads the tree.  Under a launcher the pairs are dealt to the ranks")
     p.add_argument("--patch_maps", type=str, default=None, choices=list(PATCH_MAP_CHOICES),
                    help="after main(), write per-patch maps (moc_amd.patch_maps) of these splits with the best checkpoint to "
                         "{result_dir}/patch_maps_shot_S_fold_F/{split}/ (default: none; test with --patch_maps_from)")
@@ -108,8 +114,8 @@ def check_patch_map_args(args):
         return
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise SystemExit("--patch_maps / --patch_maps_from are one-GPU options: run them without a launcher")
-    if args.folds:
-        raise SystemExit("--patch_maps / --patch_maps_from do not combine with --folds: run one --fold at a time")
+    if args.folds or getattr(args, "shots", ""):
+        raise SystemExit("--patch_maps / --patch_maps_from do not combine with --folds / --shots: run one --fold and --shot at a time")
     if args.ablation_study != "none":
         raise SystemExit("--patch_maps / --patch_maps_from need the meta-learner: the ablation study trains none")
 
@@ -179,23 +185,114 @@ def _load_weights(args, task, device):
     return W.to(device), We.to(device)
 
 
-def prepare(args, device):
+def _synthetic_splits(args, C):
+    """(seed base, slides, visits per pass or None) of the generated train / val / test split of (args.shot, args.fold)."""
+    fo = 17 * int(getattr(args, "fold", 0))          # (every fold its own generated slides; fold 0: the fixtures' slides)
+    return ((100 + fo, args.shot * C, args.shot * C), (5000 + fo, args.synthetic, None), (9000 + fo, args.synthetic, None))
+
+
+def _synthetic_classes(args):
+    return 2 if args.dataset == "nsclc" else 3 if args.dataset == "rcc" else 12 if args.dataset == "ebrains12" else 30
+
+
+def _label_map(args):
+    """The dataset's label map: the table's own, or (table driven) its classes in order of first appearance."""
+    task = TASKS[args.dataset]
+    labels = task["labels"]
+    if labels is None:
+        seen = list(dict.fromkeys(pd.read_csv(os.path.join(args.root, task["csv"]), dtype=str)["label"]))
+        labels = {name: i for i, name in enumerate(seen)}
+    return labels
+
+
+def _real_splits(args):
+    """The reference's dataset object and the three splits of (args.shot, args.fold), nothing loaded yet."""
+    task = TASKS[args.dataset]
+    labels = _label_map(args)
+    csv_path = os.path.join(args.root, task["csv"])
+    data_dir = os.path.join(args.root, task["data"], "merge_features_conch")
+    dataset = Generic_MIL_Dataset(csv_path=csv_path, data_dir=data_dir, shuffle=False, seed=1, print_info=True,
+                                  label_dict=labels, patient_strat=False, ignore=[])
+    dataset.load_from_h5(True)
+    dataset.load_full_path(True)
+    splits = dataset.return_splits(from_id=False,
+                                   csv_path=os.path.join(args.root, task["splits"], f"{args.shot}shots", f"splits_{args.fold}.csv"),
+                                   repeat_num=int(args.shot) * len(labels))
+    return labels, splits
+
+
+def split_footprints(args):
+    """[(share key, bag rows)] of the train / val / test split of (args.shot, args.fold) WITHOUT loading a bag: two runs whose
+    keys for a split are equal visit the same slides in the same order and hold that split once (`prepare(share=)`)."""
+    if args.synthetic:
+        from . import synth
+        C = _synthetic_classes(args)
+        return [(("synthetic", s, base, n), int(sum(synth.bag_sizes(base, n, 3000, fixed=False, lo=500, hi=8000))))
+                for s, (base, n, _) in enumerate(_synthetic_splits(args, C))]
+    from .datasets import bag_rows
+    _, splits = _real_splits(args)
+    out = []
+    for s_i, sp in enumerate(splits):
+        ids = tuple(str(v) for v in sp.slide_data["slide_id"])
+        out.append((("files", s_i, ids), sum(bag_rows(sp.data_dir, i, FEATURE_DIM) for i in ids)))
+    return out
+
+
+FEATURE_DIM = 512        # CONCH embeddings: the width of the bags and of the meta-learner this driver builds (main_moc.py:315)
+
+
+def grid_bytes(footprints, D, itemsize, C):
+    """Device bytes a grid of runs holds: `footprints[r]` = split_footprints of run r.  An estimate from the row counts: pure.
+      * the bags of every DISTINCT split once (splits that two runs list alike are shared);
+      * the work arrays of the evaluation passes per VISIT (main_moc.evaluation_runs puts a shared split into its batch
+        once for every run that names it): statistics, selection, candidates and mixed scores per row -- no H1 / gates --
+        for every run's train and validation split (the plan of every epoch) and twice for its test split (the plans of
+        two different sets of improved runs are kept, main_moc.EVAL_RUN_PLANS);
+      * every train split a second time with two sets of training work arrays (runs.TrainRuns packs its runs' bags);
+      * the largest one-time packing copy (the splits of an evaluation pass are laid side by side)."""
+    ws_eval = 4 * (2 * C + 3) + 4 * (2 * C + 2) + 13 + 4 * C
+    ws_train = ws_eval + 4 * 64 + 16 + 8
+    seen, total, pack = set(), 0, [0, 0]
+    for fp in footprints:
+        for s_i, (key, rows) in enumerate(fp):
+            if key not in seen:
+                seen.add(key)
+                total += rows * D * itemsize
+                pack[0 if s_i < 2 else 1] += rows * D * itemsize
+        (_, tr), (_, va), (_, te) = fp
+        total += (tr + va + 2 * te) * ws_eval + tr * (D * itemsize + 2 * ws_train)
+    return total + max(pack)
+
+
+def largest_grid(footprints, D, itemsize, C, free_bytes):
+    """How many of the leading runs of the grid fit into `free_bytes` (all of them: len(footprints))."""
+    k = len(footprints)
+    while k > 0 and grid_bytes(footprints[:k], D, itemsize, C) > free_bytes:
+        k -= 1
+    return k
+
+
+def prepare(args, device, share=None):
     """-> (train_loader, val_loader, test_loader) and the classifier bank installed in moc_amd.main_moc.  Inside a
-    process group of more than one rank the three are moc_amd.dist.ShardedSplit objects (each rank holds its block)."""
+    process group of more than one rank the three are moc_amd.dist.ShardedSplit objects (each rank holds its block).
+    `share` (a dict kept by a caller that prepares several runs): a resident split whose key (split_footprints) is in it is
+    not loaded again -- the runs share the object and its array."""
     import torch.distributed as dist
     world = dist.get_world_size() if dist.is_initialized() else 1
     rank = dist.get_rank() if dist.is_initialized() else 0
     if args.synthetic:
         from . import synth
-        C = 2 if args.dataset == "nsclc" else 3 if args.dataset == "rcc" else 12 if args.dataset == "ebrains12" else 30
+        C = _synthetic_classes(args)
         args.n_classes = C
         W, We = synth.make_bank(1234, 512, C)
         M.set_classifier_bank(W.to(device), We.to(device))
         dt = {"bf16": torch.bfloat16, "fp16": torch.float16}.get(args.bag_dtype, torch.float32)
         loaders = []
-        fo = 17 * int(getattr(args, "fold", 0))          # (every fold its own generated slides; fold 0: the fixtures' slides)
-        for s, (base, n, rep) in enumerate(((100 + fo, args.shot * C, args.shot * C), (5000 + fo, args.synthetic, None),
-                                            (9000 + fo, args.synthetic, None))):
+        for s, (base, n, rep) in enumerate(_synthetic_splits(args, C)):
+            key = ("synthetic", s, base, n)
+            if share is not None and s > 0 and key in share:
+                loaders.append(share[key])
+                continue
             sizes = synth.bag_sizes(base, n, 3000, fixed=False, lo=500, hi=8000)
             if world > 1:                    # every rank generates only the slides of its block (seeds are per slide)
                 blocks = mdist.block_lists(n, world)
@@ -206,29 +303,23 @@ def prepare(args, device):
                 continue
             bags, labels = synth.make_slide_set(base, sizes, 512, We, C)
             loaders.append(M.ResidentBags(bags, labels, device, dtype=dt, repeat_num=rep, cache_scores=bool(args.cache_scores) and s == 0))
+            if share is not None and s > 0:
+                share[key] = loaders[-1]
         return loaders
     task = TASKS[args.dataset]
-    labels = task["labels"]
-    csv_path = os.path.join(args.root, task["csv"])
-    if labels is None:       # table driven: classes in order of first appearance in the slide table
-        seen = list(dict.fromkeys(pd.read_csv(csv_path, dtype=str)["label"]))
-        labels = {name: i for i, name in enumerate(seen)}
+    labels, splits = _real_splits(args)
     args.n_classes = len(labels)
     W, We = _load_weights(args, task, device)
     assert W.size(1) == args.n_classes and We.size(1) > W.size(1), "classifier bank does not match the label map"
     M.set_classifier_bank(W, We)
-    data_dir = os.path.join(args.root, task["data"], "merge_features_conch")
-    dataset = Generic_MIL_Dataset(csv_path=csv_path, data_dir=data_dir, shuffle=False, seed=1, print_info=True,
-                                  label_dict=labels, patient_strat=False, ignore=[])
-    dataset.load_from_h5(True)
-    dataset.load_full_path(True)
-    splits = dataset.return_splits(from_id=False,
-                                   csv_path=os.path.join(args.root, task["splits"], f"{args.shot}shots", f"splits_{args.fold}.csv"),
-                                   repeat_num=int(args.shot) * args.n_classes)
     loaders = []
     for s_i, sp in enumerate(splits):
         sp.load_full_path(True)
         sp.load_from_h5(True)
+        key = ("files", s_i, tuple(str(v) for v in sp.slide_data["slide_id"]))
+        if share is not None and s_i > 0 and world == 1 and args.resident and key in share:
+            loaders.append(share[key])
+            continue
         if world > 1:
             loaders.append(to_sharded(sp, device, rank, world, {"bf16": torch.bfloat16, "fp16": torch.float16}.get(args.bag_dtype),
                                       train=(s_i == 0)))
@@ -236,6 +327,8 @@ def prepare(args, device):
             loaders.append(to_resident(sp, device, {"bf16": torch.bfloat16, "fp16": torch.float16}.get(args.bag_dtype),
                                        loader_seed_draw=bool(args.loader_seed_draw)))
             loaders[-1].cache_scores = bool(args.cache_scores) and s_i == 0
+            if share is not None and s_i > 0:
+                share[key] = loaders[-1]
         else:
             loaders.append(torch.utils.data.DataLoader(sp, batch_size=1, shuffle=False, num_workers=1))
     return loaders
@@ -353,12 +446,15 @@ def patch_maps_from(args, model, loaders, device):
 
 
 def main_runs(args_list, models, optimizers, loaders_list, device, generators=None):
-    """main() (main_moc.py:586-644) for several runs at once: the zero-shot evaluations and the per-epoch evaluations run
-    per run, the training passes of all runs in lockstep (moc_amd.main_moc.train_runs).  `args_list[r]` carries run r's
-    fold / shot / result_dir; loaders_list[r] = (train, val, test) resident splits.  Every run prints, saves and returns what
-    main() would for it alone.  -> list of result dicts."""
+    """main() (main_moc.py:586-644) for several runs at once: the zero-shot evaluations run per run, the training passes of
+    all runs in lockstep (moc_amd.main_moc.train_runs), and every epoch's evaluations in one pass for all runs' train and
+    validation splits, then one more for the test splits of the runs whose validation AUC improved (the reference visits
+    the test set only then) -- moc_amd.main_moc.evaluation_runs.  `args_list[r]` carries run r's fold / shot / result_dir;
+    loaders_list[r] = (train, val, test) resident splits.  Every run prints, saves and returns what main() would for it
+    alone.  -> list of result dicts."""
     R = len(models)
     a0 = args_list[0]
+    tag = (lambda a: f"[shot {a.shot} fold {a.fold}]") if len({a.shot for a in args_list}) > 1 else (lambda a: f"[fold {a.fold}]")
     assert a0.ablation_study == "none", "main_runs: the ablation study trains nothing -- run it per fold"
     st = []
     for r in range(R):
@@ -368,31 +464,36 @@ def main_runs(args_list, models, optimizers, loaders_list, device, generators=No
         zs = (-1, -1, -1)
         if a.check_zeroshot:
             zs = (M.zs_evaluation(tr, device, a), M.zs_evaluation(va, device, a), M.zs_evaluation(te, device, a))
-            print(f"[fold {a.fold}] Zero-shot Train: {zs[0]}, Val: {zs[1]}, Test: {zs[2]}")
+            print(f"{tag(a)} Zero-shot Train: {zs[0]}, Val: {zs[1]}, Test: {zs[2]}")
             with open(os.path.join(a.result_dir, f"zs_results_shot_{a.shot}_fold_{a.fold}.json"), "w") as f:
                 json.dump({"zs_train": zs[0], "zs_val": zs[1], "zs_test": zs[2]}, f, indent=4)
         st.append(dict(zs=zs, best_val=0, test_at_best_val=0, test_acc_at_best_val=0, best_epoch=0,
                        model_path=os.path.join(a.result_dir, f"best_model_shot_{a.shot}_fold_{a.fold}.pt")))
     trains = [ls[0] for ls in loaders_list]
+    M.pack_splits(trains + [ls[1] for ls in loaders_list])       # (one array per pass of evaluation_runs, packed once)
+    M.pack_splits([ls[2] for ls in loaders_list])
     for epoch in range(getattr(a0, "epochs", 25)):
         print("Epoch: ", epoch)
         M.train_runs(models, trains, optimizers, device, a0, generators=generators)
+        # all runs' train and validation splits in one pass, then the test splits of the runs that improved in another
+        ev = M.evaluation_runs(list(models) + list(models), trains + [ls[1] for ls in loaders_list], device, a0)
+        better = [r for r in range(R) if ev[R + r]["auc"] > st[r]["best_val"]]
+        ev_test = dict(zip(better, M.evaluation_runs([models[r] for r in better], [loaders_list[r][2] for r in better], device, a0))) \
+            if better else {}
         for r in range(R):
             a, s_ = args_list[r], st[r]
-            tr, va, te = loaders_list[r]
-            train_eval = M.evaluation(models[r], tr, device, a)
-            val_eval = M.evaluation(models[r], va, device, a)
-            if val_eval["auc"] > s_["best_val"]:
-                test_eval = M.evaluation(models[r], te, device, a)
-                print(f"[fold {a.fold}] Epoch: {epoch}, Train: {train_eval}, Val: {val_eval}, Test: {test_eval}")
+            train_eval, val_eval = ev[r], ev[R + r]
+            if r in ev_test:
+                test_eval = ev_test[r]
+                print(f"{tag(a)} Epoch: {epoch}, Train: {train_eval}, Val: {val_eval}, Test: {test_eval}")
                 s_.update(best_val=val_eval["auc"], test_at_best_val=test_eval["auc"], test_acc_at_best_val=test_eval["acc"], best_epoch=epoch)
                 torch.save(models[r].state_dict(), s_["model_path"])
             else:
-                print(f"[fold {a.fold}] Epoch: {epoch}, Train: {train_eval}, Val: {val_eval}")
+                print(f"{tag(a)} Epoch: {epoch}, Train: {train_eval}, Val: {val_eval}")
     out = []
     for r in range(R):
         a, s_ = args_list[r], st[r]
-        print(f"[fold {a.fold}] Best Val: {s_['best_val']}, Test at Best Val: {s_['test_at_best_val']}, Test acc: {s_['test_acc_at_best_val']}, "
+        print(f"{tag(a)} Best Val: {s_['best_val']}, Test at Best Val: {s_['test_at_best_val']}, Test acc: {s_['test_acc_at_best_val']}, "
               f"Best Epoch: {s_['best_epoch']}")
         res = {"zero_shot_train": s_["zs"][0], "zero_shot_val": s_["zs"][1], "zero_shot_test": s_["zs"][2],
                "best_val": s_["best_val"], "test_at_best_val": s_["test_at_best_val"], "test_acc_at_best_val": s_["test_acc_at_best_val"],
@@ -412,28 +513,67 @@ def folds_of_rank(spec: str, rank: int, world: int):
     return folds[rank::world]
 
 
+def pairs_of_rank(shots: str, folds: str, shot: int, fold: int, rank: int, world: int):
+    """The (shot, fold) pairs of `--shots a,b,... --folds c,d,...` this rank trains, shot-major (runs of one pass length side
+    by side: they step in one lockstep chain), dealt round-robin as folds_of_rank deals folds: every pair exactly once over
+    the job, nothing exchanged.  An empty `shots` / `folds` means the one --shot / --fold."""
+    sh = [int(v) for v in shots.split(",") if v.strip() != ""] or [int(shot)]
+    fo = [int(v) for v in folds.split(",") if v.strip() != ""] or [int(fold)]
+    assert len(set(sh)) == len(sh), "--shots: a shot count named twice"
+    assert len(set(fo)) == len(fo), "--folds: a fold named twice"
+    pairs = [(s_, f_) for s_ in sh for f_ in fo]
+    return pairs[rank::world]
+
+
+def run_result_dir(args, shot: int):
+    """Where run (shot, fold) of this command writes: --result_dir itself for --folds alone, {result_dir}/{shot}_shot with
+    --shots (what --summary reads)."""
+    return os.path.join(args.result_dir, f"{shot}_shot") if getattr(args, "shots", "") else args.result_dir
+
+
 def cli_folds(args):
-    """`--folds a,b,...`: those folds in this process (under a launcher: this rank's share of them, nothing exchanged)."""
+    """`--folds a,b,...` and / or `--shots a,b,...`: those runs in this process (under a launcher: this rank's share of
+    them, nothing exchanged)."""
     import copy
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
-    folds = folds_of_rank(args.folds, rank, world)
+    pairs = pairs_of_rank(getattr(args, "shots", ""), args.folds, args.shot, args.fold, rank, world)
     device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")) if world > 1 else torch.cuda.current_device())
     torch.cuda.set_device(device)
-    if not folds:
+    if not pairs:
         print(f"rank {rank}: no fold to train")
         return []
     assert not args.loader_seed_draw, "--folds: the runs draw their masks from private generators (no DataLoader base-seed draw)"
+    from . import runs as RUNS
+    if len(pairs) > RUNS.MAX_RUNS:
+        raise SystemExit(f"--shots x --folds: {len(pairs)} runs in one process, at most {RUNS.MAX_RUNS}")
+    if getattr(args, "shots", ""):
+        # the footprint of the grid before a bag is loaded: splits that two runs share count once
+        fps = []
+        for shot, fold in pairs:
+            a = copy.copy(args)
+            a.fold, a.shot = fold, shot
+            fps.append(split_footprints(a))
+        itemsize = 2 if args.bag_dtype in ("bf16", "fp16") else 4
+        C_ = _synthetic_classes(args) if args.synthetic else len(_label_map(args))
+        free = torch.cuda.mem_get_info(device)[0]
+        need = grid_bytes(fps, FEATURE_DIM, itemsize, C_)
+        if need > free:
+            k = largest_grid(fps, FEATURE_DIM, itemsize, C_, free)
+            raise SystemExit(f"--shots x --folds: this grid needs about {need / 2**30:.1f} GiB of device memory, {free / 2**30:.1f} GiB "
+                             f"are free.  The largest leading part of it that fits is {k} run(s): {pairs[:k]}")
     args_list, models, optimizers, loaders_list, gens = [], [], [], [], []
-    for fold in folds:
+    share = {}
+    for shot, fold in pairs:
         a = copy.copy(args)
-        a.fold = fold
-        loaders = prepare(a, device)
+        a.fold, a.shot = fold, shot
+        a.result_dir = run_result_dir(args, shot)
+        loaders = prepare(a, device, share=share)
         assert all(isinstance(ld, M.ResidentBags) for ld in loaders), "--folds needs resident splits (--resident 1)"
         # exactly what `--fold F` alone does with the default generator: seed, build the meta-learner, and the masks follow
         # from wherever that leaves the stream -- here in a generator of the run's own
         if args.seed is not None:
             torch.manual_seed(args.seed)
-        model = M.senet(512, 4).to(device)
+        model = M.senet(FEATURE_DIM, 4).to(device)
         g = torch.Generator()
         g.set_state(torch.get_rng_state())
         args_list.append(a)
@@ -452,7 +592,7 @@ def cli(argv=None):
     check_patch_map_args(args)
     if not torch.cuda.is_available():
         raise RuntimeError("moc_amd needs a GPU: there is no CPU fallback")
-    if args.folds:
+    if args.folds or args.shots:
         return cli_folds(args)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1:                                   # one process per GPU under a launcher (torch.distributed.run)
@@ -476,7 +616,7 @@ def cli(argv=None):
     train_loader, val_loader, test_loader = prepare(args, device)
     if args.seed is not None:
         torch.manual_seed(args.seed)
-    model = M.senet(512, 4).to(device)                                                   # main_moc.py:315
+    model = M.senet(FEATURE_DIM, 4).to(device)                                                   # main_moc.py:315
     optimizer = torch.optim.Adam(model.parameters(), lr=1e-3, weight_decay=1e-4)         # main_moc.py:316
     loaders = (train_loader, val_loader, test_loader)
     if args.patch_maps_from:

@@ -11,9 +11,16 @@ state, its own stream of row masks -- `torch.rand(N) > 0.5` per slide drawn from
 reference's runs are separate processes, each with its own default generator).  Per run the result is bit-identical to
 training it alone with `main_moc.train` from the same generator state (tests/test_gpu_runs.py).
 
-What the runs share: the classifier bank, the hyper-parameters of Adam, the number of visits per pass, topj / topk /
-discard_classifiers.  The models' parameter tensors and the optimizers' moments are re-seated as views into one arena
-per kind (state_dict() / load_state_dict() keep working; the tensors' values are preserved).
+What the runs share: the classifier bank, the hyper-parameters of Adam, topj / topk / discard_classifiers, storage type
+and width.  The models' parameter tensors and the optimizers' moments are re-seated as views into one arena per kind
+(state_dict() / load_state_dict() keep working; the tensors' values are preserved).
+
+Runs need NOT be alike in the number of visits per pass or in the Adam steps already taken (a shots x folds grid:
+`scripts/moc_train.sh` trains 1, 2, 4, 8 and 16 shots).  They are grouped by (visits per pass, step count) -- `group_runs`
+-- and every group is one lockstep chain with its own moc_meta_t copy (so its own `step`) on a stream of its own, as the
+chains of more than eight like runs already were; a chain ends its pass when its runs have made their visits.  The step
+kernels are the same.  Phase A still covers all runs' slides of a pass in one go, and every run still draws its masks
+from its private generator in its own loader order.
 """
 from __future__ import annotations
 
@@ -27,7 +34,27 @@ from . import engine
 from ._lib import MocRuns, check, lib, ptr
 from .engine import HIDDEN, MetaState, SlideBatch
 
-MAX_RUNS = 16
+MAX_RUNS = 32           # runs of one TrainRuns (five shots x five folds and some); one moc_train_steps_runs call: 16
+MAX_CHAIN = 16          # runs one moc_train_steps_runs call serves (MOC_MAX_RUNS of the library)
+
+
+def group_runs(keys, cap=8):
+    """Lockstep chains for runs whose passes are not alike.  `keys[r]`: what the runs of a chain must share (the number of
+    visits per pass, or a tuple with the Adam step count too).  Runs with equal keys form a group, in order of first
+    appearance, the runs inside it in their given order; a group of more than `cap` runs is cut into chains of at most `cap`
+    (`cap` <= 16, what one moc_train_steps_runs call serves; measured best: eight).  -> list of lists of run indices: every
+    run in exactly one chain.  Pure."""
+    cap = int(cap)
+    assert 1 <= cap <= MAX_CHAIN, f"group_runs: 1 .. {MAX_CHAIN} runs per chain"
+    by_key = {}
+    for r, k in enumerate(keys):
+        by_key.setdefault(k, []).append(r)
+    chains = []
+    for rs in by_key.values():
+        n_chains = (len(rs) + cap - 1) // cap
+        per = (len(rs) + n_chains - 1) // n_chains           # (even chains: nine runs are 5 + 4, not 8 + 1)
+        chains += [rs[i:i + per] for i in range(0, len(rs), per)]
+    return chains
 
 
 class TrainRuns:
@@ -40,9 +67,9 @@ class TrainRuns:
         assert 1 <= R <= MAX_RUNS and len(optimizers) == R and len(splits) == R, f"1 .. {MAX_RUNS} runs"
         assert all(isinstance(sp, M.ResidentBags) for sp in splits), "train_runs: resident splits (main_moc.ResidentBags)"
         self.R, self.models, self.optimizers, self.splits, self.device = R, list(models), list(optimizers), list(splits), device
-        n = len(splits[0])
-        assert all(len(sp) == n for sp in splits), "train_runs: every run must make the same number of visits per pass"
-        self.n = n
+        self.run_n = [len(sp) for sp in splits]               # visits per pass of each run
+        self.n = self.run_n[0] if len(set(self.run_n)) == 1 else None      # (the common number, when there is one)
+        self.run_slide0 = [sum(self.run_n[:r]) for r in range(R)]         # first slide of each run in the batches
         dt, D = splits[0].X.dtype, splits[0].X.size(1)
         assert all(sp.X.dtype == dt and sp.X.size(1) == D for sp in splits), "train_runs: one storage type and width"
         assert not any(sp.loader_seed_draw for sp in splits), "train_runs: loader_seed_draw splits are not batched"
@@ -115,13 +142,14 @@ class TrainRuns:
         self.W2_alt = torch.empty((R, 4, H), **f32)
         offs = (0, H * D, H * D + H, H * D + H + 4 * H)
         shapes = ((H, D), (H,), (4, H), (4,))
-        group0 = None
+        group0, run_steps = None, []
         for r, (model, opt) in enumerate(zip(self.models, self.optimizers)):
             meta = MetaState(model, opt)                      # (validates the pair; creates Adam's state if it is new)
             g = meta._group
-            hp = (float(g["lr"]), tuple(float(b) for b in g["betas"]), float(g["eps"]), float(g["weight_decay"]), meta.c.step)
+            hp = (float(g["lr"]), tuple(float(b) for b in g["betas"]), float(g["eps"]), float(g["weight_decay"]))
             group0 = group0 or hp
-            assert hp == group0, "train_runs: the runs must share Adam's hyper-parameters and step count"
+            assert hp == group0, "train_runs: the runs must share Adam's hyper-parameters"
+            run_steps.append(int(meta.c.step))
             for p, o, shp in zip(meta.params, offs, shapes):
                 cnt = p.numel()
                 for arena, src in ((self.P, p.data), (self.Mo, opt.state[p]["exp_avg"]), (self.Vo, opt.state[p]["exp_avg_sq"])):
@@ -131,7 +159,6 @@ class TrainRuns:
                 opt.state[p]["exp_avg_sq"] = self.Vo[r, o:o + cnt].view(shp)
         self.meta = MetaState(self.models[0], self.optimizers[0])            # run 0's tensors: the base of every arena
         self.meta.c.W1_image = ptr(self.images)
-        self.runs = MocRuns(n_runs=R, slide_stride=n, par_stride=self.par_stride, image_stride=self.img_stride)
         self.turn, self.ahead, self.steps_done = 0, None, [None, None]
         self.last = None
         # The runs step in lockstep inside a GROUP; several groups are independent chains on streams of their own, whose
@@ -141,20 +168,31 @@ class TrainRuns:
         # a few dozen CUs busy (include/moc_hip.h moc_train_runs_mode)
         self.mode = int(lib().moc_train_runs_mode(C.byref(self.batches[0].c), C.byref(self.batches[0].meta_ws()[1])))
         assert self.mode != 0, "train_runs: this shape takes the three-launch step, whose scratch is one per batch -- train the runs one by one"
-        G_default = (R + 7) // 8 if self.mode == 1 else R
-        G = max(1, min(R, int(os.environ.get("MOC_RUNS_GROUPS", str(G_default)))))        # (measured, lockstep: chains of up to eight runs)
-        per = (R + G - 1) // G
+        cap = 8 if self.mode == 1 else 1                      # (measured, lockstep: chains of up to eight runs)
+        if "MOC_RUNS_GROUPS" in os.environ:
+            G = max(1, min(R, int(os.environ["MOC_RUNS_GROUPS"])))
+            cap = min(MAX_CHAIN, (R + G - 1) // G)
+        # a chain's runs share the visits per pass and the step count, and lie a constant stride apart in the arenas and in
+        # the batches: chains are cut where the run indices stop being consecutive
         self.groups = []
-        for r0 in range(0, R, per):
-            r1 = min(R, r0 + per)
-            mc = type(self.meta.c).from_buffer_copy(self.meta.c)
-            for name in ("W1", "b1", "W2", "b2", "m_W1", "m_b1", "m_W2", "m_b2", "v_W1", "v_b1", "v_W2", "v_b2"):
-                setattr(mc, name, getattr(self.meta.c, name) + 4 * r0 * self.par_stride)
-            mc.W1_image = ptr(self.images) + r0 * self.img_stride
-            self.groups.append({"r0": r0, "meta": mc, "runs": MocRuns(n_runs=r1 - r0, slide_stride=n, par_stride=self.par_stride,
-                                                                  image_stride=self.img_stride),
-                                "w2alt": ptr(self.W2_alt) + 4 * r0 * 4 * H,
-                                "stream": None if r0 == 0 else torch.cuda.Stream(device=device)})
+        for chain in group_runs([(n_, st_) for n_, st_ in zip(self.run_n, run_steps)], cap):
+            pieces = [[chain[0]]]
+            for r in chain[1:]:
+                if r == pieces[-1][-1] + 1:
+                    pieces[-1].append(r)
+                else:
+                    pieces.append([r])
+            for piece in pieces:
+                r0, n_ = piece[0], self.run_n[piece[0]]
+                mc = type(self.meta.c).from_buffer_copy(self.meta.c)
+                for name in ("W1", "b1", "W2", "b2", "m_W1", "m_b1", "m_W2", "m_b2", "v_W1", "v_b1", "v_W2", "v_b2"):
+                    setattr(mc, name, getattr(self.meta.c, name) + 4 * r0 * self.par_stride)
+                mc.W1_image = ptr(self.images) + r0 * self.img_stride
+                self.groups.append({"r0": r0, "n": n_, "slide0": self.run_slide0[r0], "meta": mc,
+                                    "runs": MocRuns(n_runs=len(piece), slide_stride=n_, par_stride=self.par_stride,
+                                                    image_stride=self.img_stride),
+                                    "w2alt": ptr(self.W2_alt) + 4 * r0 * 4 * H,
+                                    "stream": None if not self.groups else torch.cuda.Stream(device=device)})
 
     # ---- the masks of one pass: every run draws its own, side by side (moc_host_draw_masks releases the GIL)
     def _draw(self, buf):
@@ -172,8 +210,8 @@ class TrainRuns:
                 kept = int(m.sum())
             else:
                 g.set_state(st)
-            # the run's slides are slides r * n ... of the batch: its largest kept-row count, from the same thread
-            mk = lib().moc_host_max_kept(buf.data_ptr(), C.c_void_p(C.addressof(off_c) + 8 * r * self.n), self.n)
+            # the run's slides are slides run_slide0[r] ... of the batch: its largest kept-row count, from the same thread
+            mk = lib().moc_host_max_kept(buf.data_ptr(), C.c_void_p(C.addressof(off_c) + 8 * self.run_slide0[r]), self.run_n[r])
             return int(kept), int(mk)
         res = list(self.pool.map(one, range(self.R)))
         return sum(k for k, _ in res), max(m for _, m in res)
@@ -228,6 +266,11 @@ class TrainRuns:
         t, ws0 = batch.meta_ws()
         batch.publish_n_sel()
         self.meta.refresh()
+        for grp in self.groups:                               # the chain's own step count: its runs' optimizers hold it
+            steps = {int(self.optimizers[r].state[self.models[r].model[0].weight]["step"])
+                     for r in range(grp["r0"], grp["r0"] + grp["runs"].n_runs)}
+            assert len(steps) == 1, "train_runs: the runs of a chain no longer agree on the Adam step count"
+            grp["step"] = steps.pop()
         main = engine.stream_obj()
         ready = None
         if len(self.groups) > 1:
@@ -239,10 +282,11 @@ class TrainRuns:
             ws = type(ws0).from_buffer_copy(ws0)
             ws.W2_alt = grp["w2alt"]
             mc = grp["meta"]
-            mc.lr, mc.beta1, mc.beta2, mc.eps, mc.weight_decay, mc.step = (self.meta.c.lr, self.meta.c.beta1, self.meta.c.beta2,
-                                                                            self.meta.c.eps, self.meta.c.weight_decay, self.meta.c.step)
+            mc.lr, mc.beta1, mc.beta2, mc.eps, mc.weight_decay = (self.meta.c.lr, self.meta.c.beta1, self.meta.c.beta2,
+                                                                  self.meta.c.eps, self.meta.c.weight_decay)
+            mc.step = grp["step"]
             return lib().moc_train_steps_runs(C.byref(batch.c), C.byref(mc), C.byref(grp["runs"]), C.byref(ws), ptr(self.labels),
-                                              grp["r0"] * self.n, self.n, use, raw_stream)
+                                              grp["slide0"], grp["n"], use, raw_stream)
         main_raw = engine._stream()
         raw_of = lambda grp: main_raw if grp["stream"] is None else C.c_void_p(grp["stream"].cuda_stream)
         for grp in self.groups:
@@ -267,10 +311,10 @@ class TrainRuns:
                 joins.append(ev)
         for ev in joins:
             main.wait_event(ev)
-        for opt in self.optimizers:                           # n fused Adam steps in every optimizer's own counters
+        for opt, n_ in zip(self.optimizers, self.run_n):      # n fused Adam steps in every optimizer's own counters
             for st in opt.state.values():
                 if "step" in st:
-                    st["step"] += self.n
+                    st["step"] += n_
         self.last = (batch, self.labels)
         mark = torch.cuda.Event()
         mark.record(engine.stream_obj())
@@ -286,6 +330,9 @@ class TrainRuns:
         self.ahead = {"turn": other, "done": done, "head_only": not self.lookahead}
 
     def losses(self):
-        """[R, n] losses of the last pass (device)."""
+        """[R, n] losses of the last pass (device); runs of different pass lengths: a list of R tensors [n_r]."""
         batch, _ = self.last
-        return batch.meta_ws()[0]["loss"].view(self.R, self.n)
+        loss = batch.meta_ws()[0]["loss"]
+        if self.n is not None:
+            return loss.view(self.R, self.n)
+        return [loss[s0:s0 + n_] for s0, n_ in zip(self.run_slide0, self.run_n)]
