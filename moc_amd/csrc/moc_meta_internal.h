@@ -1,0 +1,138 @@
+// What the two halves of phase B share: moc_meta_forward.hip (the meta forward) and moc_meta.hip (the step).  Private to
+// those two sources; nothing here is exported from the library.
+#pragma once
+#include "moc_common.h"
+
+namespace moc_meta_internal __attribute__((visibility("hidden"))) {
+
+constexpr int H = MOC_HIDDEN;
+
+// ------------------------------------------------------------------ tile records (round 4)
+// The step kernel used to request and rank ALL S x C mixed scores of the slide the forward had just written -- a memory
+// round trip of sixteen loads per thread, then the candidate search over them on sixteen waves of one CU.  The forward's
+// workgroups now leave, per 16-row tile and class, the tile's TILE_R largest scores as RECORDS -- the key (score | ~row),
+// the row's id in the bag, its four gates and its four candidate scores: everything the backward needs of a pooled row
+// except its hidden activations and the row itself -- plus rho = the key of the tile's (TILE_R + 1)-th largest score.
+// The step kernel reads a class's ceil(S / 16) x TILE_R keys with ONE wave, finds a lower bound T0 of the K-th largest
+// score (the K-th largest of sixteen group maxima: group g = the tiles g, g + 16, ...) and pools among the records >= T0.
+// That is EXACT whenever every score >= T0 is a record, i.e. when no tile holds more than TILE_R of them: rho < T0 for
+// every tile -- checked; otherwise (and for more than 64 candidates) the kernel falls back to the full scores, which the
+// forward still writes.  Same rows, same (value desc, row asc) order, same sum: same bits.
+constexpr int TILE_R = 4;
+constexpr int MOC_MAX_RUNS = 16;        // meta-learners one launch can serve (moc_train_steps_runs)
+constexpr int MOC_TILE_PATH_RECORDS = 1000001, MOC_TILE_PATH_FULL = 1000002;   // left in ws->n_pair[0] by the tile-record step
+struct TileWs {
+    float4* lam;                 // [slots] gates of the record's row
+    float4* sc;                  // [slots] its candidate scores s_p[c], s_sigma[c], s_delta, s_beta
+    unsigned long long* key;     // [slots] (moc_key_desc(score) << 32) | ~row; high word 0: empty
+    int64_t* rid;                // [slots] sel_row of the row
+    uint32_t* rho;               // [slots / TILE_R] high word of the (TILE_R + 1)-th largest key of the (tile, class); 0: none
+};
+// Slide b owns the slots from slot0 = ((row_off[b] >> 4) + b) * C * TILE_R on: C * cap * TILE_R of them, cap = ceil(rows of
+// the slide / 16), class-major: record r of (tile x, class c) is slot0 + (c * cap + x) * TILE_R + r (a class's records are
+// contiguous: one wave reads them); rho of (x, c) is entry slot0 / TILE_R + c * cap + x.
+__host__ __device__ inline int64_t tile_slots(int64_t total_rows, int n_slides, int C) {
+    return ((total_rows >> 4) + n_slides + 2) * (int64_t)C * TILE_R;
+}
+__host__ __device__ inline TileWs tile_carve(void* p, int64_t ns) {
+    TileWs T;
+    unsigned char* q = (unsigned char*)p;
+    T.lam = (float4*)q; q += ns * 16;
+    T.sc = (float4*)q; q += ns * 16;
+    T.key = (unsigned long long*)q; q += ns * 8;
+    T.rid = (int64_t*)q; q += ns * 8;
+    T.rho = (uint32_t*)q;
+    return T;
+}
+__host__ __device__ inline size_t tile_bytes(int64_t ns) { return (size_t)ns * 48 + (size_t)(ns / TILE_R) * 4 + 16; }
+
+// Epilogue of a forward workgroup: thread t = class * 16 + row holds the mixed score v of (row0 + row, class); the 16 rows
+// of a class are 16 consecutive lanes (one DPP row).  Every lane ranks its key among the row's sixteen by fifteen row
+// rotations (keys are unique: absent rows carry (0 | ~row)), ranks 0 .. TILE_R-1 write their record, rank TILE_R writes rho.
+__device__ __forceinline__ void tile_emit(const TileWs& T, int64_t tc, bool ok, float v, int row, int64_t rid, float4 lam, float4 sc) {
+    const unsigned hi = ok ? moc_key_desc(v) : 0u, lo = ~(unsigned)row;
+    int rank = 0;
+#define MOC_ROR(n)                                                                                              \
+    {                                                                                                           \
+        const unsigned ohi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)hi, 0x120 + n, 0xf, 0xf, false);     \
+        const unsigned olo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)lo, 0x120 + n, 0xf, 0xf, false);     \
+        rank += (ohi > hi || (ohi == hi && olo > lo)) ? 1 : 0;                                                  \
+    }
+    MOC_ROR(1) MOC_ROR(2) MOC_ROR(3) MOC_ROR(4) MOC_ROR(5) MOC_ROR(6) MOC_ROR(7) MOC_ROR(8)
+    MOC_ROR(9) MOC_ROR(10) MOC_ROR(11) MOC_ROR(12) MOC_ROR(13) MOC_ROR(14) MOC_ROR(15)
+#undef MOC_ROR
+    if (rank < TILE_R) {
+        const int64_t slot = tc * TILE_R + rank;
+        T.key[slot] = ((unsigned long long)hi << 32) | lo;
+        T.rid[slot] = rid;
+        T.lam[slot] = lam;
+        T.sc[slot] = sc;
+    } else if (rank == TILE_R) {
+        T.rho[tc] = hi;
+    }
+}
+
+// An entry of an array inside the kernel's (single, by-value) argument struct, read straight from the kernel-argument
+// segment by a uniform index: indexing the struct itself with a runtime index makes hipcc copy all of it to scratch.
+template <typename T>
+__device__ __forceinline__ T kernarg_at(size_t off) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef __attribute__((address_space(4))) const char* kp_t;
+    kp_t p = (kp_t)__builtin_amdgcn_kernarg_segment_ptr();
+    return *(__attribute__((address_space(4))) const T*)(p + off);
+#else
+    return T();
+#endif
+}
+
+// ---- W1 image (the forward reads it, the step's W1 update rewrites it) -----------------------
+// The forward's B operand is W1^T: B[k][n] = W1[n][k].  Read from the [H][D] parameter tensor,
+// a wave's fragment load touches 64 scattered 16-B pieces (16 rows 2 KB apart) and the address
+// unit, not HBM, sets the pace.  So the kernels keep a second copy in fragment order -- one
+// contiguous 1 KiB per wave-load -- rewritten by the W1 update itself, hence always in sync:
+//   bf16 and fp32 bags: [nt][kk][term][lane][8] bf16, element j of lane l = term t of W1[nt*16 + (l&15)][kk*32 + (l>>4)*8 + j]
+//              (hi/mid/lo split, 24 mantissa bits: bf16 MFMA with fp32-exact products; fp32 bags split their rows
+//              the same way, fwd_split4 / fwd_mfma6 in moc_meta_forward.hip)
+//   fp16 bags: as bf16, the three fp16 terms of W1 * 2^10 (moc_common.h); the forward scales back
+template <bool F16>
+__device__ __forceinline__ void w1_image_store_half(unsigned char* img, int D, int h, int d, float w) {
+    const int KK = D / 32;
+    const int nt = h >> 4, kk = d >> 5, lane = (((d & 31) >> 3) << 4) | (h & 15), j = d & 7;
+    uint16_t* o = reinterpret_cast<uint16_t*>(img) + ((size_t)(nt * KK + kk) * 3 * 64 + lane) * 8 + j;
+    uint16_t hi, mid, lo;
+    moc_split3<F16>(w, MOC_F16_W1_SCALE, hi, mid, lo);
+    o[0] = hi;
+    o[64 * 8] = mid;
+    o[2 * 64 * 8] = lo;
+}
+__device__ __forceinline__ void w1_image_store_bf16(unsigned char* img, int D, int h, int d, float w) {
+    w1_image_store_half<false>(img, D, h, d, w);
+}
+__device__ __forceinline__ void w1_image_store_f32(unsigned char* img, int D, int h, int d, float w) {
+    w1_image_store_half<false>(img, D, h, d, w);            // the bf16 bags' image: fp32 rows are split into bf16 terms too
+}
+// storage code (MOC_F32 / MOC_BF16 / MOC_F16) known at run time
+__device__ __forceinline__ void w1_image_store(int dt, unsigned char* img, int D, int h, int d, float w) {
+    if (dt == MOC_F16) w1_image_store_half<true>(img, D, h, d, w);
+    else if (dt == MOC_BF16) w1_image_store_half<false>(img, D, h, d, w);
+    else w1_image_store_f32(img, D, h, d, w);
+}
+
+// ------------------------------------------------------------------ the forward's host side, as the step calls it
+// (moc_meta_forward.hip, but for tiles_ok: moc_meta.hip, the step's own limits)
+// the argument checks every entry over a meta-learner and its work arrays starts with
+int check_meta(const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws_t* ws, const char* who, bool need_adam,
+               bool need_grad, bool need_h1 = true);
+// rewrites the W1 image(s) from the parameters; R: one image per run (grid.y = run), NULL: M's one
+int launch_w1_images(const moc_batch_t* B, const moc_meta_t* M, const moc_runs_t* R, hipStream_t s);
+// the most selected rows a slide of the batch can have
+int s_bound(const moc_batch_t* B);
+// whether the one-launch step over tile records serves this shape
+bool tiles_ok(const moc_batch_t* B, const moc_meta_ws_t* ws);
+// The forward of slides [slide0, slide0 + n) into ws.  emit_tiles: the one-launch step over tile records follows (training
+// step of one slide): leave the records.  runs != nullptr: the training forward of runs->n_runs meta-learners in one launch
+// (moc_train_steps_runs), `M->W2` / `w2_stride` = where their current W2 lives.
+int launch_forward(const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws_t* ws, int slide0, int n, uint32_t use_bits,
+                   hipStream_t s, bool emit_tiles = false, const moc_runs_t* runs = nullptr, int64_t w2_stride = 0);
+
+}  // namespace moc_meta_internal

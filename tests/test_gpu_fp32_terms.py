@@ -1,5 +1,5 @@
 """fp32 bags on the bf16 matrix cores: every fp32-bag forward multiplies a row by W1 as the six products of their three
-bf16 terms (moc_meta.hip fwd_split4 / fwd_mfma6; the W1 image holds moc_split3 of W1).  Needs an MI355X: run with -m gpu.
+bf16 terms (moc_meta_forward.hip fwd_split4 / fwd_mfma6; the W1 image holds moc_split3 of W1).  Needs an MI355X: run with -m gpu.
 
 Stated bound: against a float64 product of the same rows, the pre-activations (read back through the hidden layer,
 relu(x W1^T + b1)) are within 1e-6 absolute on values up to 1 (relative above; 2e-6 at D = 1024) and within twice the error of an fp32 fused-multiply-add chain
