@@ -526,6 +526,19 @@ int moc_topk_mean(const float* keys, int64_t key_stride, const float* vals, int6
                   int smallest, float* pooled, int32_t* idx_out, int32_t* cnt_out,
                   moc_stream_t stream);
 
+/* ---- pooling at several K from one ranking (sensitivity sweeps) ----------
+ * For each segment s and class c: rank as moc_topk_mean does (largest first, or smallest first when `smallest`; ties:
+ * lower row first) ONCE to Kmax = max(Ks), and for every i write the mean of the first min(Ks[i], len) values, summed
+ * in rank order, to pooled[(i * n_seg + s) * C + c] -- bit for bit moc_topk_mean at K = Ks[i].
+ * Ks: HOST array, 1 <= n_K <= 8, every K in [1, 64], any order, repeats allowed.
+ * idx_out (nullable) int32 [n_seg, C, Kmax], cnt_out (nullable) [n_seg, C] = min(Kmax, len): as moc_topk_mean at Kmax
+ * (an empty segment's idx_out row is all -1).  An empty segment pools to NaN for every K.
+ * Additive to ABI 20: the version number is unchanged. */
+int moc_topk_mean_multi(const float* keys, int64_t key_stride, const float* vals, int64_t val_stride,
+                        const int64_t* seg_off, const int32_t* seg_len /*nullable*/, int n_seg, int C,
+                        const int32_t* Ks, int n_K, int smallest, float* pooled, int32_t* idx_out, int32_t* cnt_out,
+                        moc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -122,6 +122,8 @@ SIGNATURES = {
     "moc_cu_census": (C.c_int, [_p, C.c_int, C.c_int, _p]),
     "moc_topk_mean": (C.c_int, [_p, C.c_int64, _p, C.c_int64, _p, _p, C.c_int, C.c_int, C.c_int,
                                 C.c_int, _p, _p, _p, _p]),
+    "moc_topk_mean_multi": (C.c_int, [_p, C.c_int64, _p, C.c_int64, _p, _p, C.c_int, C.c_int, _p, C.c_int,
+                                      C.c_int, _p, _p, _p, _p]),
 }
 
 _lib = None

@@ -1044,6 +1044,33 @@ def topk_mean(keys: torch.Tensor, vals: torch.Tensor, K: int, smallest=False, ke
     return (pooled, idx, cnt) if want_idx else pooled
 
 
+MULTI_MAX_K, MULTI_MAX_NK = 64, 8       # moc_topk_mean_multi: one rank per lane; the Ks travel in the kernel's arguments
+
+
+def topk_mean_multi(keys: torch.Tensor, vals: torch.Tensor, Ks, smallest=False, key_shared=False,
+                    want_idx=False, seg_off: torch.Tensor | None = None, seg_len: torch.Tensor | None = None):
+    """topk_mean at every K of `Ks` (at most 8, each at most 64) from ONE ranking: pooled [n_K, n_seg, C], slab i bit for
+    bit topk_mean(..., Ks[i]) (and, with want_idx, idx [n_seg, C, max(Ks)], cnt [n_seg, C] as topk_mean at max(Ks)).
+    seg_len (device int32 [n_seg], optional): segment lengths where they are not the gaps of seg_off."""
+    assert keys.is_cuda and vals.is_cuda and keys.dtype == vals.dtype == torch.float32
+    Ks = [int(k) for k in Ks]
+    keys, vals = keys.contiguous(), vals.contiguous()
+    Cc, N = vals.shape
+    dev = vals.device
+    if seg_off is None:
+        seg_off = torch.tensor([0, N], dtype=torch.int64, device=dev)
+    n_seg = seg_len.numel() if seg_len is not None else seg_off.numel() - 1
+    pooled = torch.empty((len(Ks), n_seg, Cc), dtype=torch.float32, device=dev)
+    kmax = max(Ks) if Ks else 1
+    idx = torch.empty((n_seg, Cc, kmax), dtype=torch.int32, device=dev) if want_idx else None
+    cnt = torch.empty((n_seg, Cc), dtype=torch.int32, device=dev) if want_idx else None
+    ks_c = (C.c_int32 * max(len(Ks), 1))(*Ks)
+    check(lib().moc_topk_mean_multi(ptr(keys), 0 if key_shared else N, ptr(vals), N, ptr(seg_off), ptr(seg_len), n_seg, Cc,
+                                    C.cast(ks_c, C.c_void_p), len(Ks), int(bool(smallest)), ptr(pooled), ptr(idx), ptr(cnt),
+                                    _stream()), "moc_topk_mean_multi")
+    return (pooled, idx, cnt) if want_idx else pooled
+
+
 def gated_attention_pool(h: torch.Tensor, Wa, ba, Wb, bb, Wc, bc):
     """SURVEY.md section 8 row f4 (models/model_clam.py:41-64, :178-183, :206): h [N, L] fp32 on the GPU,
     Wa / Wb [D, L], Wc [K, D] in nn.Linear layout.  -> (A_raw [K, N], M [K, L])."""

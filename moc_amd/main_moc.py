@@ -784,6 +784,183 @@ def evaluation(model, loader, device, args):
     return _metrics(pooled, labels, losses, len(loader.dataset), real_len, args)
 
 
+# ---- sensitivity sweeps: the (topj, topk, discard) table of one split from ONE score pass ---------------------------------
+SWEEP_MAX_TOPK = engine.MULTI_MAX_K     # one ranking serves every K up to here bit for bit (moc_topk_mean_multi)
+ZS_POOLING_FUNCS = (topj_pooling, delta_softmax_classifier_pooling, delta_diff_classifier_pooling,
+                    bottomk_irrel_classifier_pooling)
+
+
+def _sweep_checks(who, loader, topks):
+    topks = [int(k) for k in topks]
+    assert len(topks) >= 1, f"{who}: no topk given"
+    assert all(1 <= k <= SWEEP_MAX_TOPK for k in topks), \
+        f"{who}: every topk must lie in [1, {SWEEP_MAX_TOPK}] (above {SWEEP_MAX_TOPK} a K's mean is no prefix of a longer ranking's sum); got {topks}"
+    assert isinstance(loader, ResidentBags), f"{who}: resident splits only (main_moc.ResidentBags)"
+    assert not loader.loader_seed_draw, f"{who}: loader_seed_draw splits are not swept"
+    return topks
+
+
+def _pool_slabs(keys, vals, topks, lab, n, small=False, shared=False, seg_off=None, seg_len=None):
+    """[n_K, n, C + 1] on the device: per K the pooled logits of moc_topk_mean at that K | their loss (moc_ce_loss) -- one
+    ranking per group of at most eight K."""
+    Cc = vals.size(0)
+    out = torch.empty((len(topks), n, Cc + 1), dtype=torch.float32, device=vals.device)
+    loss = torch.empty(n, dtype=torch.float32, device=vals.device)
+    pred = torch.empty(n, dtype=torch.int32, device=vals.device)
+    for g0 in range(0, len(topks), engine.MULTI_MAX_NK):
+        ks = topks[g0:g0 + engine.MULTI_MAX_NK]
+        slabs = engine.topk_mean_multi(keys, vals, ks, smallest=small, key_shared=shared, seg_off=seg_off, seg_len=seg_len)
+        for i in range(len(ks)):
+            engine.check(engine.lib().moc_ce_loss(engine.ptr(slabs[i]), engine.ptr(lab), n, Cc, engine.ptr(loss), engine.ptr(pred),
+                                                  engine._stream()), "moc_ce_loss")
+            out[g0 + i, :, :Cc] = slabs[i]
+            out[g0 + i, :, Cc] = loss
+    return out
+
+
+def _pool_loss_slabs(batch, topks, lab, n):
+    """The same [n_K, n, C + 1] by evaluation()'s own launch, moc_pool_loss, once per K (the batch's topk set to it).  For
+    3 .. 16 classes: there evaluation() may pool and take the loss in ONE kernel (moc_meta.hip pool_step_kernel, K <= 16),
+    whose cross entropy adds the C exponentials in a butterfly where moc_ce_loss adds them in class order -- the same sum
+    for one or two classes, and never taken above sixteen, but in between a loss could differ in its last bit.  The cell
+    must be evaluation()'s float, so it takes evaluation()'s launch; the ranking it repeats is the cheap end of a tail."""
+    t, ws = batch.meta_ws()
+    Cc = batch.C
+    out = torch.empty((len(topks), n, Cc + 1), dtype=torch.float32, device=batch.device)
+    w = type(ws).from_buffer_copy(ws)
+    idx = torch.empty((n, Cc, max(topks)), dtype=torch.int32, device=batch.device)     # (the batch's own holds args.topk rows)
+    w.topk_idx = engine.ptr(idx)
+    keep = batch.c.topk
+    try:
+        for i, k in enumerate(topks):
+            batch.c.topk = k
+            engine.check(engine.lib().moc_pool_loss(engine.C.byref(batch.c), engine.C.byref(w), engine.ptr(lab), 0, n,
+                                                    engine._stream()), "moc_pool_loss")
+            out[i, :, :Cc] = t["pooled"]
+            out[i, :, Cc] = t["loss"]
+    finally:
+        batch.c.topk = keep
+    return out
+
+
+def evaluation_sweep(model, loader, device, args, topjs, topks, discard_sets=None):
+    """{(topj, topk, tuple(discard)): evaluation(model, loader, device, args')} for every combination, args' = args with
+    those three fields -- the same floats -- from ONE score pass per chunk: the statistics depend on none of the three.  Per
+    chunk: mask compaction + scores once; per (topj, discard) the selection, the candidates and the meta forward; one
+    moc_topk_mean_multi over the mixed scores for all topk (each at most 64) and moc_ce_loss per K (3 .. 16 classes:
+    _pool_loss_slabs); one device-to-host copy per (topj, discard).
+    discard_sets=None: [args.discard_classifiers].  Resident splits without loader_seed_draw only."""
+    topks = _sweep_checks("evaluation_sweep", loader, topks)
+    topjs = [int(j) for j in topjs]
+    assert topjs and min(topjs) >= 1, "evaluation_sweep: topj must be >= 1"
+    sets = [tuple(d) for d in ([args.discard_classifiers or ()] if discard_sets is None else discard_sets)]
+    assert sets, "evaluation_sweep: no discard set given"
+    if model.training:
+        model.eval()
+    parts = {(j, d): [] for j in topjs for d in sets}
+    labels = []
+    with torch.no_grad():
+        real_len = loader.dataset.real_len()
+        set_len = len(loader.dataset)
+        loader.dataset.repeat_num = real_len
+        try:
+            bank, batches = _eval_batches(loader, device, args, "eval")
+            meta = MetaState(model)
+            for batch, lab, lab_list in batches:
+                n = batch.n_slides
+                tensors, _ = batch.meta_ws()
+                keep = (batch.c.topj, batch.c.discard_bits, batch.c.flags)      # (the batch may be a cached plan's)
+                try:
+                    # phase_a(for_eval=True)'s layout, then its first two launches -- once
+                    batch._layout(engine.COMPACT_STATS and batch.Ce > 16, cand_from_stats=engine.CAND_FROM_STATS and batch.C > 4)
+                    batch._n_sel_stale()
+                    engine.check(engine.lib().moc_mask_compact(engine.C.byref(batch.c), engine._stream()), "moc_mask_compact")
+                    engine.check(engine.lib().moc_scores(engine.C.byref(batch.c), engine.ptr(bank.image), engine._stream()), "moc_scores")
+                    for ci, (j, d) in enumerate(parts):
+                        batch.c.topj, batch.c.discard_bits = j, engine._lib.discard_bits(d)
+                        if ci > 0:
+                            # the selectors only SET flags: the score pass cleared them for the first configuration, the
+                            # sweep clears what the configuration before this one selected
+                            batch.sel_flag.zero_()
+                        batch.select()
+                        batch.gather_candidates()
+                        engine.meta_forward(batch, meta, 0, n, engine.eval_use_bits(d), keep_hidden=False)
+                        mixed = tensors["mixed"]
+                        if batch.C <= 2 or batch.C > 16:
+                            slabs = _pool_slabs(mixed, mixed, topks, lab, n, seg_off=batch.row_off, seg_len=batch.n_sel)
+                        else:
+                            slabs = _pool_loss_slabs(batch, topks, lab, n)
+                        parts[(j, d)].append(slabs.cpu())
+                finally:
+                    batch.c.topj, batch.c.discard_bits, batch.c.flags = keep
+                    batch._n_sel_stale()
+                labels.extend(lab_list)
+        finally:
+            loader.dataset.repeat_num = set_len
+    out = {}
+    for (j, d), chunks in parts.items():
+        allv = torch.cat(chunks, 1)
+        for i, k in enumerate(topks):
+            out[(j, k, d)] = _metrics(allv[i, :, :-1].contiguous(), labels, allv[i, :, -1].tolist(), len(loader.dataset), real_len, args)
+    return out
+
+
+def zs_evaluation_sweep(loader, device, args, topks, pooling_funcs=ZS_POOLING_FUNCS):
+    """{(pooling_func.__name__, topk): zs_evaluation(loader, device, args', pooling_func)} with args'.topk = topk -- the
+    same floats -- from one score pass (full statistics layout) and one moc_topk_mean_multi per pooling function, with
+    that function's key / value columns.  (bottomk_irrel_classifier_pooling ranks the logits of zeroshot_weights_ext: it
+    shares the pass when those foreground columns ARE zeroshot_weights, and gets a pass of its own otherwise.)  Only the
+    four fused pooling functions; any other callable stays with zs_evaluation."""
+    topks = _sweep_checks("zs_evaluation_sweep", loader, topks)
+    kinds = {topj_pooling: "topj", delta_softmax_classifier_pooling: "delta_softmax",
+             delta_diff_classifier_pooling: "delta_diff", bottomk_irrel_classifier_pooling: "bottomk"}
+    funcs = list(pooling_funcs)
+    assert funcs and all(f in kinds for f in funcs), \
+        "zs_evaluation_sweep: only the four fused pooling functions (others: zs_evaluation, one call each)"
+    Cn = zeroshot_weights.size(1)
+    ext_is_fg = bool(torch.equal(zeroshot_weights_ext[:, :Cn].to(device=zeroshot_weights.device, dtype=torch.float32),
+                                 zeroshot_weights.to(torch.float32)))
+    passes = {}                          # fg_from_ext -> the functions scored by that bank
+    for f in funcs:
+        passes.setdefault(kinds[f] == "bottomk" and not ext_is_fg, []).append(f)
+    parts = {f: [] for f in funcs}
+    labels = []
+    with torch.no_grad():
+        real_len = loader.dataset.real_len()
+        set_len = loader.dataset.repeat_num
+        loader.dataset.repeat_num = real_len
+        try:
+            for pi, (from_ext, fs) in enumerate(passes.items()):
+                bank, batches = _eval_batches(loader, device, args, "zs_bottomk" if from_ext else "zs_topj")
+                C_ = bank.C
+                for batch, lab, lab_list in batches:
+                    batch.scores(bank)
+                    st = batch.stats
+                    for f in fs:
+                        kind = kinds[f]
+                        if kind == "topj":
+                            keys, vals, small, shared = st[:C_], st[:C_], False, False
+                        elif kind == "delta_softmax":
+                            keys, vals, small, shared = st[C_:2 * C_], st[:C_], False, False
+                        elif kind == "delta_diff":
+                            keys, vals, small, shared = st[2 * C_:2 * C_ + 1], st[:C_], False, True
+                        else:
+                            keys, vals, small, shared = st[2 * C_ + 1:2 * C_ + 2], st[:C_], True, True
+                        parts[f].append(_pool_slabs(keys, vals, topks, lab, batch.n_slides, small, shared,
+                                                    seg_off=batch.row_off).cpu())
+                    if pi == 0:
+                        labels.extend(lab_list)
+        finally:
+            loader.dataset.repeat_num = set_len
+    out = {}
+    for f in funcs:
+        allv = torch.cat(parts[f], 1)
+        for i, k in enumerate(topks):
+            out[(f.__name__, k)] = _metrics(allv[i, :, :-1].contiguous(), labels, allv[i, :, -1].tolist(), len(loader.dataset),
+                                            real_len, args)
+    return out
+
+
 # plans of evaluation_runs, least recently used first.  A caller that evaluates one fixed set every epoch and a varying
 # subset of another (run_moc.main_runs: all train + validation splits, then the test splits of the runs that improved)
 # keeps its fixed plan for good: it is used between any two subset plans, so it is never the least recently used.  A new

@@ -16,8 +16,16 @@ from .patch_selection_classifier_index import row_stats, _require_gpu
 
 def _pool(keys, vals, topj, maxj, smallest=False, shared=False, return_indices=False):
     pooled = {}
-    for j in topj:
-        pooled[j] = engine.topk_mean(keys, vals, min(j, maxj), smallest=smallest, key_shared=shared)
+    js = list(topj)
+    if 1 < len(js) <= engine.MULTI_MAX_NK and all(min(j, maxj) <= engine.MULTI_MAX_K for j in js):
+        # several entries: ONE ranking to the largest, every entry's mean from its prefix (moc_topk_mean_multi: the bits of
+        # a launch per entry)
+        slabs = engine.topk_mean_multi(keys, vals, [min(j, maxj) for j in js], smallest=smallest, key_shared=shared)
+        for i, j in enumerate(js):
+            pooled[j] = slabs[i]
+    else:
+        for j in js:
+            pooled[j] = engine.topk_mean(keys, vals, min(j, maxj), smallest=smallest, key_shared=shared)
     preds = {j: v.argmax(dim=1) for j, v in pooled.items()}
     if not return_indices:
         return preds, pooled
