@@ -249,6 +249,22 @@ int moc_gather_candidates(const moc_batch_t* B, void* selected_feat, moc_stream_
 /* all four above, in order */
 int moc_phase_a(const moc_batch_t* B, const void* bank, moc_stream_t stream);
 
+/* ---- hyper-parameter grids: one score pass for the slides that visit the same rows under the same mask ----------
+ * Runs that differ only in topj / topk / discard_bits see the same kept rows and the same statistics (everything in front of
+ * moc_select depends on none of the three).  After moc_mask_compact + moc_scores (or moc_scores_from_cache) over the LEADER
+ * slides, every follower slide b in [slide0, slide0 + n) with leader l = leader_of_slide[b] (device int32 [B->n_slides],
+ * indexed by the slide's position in the batch; a negative value: b is not a follower and is left alone) receives
+ *   n_kept[b] = n_kept[l];   kept[row_off[b] + i] = kept[row_off[l] + i];
+ *   stats[r][row_off[b] + i] = stats[r][row_off[l] + i]  for every row r of the layout B->flags names (2C+3, or C+5 with
+ *   MOC_STATS_COMPACT);   sel_flag[row_off[b] + i] = 0 (as the score pass leaves it)            for i < n_kept[l]
+ * -- everything moc_select / moc_gather_candidates read per slot; the follower then is, bit for bit, a slide the score pass
+ * ran over.  An unmasked batch copies the statistics of all rows of l.  A leader may lie behind its follower and may have
+ * several; a leader must not itself be a follower.  l is CLAMPED into the batch on the device and the copy never leaves
+ * either slide's slots (a follower and its leader are meant to have equal sizes): nothing outside the arrays is touched.
+ * Errors (not faults), before anything is launched: null B / leader_of_slide, a batch without stats / sel_flag, a bad slide
+ * range.  Additive to ABI 20: the version number is unchanged. */
+int moc_stats_share(const moc_batch_t* B, const int32_t* leader_of_slide, int slide0, int n, moc_stream_t stream);
+
 /* Phase A's result for slides [slide0, slide0+n) in a fixed-capacity, position-independent form -- what
  * slide_process hands to the meta-learner (main_moc.py:367-375: selected_feat + the four candidate matrices),
  * `cap` rows per slide: feat_out device [n][cap][D] in X's dtype, cand_out device [n][2C+2][cap] fp32; entries at

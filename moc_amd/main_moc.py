@@ -552,10 +552,14 @@ def train_runs(models, train_loaders, optimizers, device, args, generators=None)
     launch pair per meta-step (moc_amd.runs.TrainRuns; include/moc_hip.h moc_train_steps_runs).  Per run bit-identical to
     `train` from the same mask stream; run r's masks come from `generators[r]` (a private CPU torch.Generator each; by
     default seeded from the default generator on the first call).  The loaders are resident splits (ResidentBags); their
-    passes may differ in length (runs.group_runs: one lockstep chain per length).  -> the TrainRuns object (kept for the next pass: call again with the same lists)."""
+    passes may differ in length (runs.group_runs: one lockstep chain per length).  `args` may be a list of one namespace per
+    run: run r then trains with args[r].topj / .topk / .discard_classifiers (a hyper-parameter grid; runs that name the same
+    split object and hold equal generator states share one draw and one score pass per pass -- DESIGN.md section 9h).
+    -> the TrainRuns object (kept for the next pass: call again with the same lists)."""
     from .runs import TrainRuns
+    hp = lambda a: (a.topj, a.topk, tuple(sorted(a.discard_classifiers or ())))
     key = (tuple(id(m) for m in models), tuple(id(o) for o in optimizers), tuple(id(l) for l in train_loaders),
-           args.topj, args.topk, tuple(sorted(args.discard_classifiers or ())), tuple(len(l) for l in train_loaders))
+           tuple(hp(a) for a in args) if isinstance(args, (list, tuple)) else hp(args), tuple(len(l) for l in train_loaders))
     ent = _run_sets.get(key)
     if ent is None:
         if len(_run_sets) > 2:

@@ -8,6 +8,7 @@ around the GPU callables of moc_amd.main_moc.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 -m moc_amd.run_moc ...   # 8 GPUs
     python -m moc_amd.run_moc --folds 0,1,2,3,4 --shot 16 --seed 1 ...      # five folds in ONE process, stepped in lockstep
     python -m moc_amd.run_moc --shots 1,2,4,8,16 --folds 0,1,2,3,4 --seed 1 ...   # the launcher's whole grid in one process
+    python -m moc_amd.run_moc --topjs 100,400 --topks 5,10 --discard_sets none topk+bottomk --folds 0,1,2,3,4 --seed 1 ...   # a hyper-parameter grid
 
 Same flags and defaults as the reference, same result files (`zs_results_*`, `best_results_*`,
 `ablation_results_*`, `best_model_*.pt`, `summary_*.csv`) with the same keys.  Differences, all
@@ -90,6 +91,15 @@ def get_args(argv=None):
                         "--fold) in this process -- scripts/moc_train.sh's whole grid.  Run (S, F) writes into "
                         "{result_dir}/{S}_shot/ what `--fold F --shot S --result_dir {result_dir}/{S}_shot` writes alone, so that "
                         "`--summary --summary_dir {result_dir}` reads the tree.  Under a launcher the pairs are dealt to the ranks")
+    p.add_argument("--topjs", type=str, default=None,
+                   help="comma-separated topj values: train every configuration of --topjs x --topks x --discard_sets (a list that "
+                        "is not given: the one --topj / --topk / --discard_classifiers) for every fold of --folds (or the one --fold) "
+                        "in this process.  Run (J, K, set, F) writes into {result_dir}/topj{J}_topk{K}_{set}/ what `--topj J --topk K "
+                        "--discard_classifiers ... --fold F --result_dir {that dir}` writes alone.  With --seed the configurations "
+                        "of a fold draw the same masks and share one score pass per epoch (moc_amd.runs)")
+    p.add_argument("--topks", type=str, default=None, help="comma-separated topk values (see --topjs)")
+    p.add_argument("--discard_sets", nargs="*", default=None,
+                   help="discard sets, classifier names joined with + (topk+bottomk), `none` for the empty set (see --topjs)")
     p.add_argument("--patch_maps", type=str, default=None, choices=list(PATCH_MAP_CHOICES),
                    help="after main(), write per-patch maps (moc_amd.patch_maps) of these splits with the best checkpoint to "
                         "{result_dir}/patch_maps_shot_S_fold_F/{split}/ (default: none; test with --patch_maps_from)")
@@ -133,6 +143,8 @@ def summary(args):
     print("start summary")
     for shot in [1, 2, 4, 8]:
         summary_dir = args.summary_dir + f"/{shot}_shot"
+        if not os.path.isdir(summary_dir):          # a directory that holds the result files itself (a grid's configuration directory)
+            summary_dir = args.summary_dir
         summary_file = os.path.join(args.summary_dir, f"summary_{shot}.csv")
         folds = [0, 1, 2, 3, 4, "mean"]
 
@@ -248,7 +260,8 @@ def grid_bytes(footprints, D, itemsize, C):
         once for every run that names it): statistics, selection, candidates and mixed scores per row -- no H1 / gates --
         for every run's train and validation split (the plan of every epoch) and twice for its test split (the plans of
         two different sets of improved runs are kept, main_moc.EVAL_RUN_PLANS);
-      * every train split a second time with two sets of training work arrays (runs.TrainRuns packs its runs' bags);
+      * every DISTINCT train split a second time (runs.TrainRuns packs its runs' bags; splits that are one object -- the
+        configurations of a fold in a hyper-parameter grid -- once), and two sets of training work arrays per run;
       * the largest one-time packing copy (the splits of an evaluation pass are laid side by side)."""
     ws_eval = 4 * (2 * C + 3) + 4 * (2 * C + 2) + 13 + 4 * C
     ws_train = ws_eval + 4 * 64 + 16 + 8
@@ -259,8 +272,11 @@ def grid_bytes(footprints, D, itemsize, C):
                 seen.add(key)
                 total += rows * D * itemsize
                 pack[0 if s_i < 2 else 1] += rows * D * itemsize
-        (_, tr), (_, va), (_, te) = fp
-        total += (tr + va + 2 * te) * ws_eval + tr * (D * itemsize + 2 * ws_train)
+        (tr_key, tr), (_, va), (_, te) = fp
+        total += (tr + va + 2 * te) * ws_eval + tr * 2 * ws_train
+        if ("train copy", tr_key) not in seen:
+            seen.add(("train copy", tr_key))
+            total += tr * D * itemsize
     return total + max(pack)
 
 
@@ -272,11 +288,12 @@ def largest_grid(footprints, D, itemsize, C, free_bytes):
     return k
 
 
-def prepare(args, device, share=None):
+def prepare(args, device, share=None, share_train=False):
     """-> (train_loader, val_loader, test_loader) and the classifier bank installed in moc_amd.main_moc.  Inside a
     process group of more than one rank the three are moc_amd.dist.ShardedSplit objects (each rank holds its block).
     `share` (a dict kept by a caller that prepares several runs): a resident split whose key (split_footprints) is in it is
-    not loaded again -- the runs share the object and its array."""
+    not loaded again -- the runs share the object and its array (the train split too with `share_train`: the configurations of
+    one fold in a hyper-parameter grid)."""
     import torch.distributed as dist
     world = dist.get_world_size() if dist.is_initialized() else 1
     rank = dist.get_rank() if dist.is_initialized() else 0
@@ -290,7 +307,7 @@ def prepare(args, device, share=None):
         loaders = []
         for s, (base, n, rep) in enumerate(_synthetic_splits(args, C)):
             key = ("synthetic", s, base, n)
-            if share is not None and s > 0 and key in share:
+            if share is not None and (s > 0 or share_train) and key in share:
                 loaders.append(share[key])
                 continue
             sizes = synth.bag_sizes(base, n, 3000, fixed=False, lo=500, hi=8000)
@@ -303,7 +320,7 @@ def prepare(args, device, share=None):
                 continue
             bags, labels = synth.make_slide_set(base, sizes, 512, We, C)
             loaders.append(M.ResidentBags(bags, labels, device, dtype=dt, repeat_num=rep, cache_scores=bool(args.cache_scores) and s == 0))
-            if share is not None and s > 0:
+            if share is not None and (s > 0 or share_train):
                 share[key] = loaders[-1]
         return loaders
     task = TASKS[args.dataset]
@@ -317,7 +334,7 @@ def prepare(args, device, share=None):
         sp.load_full_path(True)
         sp.load_from_h5(True)
         key = ("files", s_i, tuple(str(v) for v in sp.slide_data["slide_id"]))
-        if share is not None and s_i > 0 and world == 1 and args.resident and key in share:
+        if share is not None and (s_i > 0 or share_train) and world == 1 and args.resident and key in share:
             loaders.append(share[key])
             continue
         if world > 1:
@@ -327,7 +344,7 @@ def prepare(args, device, share=None):
             loaders.append(to_resident(sp, device, {"bf16": torch.bfloat16, "fp16": torch.float16}.get(args.bag_dtype),
                                        loader_seed_draw=bool(args.loader_seed_draw)))
             loaders[-1].cache_scores = bool(args.cache_scores) and s_i == 0
-            if share is not None and s_i > 0:
+            if share is not None and (s_i > 0 or share_train):
                 share[key] = loaders[-1]
         else:
             loaders.append(torch.utils.data.DataLoader(sp, batch_size=1, shuffle=False, num_workers=1))
@@ -455,6 +472,26 @@ def main_runs(args_list, models, optimizers, loaders_list, device, generators=No
     R = len(models)
     a0 = args_list[0]
     tag = (lambda a: f"[shot {a.shot} fold {a.fold}]") if len({a.shot for a in args_list}) > 1 else (lambda a: f"[fold {a.fold}]")
+    # a hyper-parameter grid: the runs of every configuration (topj, topk, discard set), in order of first appearance
+    by_cfg = {}
+    for r, a in enumerate(args_list):
+        by_cfg.setdefault((a.topj, a.topk, tuple(a.discard_classifiers or ())), []).append(r)
+    if len(by_cfg) > 1:
+        fold_tag = tag
+        tag = lambda a: f"[topj {a.topj} topk {a.topk} {hgrid_discard_name(a.discard_classifiers)}] " + fold_tag(a)
+
+    def evaluate(ms, lds):
+        """evaluation_runs over (model, loader) pairs named by run index: its plan belongs to one `args`, so a grid evaluates
+        configuration by configuration (every call is the one the configuration alone makes)."""
+        if len(by_cfg) == 1:
+            return M.evaluation_runs([models[r] for r in ms], lds, device, a0)
+        out = [None] * len(ms)
+        for rs in by_cfg.values():
+            pick = [i for i, r in enumerate(ms) if r in rs]
+            if pick:
+                for i, e in zip(pick, M.evaluation_runs([models[ms[i]] for i in pick], [lds[i] for i in pick], device, args_list[rs[0]])):
+                    out[i] = e
+        return out
     assert a0.ablation_study == "none", "main_runs: the ablation study trains nothing -- run it per fold"
     st = []
     for r in range(R):
@@ -474,12 +511,11 @@ def main_runs(args_list, models, optimizers, loaders_list, device, generators=No
     M.pack_splits([ls[2] for ls in loaders_list])
     for epoch in range(getattr(a0, "epochs", 25)):
         print("Epoch: ", epoch)
-        M.train_runs(models, trains, optimizers, device, a0, generators=generators)
+        M.train_runs(models, trains, optimizers, device, a0 if len(by_cfg) == 1 else list(args_list), generators=generators)
         # all runs' train and validation splits in one pass, then the test splits of the runs that improved in another
-        ev = M.evaluation_runs(list(models) + list(models), trains + [ls[1] for ls in loaders_list], device, a0)
+        ev = evaluate(list(range(R)) + list(range(R)), trains + [ls[1] for ls in loaders_list])
         better = [r for r in range(R) if ev[R + r]["auc"] > st[r]["best_val"]]
-        ev_test = dict(zip(better, M.evaluation_runs([models[r] for r in better], [loaders_list[r][2] for r in better], device, a0))) \
-            if better else {}
+        ev_test = dict(zip(better, evaluate(better, [loaders_list[r][2] for r in better]))) if better else {}
         for r in range(R):
             a, s_ = args_list[r], st[r]
             train_eval, val_eval = ev[r], ev[R + r]
@@ -584,14 +620,145 @@ def cli_folds(args):
     return main_runs(args_list, models, optimizers, loaders_list, device, generators=gens)
 
 
+# ------------------------------------------------------------------ hyper-parameter grids (--topjs / --topks / --discard_sets)
+def hgrid_discard_name(d):
+    return "+".join(d) if d else "none"
+
+
+def hgrid_requested(args):
+    return any(getattr(args, n, None) is not None for n in ("topjs", "topks", "discard_sets"))
+
+
+def hgrid_configs(args):
+    """[(topj, topk, discard tuple)] of --topjs x --topks x --discard_sets in the given order (topj-major, the discard set
+    innermost); a list that is not given is the one --topj / --topk / --discard_classifiers.  The lists are parsed by
+    moc_amd.sweep's parsers (the same spellings); an empty or malformed one is refused."""
+    from .sweep import _int_list, parse_discard_set
+
+    def parsed(flag, fn, text):
+        try:
+            return fn(text)
+        except argparse.ArgumentTypeError as e:
+            raise SystemExit(f"{flag}: {e}")
+    js = [int(args.topj)] if args.topjs is None else parsed("--topjs", _int_list, args.topjs)
+    ks = [int(args.topk)] if args.topks is None else parsed("--topks", _int_list, args.topks)
+    if args.discard_sets is None:
+        ds = [tuple(args.discard_classifiers or ())]
+    else:
+        if len(args.discard_sets) == 0:
+            raise SystemExit("--discard_sets: an empty list -- name at least one set (`none` is the empty set)")
+        ds = [parsed("--discard_sets", parse_discard_set, t) for t in args.discard_sets]
+    for flag, vals in (("--topjs", js), ("--topks", ks), ("--discard_sets", ds)):
+        if len(set(vals)) != len(vals):
+            raise SystemExit(f"{flag}: a value named twice")
+    return [(j, k, d) for j in js for k in ks for d in ds]
+
+
+def hgrid_dir(result_dir, cfg):
+    """Where the runs of configuration (topj, topk, discard) write: {result_dir}/topj{J}_topk{K}_{set}."""
+    return os.path.join(result_dir, f"topj{cfg[0]}_topk{cfg[1]}_{hgrid_discard_name(cfg[2])}")
+
+
+def check_hgrid_args(args):
+    """Refusals of a hyper-parameter grid, from the command line alone (before any bag is loaded)."""
+    if not hgrid_requested(args):
+        return
+    if getattr(args, "shots", ""):
+        raise SystemExit("--topjs / --topks / --discard_sets do not combine with --shots: one --shot per grid")
+    if patch_map_splits(args) or args.patch_maps_from:
+        raise SystemExit("--topjs / --topks / --discard_sets do not combine with --patch_maps / --patch_maps_from: run one configuration at a time")
+    if args.loader_seed_draw:
+        raise SystemExit("--topjs / --topks / --discard_sets do not combine with --loader_seed_draw: the runs draw their masks from "
+                         "private generators (no DataLoader base-seed draw)")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1 and args.seed is None:
+        raise SystemExit("--topjs / --topks / --discard_sets under a launcher need --seed: every rank must build the same meta-learners")
+    if args.ablation_study != "none":
+        raise SystemExit("--topjs / --topks / --discard_sets train the meta-learner: the ablation study trains none")
+    hgrid_configs(args)
+
+
+def hgrid_blocks(n_configs, n_folds, max_runs):
+    """The configurations cut into blocks trained one after the other: whole configurations, as many as fit `max_runs` runs
+    (a configuration is n_folds runs).  -> list of lists of configuration indices.  Pure."""
+    if n_folds > max_runs:
+        raise SystemExit(f"--folds: {n_folds} folds in one process, at most {max_runs}")
+    per = max(1, max_runs // n_folds)
+    return [list(range(i, min(i + per, n_configs))) for i in range(0, n_configs, per)]
+
+
+def hgrid_runs(args, configs, folds):
+    """The runs' namespaces: configurations in the given order, fold-major inside one (the runs of a lockstep chain are
+    consecutive)."""
+    import copy
+    out = []
+    for cfg in configs:
+        for fold in folds:
+            a = copy.copy(args)
+            a.fold, a.topj, a.topk, a.discard_classifiers = fold, cfg[0], cfg[1], list(cfg[2])
+            a.result_dir = hgrid_dir(args.result_dir, cfg)
+            out.append(a)
+    return out
+
+
+def cli_hgrid(args):
+    """`--topjs / --topks / --discard_sets` (with --folds or the one --fold): every (configuration, fold) run in this process.
+    Under a launcher the configurations are dealt to the ranks, nothing exchanged."""
+    world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
+    configs = hgrid_configs(args)[rank::world]
+    folds = folds_of_rank(args.folds, 0, 1) if args.folds else [int(args.fold)]
+    device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")) if world > 1 else torch.cuda.current_device())
+    torch.cuda.set_device(device)
+    if not configs:
+        print(f"rank {rank}: no configuration to train")
+        return []
+    from . import runs as RUNS
+    blocks = hgrid_blocks(len(configs), len(folds), RUNS.MAX_RUNS)
+    # the footprint of the largest block before a bag is loaded: the splits of a fold count once for all its configurations
+    itemsize = 2 if args.bag_dtype in ("bf16", "fp16") else 4
+    C_ = _synthetic_classes(args) if args.synthetic else len(_label_map(args))
+    fps = {}
+    for a in hgrid_runs(args, configs[:1], folds):
+        fps[a.fold] = split_footprints(a)
+    need = grid_bytes([fps[f] for _ in blocks[0] for f in folds], FEATURE_DIM, itemsize, C_)
+    free = torch.cuda.mem_get_info(device)[0]
+    if need > free:
+        raise SystemExit(f"--topjs x --topks x --discard_sets: a block of {len(blocks[0])} configuration(s) x {len(folds)} fold(s) needs "
+                         f"about {need / 2**30:.1f} GiB of device memory, {free / 2**30:.1f} GiB are free: name fewer folds")
+    M.EVAL_RUN_PLANS = max(M.EVAL_RUN_PLANS, 3 * len(blocks[0]))      # (a plan per configuration and kind of pass)
+    out, share = [], {}
+    for block in blocks:
+        args_list, models, optimizers, loaders_list, gens = [], [], [], [], []
+        for a in hgrid_runs(args, [configs[i] for i in block], folds):
+            loaders = prepare(a, device, share=share, share_train=True)
+            assert all(isinstance(ld, M.ResidentBags) for ld in loaders), "a hyper-parameter grid needs resident splits (--resident 1)"
+            # exactly what the configuration's own `--fold F` command does with the default generator: seed, build the
+            # meta-learner, and the masks follow from wherever that leaves the stream -- with --seed the configurations of a
+            # fold start from equal generator states and share their masks
+            if args.seed is not None:
+                torch.manual_seed(args.seed)
+            model = M.senet(FEATURE_DIM, 4).to(device)
+            g = torch.Generator()
+            g.set_state(torch.get_rng_state())
+            args_list.append(a)
+            models.append(model)
+            optimizers.append(torch.optim.Adam(model.parameters(), lr=1e-3, weight_decay=1e-4))
+            loaders_list.append(loaders)
+            gens.append(g)
+        out += main_runs(args_list, models, optimizers, loaders_list, device, generators=gens)
+    return out
+
+
 def cli(argv=None):
     args = get_args(argv)
     if args.summary:
         summary(args)
         return None
+    check_hgrid_args(args)
     check_patch_map_args(args)
     if not torch.cuda.is_available():
         raise RuntimeError("moc_amd needs a GPU: there is no CPU fallback")
+    if hgrid_requested(args):
+        return cli_hgrid(args)
     if args.folds or args.shots:
         return cli_folds(args)
     world = int(os.environ.get("WORLD_SIZE", "1"))

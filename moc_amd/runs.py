@@ -11,8 +11,9 @@ state, its own stream of row masks -- `torch.rand(N) > 0.5` per slide drawn from
 reference's runs are separate processes, each with its own default generator).  Per run the result is bit-identical to
 training it alone with `main_moc.train` from the same generator state (tests/test_gpu_runs.py).
 
-What the runs share: the classifier bank, the hyper-parameters of Adam, topj / topk / discard_classifiers, storage type
-and width.  The models' parameter tensors and the optimizers' moments are re-seated as views into one arena per kind
+What the runs share: the classifier bank, the hyper-parameters of Adam, storage type and width.  topj / topk /
+discard_classifiers are common when `args` is one namespace and per run when it is a list of R of them (a hyper-parameter
+grid: DESIGN.md section 9h).  The models' parameter tensors and the optimizers' moments are re-seated as views into one arena per kind
 (state_dict() / load_state_dict() keep working; the tensors' values are preserved).
 
 Runs need NOT be alike in the number of visits per pass or in the Adam steps already taken (a shots x folds grid:
@@ -21,6 +22,13 @@ Runs need NOT be alike in the number of visits per pass or in the Adam steps alr
 chains of more than eight like runs already were; a chain ends its pass when its runs have made their visits.  The step
 kernels are the same.  Phase A still covers all runs' slides of a pass in one go, and every run still draws its masks
 from its private generator in its own loader order.
+
+A hyper-parameter grid trains the configurations of one (fold, shot, seed) on the same bags, and from equal generator states
+they draw the same masks: the kept-row lists, the score pass and the row statistics -- everything in front of moc_select --
+depend on none of topj / topk / discard_classifiers.  Runs whose split is the same object and whose generators hold the same
+state form a MASK GROUP per pass (`mask_groups`): its first run, the leader, draws and is scored; the others' slots are
+filled by moc_stats_share, and the selection runs once per distinct (topj, discard) over that configuration's slides.
+MOC_RUNS_SHARE=0 makes every run its own leader.
 """
 from __future__ import annotations
 
@@ -57,6 +65,27 @@ def group_runs(keys, cap=8):
     return chains
 
 
+def mask_groups(keys):
+    """Leader of every run for one pass' draw.  `keys[r]`: (id of the run's split, bytes of its generator's state) -- or None
+    for a run that takes no part.  Runs with equal keys form a group whose first member leads; -> list `leader` with
+    leader[r] = r for a leader (singletons and None keys included), else the index of the group's first run.  Pure."""
+    first, leader = {}, []
+    for r, k in enumerate(keys):
+        leader.append(r if k is None else first.setdefault(k, r))
+    return leader
+
+
+def consecutive_blocks(items):
+    """[a, a+1, a+2, b, b+1] -> [(a, 3), (b, 2)]: blocks of consecutive integers, in the given order.  Pure."""
+    out = []
+    for v in items:
+        if out and v == out[-1][0] + out[-1][1]:
+            out[-1] = (out[-1][0], out[-1][1] + 1)
+        else:
+            out.append((v, 1))
+    return out
+
+
 class TrainRuns:
     """R (model, optimizer, resident train split) triples trained in lockstep.  `generators`: one CPU torch.Generator
     per run -- the run's mask stream (default: fresh generators seeded from the default generator, in run order)."""
@@ -65,6 +94,15 @@ class TrainRuns:
         from . import main_moc as M
         R = len(models)
         assert 1 <= R <= MAX_RUNS and len(optimizers) == R and len(splits) == R, f"1 .. {MAX_RUNS} runs"
+        per_run = isinstance(args, (list, tuple))
+        args_list = list(args) if per_run else [args] * R
+        assert len(args_list) == R, "train_runs: one namespace, or one per run"
+        args = args_list[0]
+        assert all(a.n_classes == args.n_classes for a in args_list), "train_runs: the runs share the classifier bank"
+        # run r's (topj, topk, discard_bits); everything else is common
+        self.cfg = [(int(a.topj), int(a.topk), engine._lib.discard_bits(a.discard_classifiers)) for a in args_list]
+        self.run_use = [engine.train_use_bits(a.discard_classifiers) for a in args_list]
+        self.share = os.environ.get("MOC_RUNS_SHARE", "1") != "0"
         assert all(isinstance(sp, M.ResidentBags) for sp in splits), "train_runs: resident splits (main_moc.ResidentBags)"
         self.R, self.models, self.optimizers, self.splits, self.device = R, list(models), list(optimizers), list(splits), device
         self.run_n = [len(sp) for sp in splits]               # visits per pass of each run
@@ -83,24 +121,31 @@ class TrainRuns:
             "train_runs: one private CPU generator per run (the masks of a pass are drawn a pass ahead)"
         self.generators = list(generators)
         # ---- all runs' bags in one packed array (a one-time copy), the visits of run r at slides r * n ...
-        self.X = torch.cat([sp.X for sp in splits], 0) if R > 1 else splits[0].X
-        sizes, starts, labels, row0 = [], [], [], 0
+        # (splits that are the same object -- the configurations of one fold -- are placed once: their visits name the same rows)
+        uniq, split_row0 = [], {}
+        for sp in splits:
+            if id(sp) not in split_row0:
+                split_row0[id(sp)] = sum(u.X.size(0) for u in uniq)
+                uniq.append(sp)
+        self.X = torch.cat([sp.X for sp in uniq], 0) if len(uniq) > 1 else uniq[0].X
+        sizes, starts, labels = [], [], []
         self.run_rows = []                                   # (first flag, flags) of each run's pass
         for sp in splits:
             order = sp.visit_order()
-            rows = 0
+            rows, row0 = 0, split_row0[id(sp)]
             for k in order:
                 sizes.append(sp.sizes[k])
                 starts.append(row0 + sp.starts[k])
                 labels.append(sp.labels[k])
                 rows += sp.sizes[k]
             self.run_rows.append((sum(s_ for s_ in sizes) - rows, rows))
-            row0 += sp.X.size(0)
         bank = M._bank_for(self.X, device)
         assert bank.C == args.n_classes
-        self.bank, self.args = bank, args
+        self.bank, self.args, self.args_list = bank, args, args_list
         T = sum(sizes)
-        self.batches = [SlideBatch(self.X, sizes, bank.C, bank.Ce, args.topj, args.topk, args.discard_classifiers,
+        # (the batch's own topj / discard: run 0's; its topk: the largest, which sizes the work arrays -- every launch of a
+        # grid takes a copy of the struct carrying its configuration's values)
+        self.batches = [SlideBatch(self.X, sizes, bank.C, bank.Ce, args.topj, max(k for _, k, _ in self.cfg), args.discard_classifiers,
                                    mask=torch.ones(T, dtype=torch.uint8), x_starts=starts) for _ in range(2)]
         # (round 4 measurements, profiles/NOTES.md: the meta-steps crawl while a score pass streams beside them whether or not
         # it leaves them compute units, so phase A here runs at full width; MOC_RUNS_RESERVE_CUS brings the reservation back)
@@ -113,7 +158,7 @@ class TrainRuns:
         if os.environ.get("MOC_CACHE_SCORES", "0") == "1" or all(sp.cache_scores for sp in splits):
             # opt-in (main_moc.ResidentBags cache_scores): the statistics of every row once, then no score pass per epoch
             all_sizes, all_starts, r0_ = [], [], 0
-            for sp in splits:
+            for sp in uniq:
                 all_sizes += sp.sizes
                 all_starts += [r0_ + st for st in sp.starts[:-1]]
                 r0_ += sp.X.size(0)
@@ -161,21 +206,42 @@ class TrainRuns:
         self.meta.c.W1_image = ptr(self.images)
         self.turn, self.ahead, self.steps_done = 0, None, [None, None]
         self.last = None
+        # mask groups of the pass in each work-array set; `last_phase_a`: slides / scored_slides / shared_slides of the most
+        # recent draw (the look-ahead draws the NEXT pass' masks at the end of a pass), `trained_phase_a`: of the pass whose
+        # steps were issued last
+        self.pass_info, self.last_phase_a, self.trained_phase_a, self._lead_dev = [None, None], None, None, {}
         # The runs step in lockstep inside a GROUP; several groups are independent chains on streams of their own, whose
         # latency-bound kernels interleave on the device (one group: every launch serves all R runs)
         # Shapes outside the tile-record step (wide banks): moc_train_steps_runs takes a group's runs one after the other,
         # so every run is a group of its own -- R chains of (forward, top-K, wide step) side by side, each of which keeps
         # a few dozen CUs busy (include/moc_hip.h moc_train_runs_mode)
-        self.mode = int(lib().moc_train_runs_mode(C.byref(self.batches[0].c), C.byref(self.batches[0].meta_ws()[1])))
-        assert self.mode != 0, "train_runs: this shape takes the three-launch step, whose scratch is one per batch -- train the runs one by one"
-        cap = 8 if self.mode == 1 else 1                      # (measured, lockstep: chains of up to eight runs)
+        # asked per configuration: K <= 16 and C K <= 64 decide the step kernel
+        configs = list(dict.fromkeys(self.cfg))
+        topks = sorted({k for _, k, _ in configs})
+        for b in self.batches:
+            self._workspace_slabs(b, topks)
+        cfg_mode = {}
+        for c_ in configs:
+            cfg_mode[c_] = int(lib().moc_train_runs_mode(C.byref(self._struct(self.batches[0].c, c_)), C.byref(self.batches[0].meta_ws()[1])))
+            assert cfg_mode[c_] != 0, "train_runs: this shape takes the three-launch step, whose scratch is one per batch -- train the runs one by one"
+        self.run_mode = [cfg_mode[c_] for c_ in self.cfg]
+        self.mode = max(self.run_mode)
+        cap = 8                                               # (measured, lockstep: chains of up to eight runs)
+        env_cap = False
         if "MOC_RUNS_GROUPS" in os.environ:
             G = max(1, min(R, int(os.environ["MOC_RUNS_GROUPS"])))
-            cap = min(MAX_CHAIN, (R + G - 1) // G)
-        # a chain's runs share the visits per pass and the step count, and lie a constant stride apart in the arenas and in
-        # the batches: chains are cut where the run indices stop being consecutive
+            cap, env_cap = min(MAX_CHAIN, (R + G - 1) // G), True
+        # a chain's runs share the visits per pass, the step count and the configuration (one moc_train_steps_runs call has
+        # one batch struct and one use_bits), and lie a constant stride apart in the arenas and in the batches: chains are cut
+        # where the run indices stop being consecutive
+        chains = []
+        for chain in group_runs([(n_, st_, c_) for n_, st_, c_ in zip(self.run_n, run_steps, self.cfg)], cap):
+            if self.run_mode[chain[0]] == 2 and not env_cap:  # (outside the tile-record step: every run a chain of its own)
+                chains += [[r] for r in chain]
+            else:
+                chains.append(chain)
         self.groups = []
-        for chain in group_runs([(n_, st_) for n_, st_ in zip(self.run_n, run_steps)], cap):
+        for chain in chains:
             pieces = [[chain[0]]]
             for r in chain[1:]:
                 if r == pieces[-1][-1] + 1:
@@ -188,19 +254,77 @@ class TrainRuns:
                 for name in ("W1", "b1", "W2", "b2", "m_W1", "m_b1", "m_W2", "m_b2", "v_W1", "v_b1", "v_W2", "v_b2"):
                     setattr(mc, name, getattr(self.meta.c, name) + 4 * r0 * self.par_stride)
                 mc.W1_image = ptr(self.images) + r0 * self.img_stride
-                self.groups.append({"r0": r0, "n": n_, "slide0": self.run_slide0[r0], "meta": mc,
+                self.groups.append({"r0": r0, "n": n_, "slide0": self.run_slide0[r0], "meta": mc, "cfg": self.cfg[r0],
+                                    "use": self.run_use[r0],
                                     "runs": MocRuns(n_runs=len(piece), slide_stride=n_, par_stride=self.par_stride,
                                                     image_stride=self.img_stride),
                                     "w2alt": ptr(self.W2_alt) + 4 * r0 * 4 * H,
                                     "stream": None if not self.groups else torch.cuda.Stream(device=device)})
 
-    # ---- the masks of one pass: every run draws its own, side by side (moc_host_draw_masks releases the GIL)
+    # ---- struct copies: a configuration's values, a slide range
+    @staticmethod
+    def _struct(c0, cfg):
+        """A copy of the batch struct `c0` carrying configuration `cfg` = (topj, topk, discard_bits): what a chain, or a
+        selection over that configuration's slides, hands the library."""
+        c = type(c0).from_buffer_copy(c0)
+        c.topj, c.topk, c.discard_bits = cfg
+        return c
+
+    @staticmethod
+    def _view(c, slide0, n):
+        """Slides [slide0, slide0 + n) of the batch struct `c` as a batch of their own: the per-slide arrays advanced by
+        slide0, n_slides = n.  The slot arrays are addressed absolutely through row_off (mask, kept, stats, sel_flag, sel_idx,
+        sel_row, cand: every kernel of phase A forms `array + row_off[b]`), so they stay; max_rows may stay the batch's."""
+        v = type(c).from_buffer_copy(c)
+        v.n_slides = n
+        v.row_off = c.row_off + 8 * slide0
+        v.row_off_host = c.row_off_host + 8 * slide0
+        if c.x_off:
+            v.x_off = c.x_off + 8 * slide0
+        if c.n_kept:
+            v.n_kept = c.n_kept + 4 * slide0
+        v.n_sel = c.n_sel + 4 * slide0
+        v.n_sel_host = None
+        return v
+
+    def _workspace_slabs(self, batch, topks):
+        """The step workspace of a grid.  moc_meta_ws_t.topk_idx is indexed [slide, C, topk] with the BATCH's topk as its
+        stride: chains of different K, which run side by side on their own streams, would write overlapping regions (slides
+        0-2 at K = 10 and slides 3-5 at K = 5), so every K gets a slab of its own, [n_slides, C, K].  Nothing else needs one:
+        topk_cnt / pooled / loss / pred are per slide without K; pair_dh / pair_row belong to the three-launch step, which
+        moc_train_runs_mode == 0 refuses; the tile records are laid out by (slide, C) alone (moc_tile_ws_bytes)."""
+        t, ws = batch.meta_ws()
+        batch._topk_slabs = {}
+        if topks == [batch.topk]:
+            return
+        Cc = batch.C
+        for K in topks:
+            batch._topk_slabs[K] = t["topk_idx"] if K == batch.topk else \
+                torch.empty((batch.n_slides, Cc, K), dtype=torch.int32, device=batch.device)
+        # the tile records exist when ANY configuration can take the tile-record step (meta_ws decided by the largest K)
+        if t["tile_ws"] is None and engine.TILE_RECORDS and Cc <= 16 and any(K <= 16 and Cc * K <= 64 for K in topks):
+            nb = lib().moc_tile_ws_bytes(batch.total, batch.n_slides, Cc)
+            t["tile_ws"] = torch.empty(nb, dtype=torch.uint8, device=batch.device)
+            ws.tile_ws, ws.tile_ws_bytes = ptr(t["tile_ws"]), nb
+
+    def topk_idx(self, r):
+        """[n_r, C, K_r] pooled positions of run r's slides in the last pass (its configuration's slab)."""
+        batch, K = self.last[0], self.cfg[r][1]
+        slab = batch._topk_slabs.get(K, batch.meta_ws()[0]["topk_idx"])
+        return slab[self.run_slide0[r]:self.run_slide0[r] + self.run_n[r]]
+
+    # ---- the masks of one pass: every mask group's leader draws, side by side (moc_host_draw_masks releases the GIL)
     def _draw(self, buf):
-        """-> (kept rows of all runs, the largest kept-row count of any slide)."""
+        """-> (kept rows of the leaders, the largest kept-row count of any slide, leader of every run)."""
         off_c = self.batches[0]._row_off_c
+        gens = self.generators
+        if self.share:
+            leader = mask_groups([(id(sp), g.get_state().numpy().tobytes()) for sp, g in zip(self.splits, gens)])
+        else:
+            leader = list(range(self.R))
 
         def one(r):
-            g = self.generators[r]
+            g = gens[r]
             st = g.get_state()
             first, rows = self.run_rows[r]
             kept = lib().moc_host_draw_masks(ptr(st), st.numel(), rows, buf.data_ptr() + first)
@@ -213,8 +337,12 @@ class TrainRuns:
             # the run's slides are slides run_slide0[r] ... of the batch: its largest kept-row count, from the same thread
             mk = lib().moc_host_max_kept(buf.data_ptr(), C.c_void_p(C.addressof(off_c) + 8 * self.run_slide0[r]), self.run_n[r])
             return int(kept), int(mk)
-        res = list(self.pool.map(one, range(self.R)))
-        return sum(k for k, _ in res), max(m for _, m in res)
+        leaders = [r for r in range(self.R) if leader[r] == r]
+        res = list(self.pool.map(one, leaders))
+        for r in range(self.R):                                # a follower's stream goes on where its leader's does
+            if leader[r] != r:
+                gens[r].set_state(gens[leader[r]].get_state())
+        return sum(k for k, _ in res), max(m for _, m in res), leader
 
     def _free_flags(self):
         for i, ev in enumerate(self.flag_busy):
@@ -229,7 +357,7 @@ class TrainRuns:
         """Masks + phase A of the next pass into work-array set `turn`, on the CURRENT stream (head_only: the flags and the
         kept-row lists only; `_phase_a_tail` does the rest)."""
         i = self._free_flags()
-        kept, max_kept = self._draw(self.flags[i])
+        kept, max_kept, leader = self._draw(self.flags[i])
         batch = self.batches[turn]
         if self.upload_flags:
             # one asynchronous copy of the flags (the compaction kernel reading 4 MB of them in place over PCIe takes as
@@ -238,30 +366,93 @@ class TrainRuns:
             batch.c.max_rows = max(1, max_kept)
         else:
             batch.use_host_mask(self.flags[i], kept, max_kept)
-        if head_only:
-            batch.phase_a_head(self.bank)
+        scored = sum(self.run_n[r] for r in range(self.R) if leader[r] == r)
+        # one configuration and nobody to share with: the batch's own four launches, as ever
+        plain = scored == batch.n_slides and len(set((j, d) for j, _, d in self.cfg)) == 1
+        self.pass_info[turn] = {"leader": leader, "plain": plain,
+                                "report": {"slides": batch.n_slides, "scored_slides": scored, "shared_slides": batch.n_slides - scored}}
+        self.last_phase_a = self.pass_info[turn]["report"]
+        if plain:
+            if head_only:
+                batch.phase_a_head(self.bank)
+            else:
+                batch.phase_a(self.bank)
         else:
-            batch.phase_a(self.bank)
+            # head: the leaders' kept-row lists (a launch per block of consecutive leader runs)
+            bank = self.bank
+            assert bank.D == batch.D and bank.C == batch.C and bank.Ce == batch.Ce and bank.dtype == batch.X.dtype
+            batch._layout(engine.COMPACT_STATS and batch.Ce > 16)
+            batch._n_sel_stale()
+            for s0, n_ in self._slide_blocks([r for r in range(self.R) if leader[r] == r]):
+                check(lib().moc_mask_compact(C.byref(self._view(batch.c, s0, n_)), engine._stream()), "moc_mask_compact")
+            if not head_only:
+                self._phase_a_tail(turn)
         ev = torch.cuda.Event()
         ev.record(engine.stream_obj())
         self.flag_busy[i] = ev
         return ev
+
+    def _slide_blocks(self, runs):
+        """(first slide, slides) of every block of consecutive runs among `runs` (their slides are consecutive too)."""
+        return [(self.run_slide0[r0], sum(self.run_n[r0:r0 + k])) for r0, k in consecutive_blocks(runs)]
+
+    def _phase_a_tail(self, turn):
+        """The rest of phase A of set `turn`: the leaders' score pass, the share, the selection per configuration."""
+        batch, info = self.batches[turn], self.pass_info[turn]
+        self.trained_phase_a = info["report"]
+        if info["plain"]:
+            batch.phase_a_tail(self.bank)
+            return
+        leader, st = info["leader"], engine._stream()
+        for s0, n_ in self._slide_blocks([r for r in range(self.R) if leader[r] == r]):
+            v = self._view(batch.c, s0, n_)
+            if batch.stats_cache is not None:
+                cache, compact = batch.stats_cache
+                assert compact == bool(batch.c.flags & engine._lib.MOC_STATS_COMPACT) and cache.size(1) == self.X.size(0)
+                check(lib().moc_scores_from_cache(C.byref(v), ptr(cache), cache.size(1), st), "moc_scores_from_cache")
+            else:
+                check(lib().moc_scores(C.byref(v), ptr(self.bank.image), st), "moc_scores")
+        if any(leader[r] != r for r in range(self.R)):
+            # the followers' slots: kept rows, statistics and cleared union flags from their leaders' (moc_stats_share)
+            key = tuple(leader)
+            lead = self._lead_dev.get(key)
+            if lead is None:
+                if len(self._lead_dev) > 8:
+                    self._lead_dev.clear()
+                of_slide = []
+                for r in range(self.R):
+                    d = self.run_slide0[leader[r]] - self.run_slide0[r]
+                    of_slide += [-1 if d == 0 else s_ + d for s_ in range(self.run_slide0[r], self.run_slide0[r] + self.run_n[r])]
+                lead = self._lead_dev[key] = torch.tensor(of_slide, dtype=torch.int32).to(self.device)
+                lead.record_stream(self.side)
+            check(lib().moc_stats_share(C.byref(batch.c), ptr(lead), 0, batch.n_slides, st), "moc_stats_share")
+        batch._n_sel_stale()
+        by_sel = {}
+        for r, (j, _, d) in enumerate(self.cfg):               # moc_select / moc_gather_candidates read topj and discard_bits only
+            by_sel.setdefault((j, d), []).append(r)
+        for (j, d), rs in by_sel.items():
+            c = self._struct(batch.c, (j, batch.topk, d))
+            for s0, n_ in self._slide_blocks(rs):
+                v = self._view(c, s0, n_)
+                check(lib().moc_select(C.byref(v), st), "moc_select")
+                check(lib().moc_gather_candidates(C.byref(v), None, st), "moc_gather_candidates")
+        batch._n_sel_request()
 
     def train_pass(self):
         """One pass (epoch) of every run: main_moc.train for each of them, in lockstep."""
         for m in self.models:
             if not m.training:
                 m.train()
-        use = engine.train_use_bits(self.args.discard_classifiers)
         ahead, self.ahead = self.ahead, None
         if ahead is not None:
             ahead["done"].wait(engine.stream_obj())
             self.turn = ahead["turn"]
             if ahead.get("head_only"):                        # its kept-row lists exist: score pass, selection, candidates now
-                self.batches[self.turn].phase_a_tail(self.bank)
+                self._phase_a_tail(self.turn)
         else:
             self.turn = 1 - self.turn
             self._phase_a(self.turn)
+        self.trained_phase_a = self.pass_info[self.turn]["report"]
         batch = self.batches[self.turn]
         t, ws0 = batch.meta_ws()
         batch.publish_n_sel()
@@ -281,12 +472,19 @@ class TrainRuns:
         def group_call(grp, raw_stream):
             ws = type(ws0).from_buffer_copy(ws0)
             ws.W2_alt = grp["w2alt"]
+            bc = batch.c
+            if len(batch._topk_slabs) or grp["cfg"] != (batch.c.topj, batch.c.topk, batch.c.discard_bits):
+                # a grid: the chain's own topj / topk / discard_bits, and its K's slab of pooled positions
+                bc = self._struct(batch.c, grp["cfg"])
+                slab = batch._topk_slabs.get(grp["cfg"][1])
+                if slab is not None:
+                    ws.topk_idx = ptr(slab)
             mc = grp["meta"]
             mc.lr, mc.beta1, mc.beta2, mc.eps, mc.weight_decay = (self.meta.c.lr, self.meta.c.beta1, self.meta.c.beta2,
                                                                   self.meta.c.eps, self.meta.c.weight_decay)
             mc.step = grp["step"]
-            return lib().moc_train_steps_runs(C.byref(batch.c), C.byref(mc), C.byref(grp["runs"]), C.byref(ws), ptr(self.labels),
-                                              grp["slide0"], grp["n"], use, raw_stream)
+            return lib().moc_train_steps_runs(C.byref(bc), C.byref(mc), C.byref(grp["runs"]), C.byref(ws), ptr(self.labels),
+                                              grp["slide0"], grp["n"], grp["use"], raw_stream)
         main_raw = engine._stream()
         raw_of = lambda grp: main_raw if grp["stream"] is None else C.c_void_p(grp["stream"].cuda_stream)
         for grp in self.groups:
