@@ -339,6 +339,23 @@ int moc_train_steps_runs(const moc_batch_t* B, const moc_meta_t* M, const moc_ru
                          const int64_t* labels, int slide0, int n, uint32_t use_bits, moc_stream_t stream);
 int moc_train_runs_mode(const moc_batch_t* B, const moc_meta_ws_t* ws);
 
+/* Batched runs with Adam hyper-parameters PER RUN (ABI 20, additive): moc_train_steps_runs, except that run r is updated
+ * with hp[r] instead of M's lr / betas / eps / weight_decay -- a seeds x lr x weight-decay grid whose cells share a split
+ * and a mask stream and differ in the last instructions of the step.  hp: HOST array of R->n_runs records, read before
+ * the call returns; the values are the optimizers' unrounded Python floats, as in moc_meta_t.  The step count is still
+ * M->step for every run.  In lockstep shapes (moc_train_runs_mode == 1) the coefficients of run r at every step are formed
+ * on the host with the arithmetic of moc_train_steps (doubles, rounded to fp32 once) and travel in the step launch's
+ * argument block, up to eight runs per step launch (more runs: two step launches behind the one forward launch); in
+ * mode 2 every run's pass takes its record in place of M's values.  Per run bit-identical to moc_train_steps with a
+ * moc_meta_t that holds hp[r].  Errors (not faults), before anything is launched: everything moc_train_steps_runs
+ * refuses, a null hp, a non-finite or negative lr / eps / weight_decay, a beta outside [0, 1). */
+typedef struct moc_adam_hp {
+    double lr, beta1, beta2, eps, weight_decay;
+} moc_adam_hp_t;
+int moc_train_steps_runs_hp(const moc_batch_t* B, const moc_meta_t* M, const moc_runs_t* R, const moc_meta_ws_t* ws,
+                            const int64_t* labels, int slide0, int n, uint32_t use_bits, const moc_adam_hp_t* hp,
+                            moc_stream_t stream);
+
 /* Prediction with several meta-learners (an ensemble of checkpoints; ABI 20, additive): the evaluation forward of
  * moc_meta_forward for R->n_runs models (1 .. 16) over the union rows of slides [slide0, slide0 + n) of an UNMASKED batch
  * whose phase A has run, in one launch: the row ids and candidate scores are read once per tile for all models.  Model r's

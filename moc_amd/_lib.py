@@ -60,6 +60,11 @@ class MocRuns(C.Structure):
     _fields_ = [("n_runs", C.c_int32), ("slide_stride", C.c_int32), ("par_stride", C.c_int64), ("image_stride", C.c_int64)]
 
 
+class MocAdamHp(C.Structure):
+    """moc_adam_hp_t: one run's Adam hyper-parameters (moc_train_steps_runs_hp), the optimizer's unrounded Python floats."""
+    _fields_ = [(n, C.c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay")]
+
+
 # name -> (restype, argtypes); every symbol include/moc_hip.h declares
 _BP, _MP, _WP = C.POINTER(MocBatch), C.POINTER(MocMeta), C.POINTER(MocMetaWs)
 SIGNATURES = {
@@ -97,6 +102,8 @@ SIGNATURES = {
     "moc_train_steps": (C.c_int, [_BP, _MP, _WP, _p, C.c_int, C.c_int, C.c_uint32, _p]),
     "moc_train_steps_runs": (C.c_int, [_BP, _MP, C.POINTER(MocRuns), _WP, _p, C.c_int, C.c_int, C.c_uint32, _p]),
     "moc_train_runs_mode": (C.c_int, [_BP, _WP]),
+    "moc_train_steps_runs_hp": (C.c_int, [_BP, _MP, C.POINTER(MocRuns), _WP, _p, C.c_int, C.c_int, C.c_uint32,
+                                          C.POINTER(MocAdamHp), _p]),
     "moc_step_graph_workspace_bytes": (C.c_size_t, [C.c_int]),
     "moc_step_graph_create": (C.c_int, [_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "moc_step_graph_destroy": (C.c_int, [_p]),

@@ -934,13 +934,30 @@ struct TileStepArgsRuns {
     int32_t cap_r[MOC_MAX_RUNS], ntb_r[MOC_MAX_RUNS];
 };
 static_assert(sizeof(TileStepArgsRuns) <= 1024, "a kernel-argument segment over 1 KiB takes a slow launch path (profiles/NOTES.md)");
+// Batched runs with Adam coefficients PER RUN (moc_train_steps_runs_hp): run r's AdamCoef of this step travels by value
+// behind the per-run scalars and the workgroup's run index -- wave-uniform -- selects its entry with one scalar load from
+// the argument block: no device table, no upload, nothing to synchronise per step.  Sixteen entries of 32 bytes behind the
+// 864 bytes above would pass the 1-KiB bound of the fast launch path, so a launch of this form serves at most
+// MOC_HP_RUNS = 8 runs (the chain length moc_amd.runs uses: 480 + 8 x 24 + 8 x 32 = 928 bytes); the entry issues the step
+// of more runs as two launches.  The launches of moc_train_steps_runs keep the block above, and their kernel.
+constexpr int MOC_HP_RUNS = 8;
+struct TileStepArgsRunsHp {
+    TileStepArgs s;
+    int64_t base_r[MOC_HP_RUNS], slot0_r[MOC_HP_RUNS];
+    int32_t cap_r[MOC_HP_RUNS], ntb_r[MOC_HP_RUNS];
+    AdamCoef adam_r[MOC_HP_RUNS];
+};
+static_assert(sizeof(TileStepArgsRunsHp) <= 1024, "a kernel-argument segment over 1 KiB takes a slow launch path (profiles/NOTES.md)");
+static_assert(offsetof(TileStepArgsRunsHp, adam_r) % sizeof(AdamCoef) == 0, "a run's coefficients: one aligned 32-byte scalar load");
 __host__ __device__ __forceinline__ const TileStepArgs& tile_common(const TileStepArgs& x) { return x; }
 __host__ __device__ __forceinline__ const TileStepArgs& tile_common(const TileStepArgsRuns& x) { return x.s; }
+__host__ __device__ __forceinline__ const TileStepArgs& tile_common(const TileStepArgsRunsHp& x) { return x.s; }
 
 template <int VQ, typename ArgsT>
 __global__ __launch_bounds__(256, 4) void pool_w1_step_tiles_kernel(ArgsT args) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr bool RUNS = std::is_same<ArgsT, TileStepArgsRuns>::value;
+    constexpr bool RUNS = !std::is_same<ArgsT, TileStepArgs>::value;
+    constexpr bool RUN_HP = std::is_same<ArgsT, TileStepArgsRunsHp>::value;      // Adam coefficients per run
     const TileStepArgs& a = tile_common(args);
     static_assert(offsetof(TileStepArgs, n_sel) + 8 <= 64, "the first loads' arguments must share the first cache line");
     // batched runs: this workgroup's run -- its slide, its region of the records, the offsets of its tensors (the argument
@@ -952,9 +969,9 @@ __global__ __launch_bounds__(256, 4) void pool_w1_step_tiles_kernel(ArgsT args) 
     if constexpr (RUNS) {
         const int run = blockIdx.z;
         b += run * a.slide_stride;
-        slot0 = kernarg_at<int64_t>(offsetof(TileStepArgsRuns, slot0_r) + 8 * (size_t)run);
-        cap = kernarg_at<int32_t>(offsetof(TileStepArgsRuns, cap_r) + 4 * (size_t)run);
-        ntile_bound = kernarg_at<int32_t>(offsetof(TileStepArgsRuns, ntb_r) + 4 * (size_t)run);
+        slot0 = kernarg_at<int64_t>(offsetof(ArgsT, slot0_r) + 8 * (size_t)run);
+        cap = kernarg_at<int32_t>(offsetof(ArgsT, cap_r) + 4 * (size_t)run);
+        ntile_bound = kernarg_at<int32_t>(offsetof(ArgsT, ntb_r) + 4 * (size_t)run);
     }
     const int C = a.C, K = a.K, D = a.D;
     const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -995,7 +1012,7 @@ __global__ __launch_bounds__(256, 4) void pool_w1_step_tiles_kernel(ArgsT args) 
     base = a.base;
     if constexpr (RUNS) {
         const int run = blockIdx.z;
-        base = kernarg_at<int64_t>(offsetof(TileStepArgsRuns, base_r) + 8 * (size_t)run);
+        base = kernarg_at<int64_t>(offsetof(ArgsT, base_r) + 8 * (size_t)run);
         po = (int64_t)run * a.par_stride; w2o = (int64_t)run * a.w2_stride; w2outo = (int64_t)run * a.w2out_stride;
         imgo = (int64_t)run * a.img_stride;
     }
@@ -1055,6 +1072,8 @@ __global__ __launch_bounds__(256, 4) void pool_w1_step_tiles_kernel(ArgsT args) 
     }
     AdamCoef ak = a.adam;
     if (a.adam_tab) ak = a.adam_tab[a.adam_ctr[0] + a.adam_pos];
+    // (every place below that applies Adam -- the W1 tile, b1, W2 / b2, on column block 0 or on a tail workgroup -- takes `ak`)
+    if constexpr (RUN_HP) ak = kernarg_at<AdamCoef>(offsetof(ArgsT, adam_r) + sizeof(AdamCoef) * (size_t)blockIdx.z);
     const int S = (!RUNS && a.S_host >= 0) ? a.S_host : a.n_sel[b];
     const int y = (int)a.labels[b];
     const int k = K < S ? K : S;
@@ -2148,7 +2167,8 @@ void fused_step_attrs() {
     (void)hipFuncSetAttribute((const void*)pool_w1_step_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, FS_MAX_DYN_LDS);
 #define MOC_TILES_ATTR(VQ)                                                                                                         \
     (void)hipFuncSetAttribute((const void*)pool_w1_step_tiles_kernel<VQ, TileStepArgs>, hipFuncAttributeMaxDynamicSharedMemorySize, FS_MAX_DYN_LDS); \
-    (void)hipFuncSetAttribute((const void*)pool_w1_step_tiles_kernel<VQ, TileStepArgsRuns>, hipFuncAttributeMaxDynamicSharedMemorySize, FS_MAX_DYN_LDS)
+    (void)hipFuncSetAttribute((const void*)pool_w1_step_tiles_kernel<VQ, TileStepArgsRuns>, hipFuncAttributeMaxDynamicSharedMemorySize, FS_MAX_DYN_LDS); \
+    (void)hipFuncSetAttribute((const void*)pool_w1_step_tiles_kernel<VQ, TileStepArgsRunsHp>, hipFuncAttributeMaxDynamicSharedMemorySize, FS_MAX_DYN_LDS)
     MOC_TILES_ATTR(4); MOC_TILES_ATTR(8); MOC_TILES_ATTR(12); MOC_TILES_ATTR(16);
 #undef MOC_TILES_ATTR
     done = true;
@@ -2215,7 +2235,8 @@ int launch_tile_step_as(const moc_batch_t* B, const ArgsT& args, int runs, int t
 int launch_tile_step(const moc_batch_t* B, const TileStepArgs& ta, hipStream_t s) {
     return launch_tile_step_as(B, ta, 1, ta.ntile_bound, s);
 }
-int launch_tile_step_runs(const moc_batch_t* B, const TileStepArgsRuns& tr, hipStream_t s) {
+template <typename RunsT>
+int launch_tile_step_runs(const moc_batch_t* B, const RunsT& tr, hipStream_t s) {
     int tb = tr.s.ntile_bound;
     for (int r = 0; r < tr.s.n_runs; ++r) tb = tr.ntb_r[r] > tb ? tr.ntb_r[r] : tb;
     return launch_tile_step_as(B, tr, tr.s.n_runs, tb, s);
@@ -2503,16 +2524,24 @@ extern "C" int moc_train_runs_mode(const moc_batch_t* B, const moc_meta_ws_t* ws
     return fused_step_mode(B, ws) != 0 ? 2 : 0;
 }
 
-extern "C" int moc_train_steps_runs(const moc_batch_t* B, const moc_meta_t* M, const moc_runs_t* R, const moc_meta_ws_t* ws,
-                                    const int64_t* labels, int slide0, int n, uint32_t use_bits, moc_stream_t stream) {
-    if (int rc = moc_check_batch(B, "moc_train_steps_runs")) return rc;
-    if (int rc = check_meta(B, M, ws, "moc_train_steps_runs", true, false)) return rc;
-    MOC_REQUIRE(R && R->n_runs >= 1 && R->n_runs <= MOC_MAX_RUNS, "moc_train_steps_runs: 1 .. %d runs", MOC_MAX_RUNS);
+// `hp` == nullptr: the runs share M's hyper-parameters (moc_train_steps_runs: one AdamCoef per launch, the argument block
+// and the kernel it has always had); else run r steps with hp[r] (moc_train_steps_runs_hp)
+static int train_steps_runs(const moc_batch_t* B, const moc_meta_t* M, const moc_runs_t* R, const moc_meta_ws_t* ws,
+                            const int64_t* labels, int slide0, int n, uint32_t use_bits, const moc_adam_hp_t* hp,
+                            moc_stream_t stream, const char* who) {
+    if (int rc = moc_check_batch(B, who)) return rc;
+    if (int rc = check_meta(B, M, ws, who, true, false)) return rc;
+    MOC_REQUIRE(R && R->n_runs >= 1 && R->n_runs <= MOC_MAX_RUNS, "%s: 1 .. %d runs", who, MOC_MAX_RUNS);
     MOC_REQUIRE(labels && slide0 >= 0 && n >= 1 && R->slide_stride >= n &&
-                slide0 + n + (R->n_runs - 1) * R->slide_stride <= B->n_slides, "moc_train_steps_runs: bad labels/slide range");
+                slide0 + n + (R->n_runs - 1) * R->slide_stride <= B->n_slides, "%s: bad labels/slide range", who);
     MOC_REQUIRE(R->par_stride >= (int64_t)H * B->D + H + 4 * H + 4 && R->image_stride >= (int64_t)moc_w1_image_bytes(B->D, B->dtype),
-                "moc_train_steps_runs: parameter / image stride smaller than one meta-learner");
+                "%s: parameter / image stride smaller than one meta-learner", who);
     hipStream_t s = (hipStream_t)stream;
+    // run r's hyper-parameters as a moc_meta_t that adam_coef reads: M's, or record r
+    auto with_hp = [&](moc_meta_t& Mr, int r) {
+        if (!hp) return;
+        Mr.lr = hp[r].lr; Mr.beta1 = hp[r].beta1; Mr.beta2 = hp[r].beta2; Mr.eps = hp[r].eps; Mr.weight_decay = hp[r].weight_decay;
+    };
     if (!tiles_ok(B, ws)) {
         // Shapes outside the tile-record step (wide banks: EBRAINS-30, the 64-way shape; C > 16, C K > 64, more than 4,096
         // selectable rows): every run's pass through moc_train_steps' own launches, one run after the other on this stream --
@@ -2520,9 +2549,10 @@ extern "C" int moc_train_steps_runs(const moc_batch_t* B, const moc_meta_t* M, c
         // over all runs' slides in one pass and (moc_amd.runs: one group per run) the runs' chains side by side on streams
         // of their own, each of which keeps a few dozen CUs busy.  The one-launch steps only (W2_alt set): the three-launch
         // step's scratch is one per batch.
-        MOC_REQUIRE(fused_step_mode(B, ws) != 0, "moc_train_steps_runs: this shape needs ws->W2_alt (the one-launch steps)");
+        MOC_REQUIRE(fused_step_mode(B, ws) != 0, "%s: this shape needs ws->W2_alt (the one-launch steps)", who);
         for (int r = 0; r < R->n_runs; ++r) {
             moc_meta_t Mr = *M;
+            with_hp(Mr, r);
             const int64_t po = (int64_t)r * R->par_stride;
             Mr.W1 += po; Mr.b1 += po; Mr.W2 += po; Mr.b2 += po;
             Mr.m_W1 += po; Mr.m_b1 += po; Mr.m_W2 += po; Mr.m_b2 += po;
@@ -2541,41 +2571,99 @@ extern "C" int moc_train_steps_runs(const moc_batch_t* B, const moc_meta_t* M, c
     float* cur = M->W2;
     float* nxt = ws->W2_alt;
     int64_t cur_stride = R->par_stride, nxt_stride = 4 * H;
-    for (int t = 0; t < n; ++t) {
-        const int b = slide0 + t;
-        const AdamCoef k = adam_coef(M, M->step + 1 + t, 1.f);
-        Mt.W2 = cur;
-        if (int rc = launch_forward(B, &Mt, ws, b, 1, use_bits, s, true, R, cur_stride)) return rc;
-        TileStepArgsRuns tr;
-        tr.s = tile_step_args(B, &Mt, ws, labels, b, use_bits, k, nxt, 1, nullptr);
-        TileStepArgs& ta = tr.s;
-        ta.n_runs = R->n_runs; ta.slide_stride = R->slide_stride;
-        // four runs or more: throughput, not one run's latency, is what a launch is about -- no tail workgroups
-        static const int tail_env = getenv("MOC_RUNS_TAIL_INSIDE") ? atoi(getenv("MOC_RUNS_TAIL_INSIDE")) : -1;   // diagnostic override
+    // four runs or more: throughput, not one run's latency, is what a launch is about -- no tail workgroups
+    static const int tail_env = getenv("MOC_RUNS_TAIL_INSIDE") ? atoi(getenv("MOC_RUNS_TAIL_INSIDE")) : -1;   // diagnostic override
+    static const bool prefetch = !(getenv("MOC_STEP_PREFETCH") && atoi(getenv("MOC_STEP_PREFETCH")) == 0);   // diagnostic: off
+    // the common block of the step launch of runs [r0, r0 + nr) at step t: M's tensors and both W2 buffers advanced to run r0
+    auto common = [&](int t, int r0, int nr, const AdamCoef& k) {
+        const int64_t po = (int64_t)r0 * R->par_stride;
+        moc_meta_t Mr = Mt;
+        Mr.W1 += po; Mr.b1 += po; Mr.b2 += po;
+        Mr.m_W1 += po; Mr.m_b1 += po; Mr.m_W2 += po; Mr.m_b2 += po;
+        Mr.v_W1 += po; Mr.v_b1 += po; Mr.v_W2 += po; Mr.v_b2 += po;
+        Mr.W2 = cur + (int64_t)r0 * cur_stride;
+        Mr.W1_image = (unsigned char*)M->W1_image + (int64_t)r0 * R->image_stride;
+        TileStepArgs ta = tile_step_args(B, &Mr, ws, labels, slide0 + t + r0 * R->slide_stride, use_bits, k,
+                                         nxt + (int64_t)r0 * nxt_stride, 1, nullptr);
+        ta.n_runs = nr; ta.slide_stride = R->slide_stride;
         ta.tail_inside = tail_env >= 0 ? tail_env : (R->n_runs >= 4 ? 1 : 0);
         ta.par_stride = R->par_stride; ta.img_stride = R->image_stride; ta.w2_stride = cur_stride; ta.w2out_stride = nxt_stride;
-        static const bool prefetch = !(getenv("MOC_STEP_PREFETCH") && atoi(getenv("MOC_STEP_PREFETCH")) == 0);   // diagnostic: off
         // (launches of four runs or more are bound by workgroup slots, not by one run's latency: the prefetch cost eight
         // batched runs 3.6 %)
         if (prefetch && t + 1 < n && B->C < 4 && R->n_runs < 4) ta.prefetch_next = 1;
-        for (int r = 0; r < R->n_runs; ++r) {
-            const int sl = b + r * R->slide_stride;
+        return ta;
+    };
+    // the per-run scalars of runs [r0, r0 + nr) behind it (the arrays' unused entries: zero)
+    auto per_run = [&](auto& tr, int t, int r0, int nr, int cap_runs) {
+        for (int r = 0; r < cap_runs; ++r) {
+            tr.base_r[r] = 0; tr.slot0_r[r] = 0; tr.cap_r[r] = 0; tr.ntb_r[r] = 0;
+            if (r >= nr) continue;
+            const int sl = slide0 + t + (r0 + r) * R->slide_stride;
             tr.base_r[r] = B->row_off_host[sl];
             int cap_, tb_;
             tile_region(B, sl, &tr.slot0_r[r], &cap_, &tb_);
             tr.cap_r[r] = cap_; tr.ntb_r[r] = tb_;
         }
-        for (int r = R->n_runs; r < MOC_MAX_RUNS; ++r) { tr.base_r[r] = 0; tr.slot0_r[r] = 0; tr.cap_r[r] = 0; tr.ntb_r[r] = 0; }
-        if (int rc = launch_tile_step_runs(B, tr, s)) return rc;
+    };
+    // more runs than one launch with per-run coefficients carries: even pieces (nine runs: 5 + 4)
+    const int hp_pieces = moc_cdiv(R->n_runs, MOC_HP_RUNS), hp_per = moc_cdiv(R->n_runs, hp_pieces);
+    for (int t = 0; t < n; ++t) {
+        const int b = slide0 + t;
+        Mt.W2 = cur;
+        if (int rc = launch_forward(B, &Mt, ws, b, 1, use_bits, s, true, R, cur_stride)) return rc;
+        if (!hp) {
+            TileStepArgsRuns tr;
+            tr.s = common(t, 0, R->n_runs, adam_coef(M, M->step + 1 + t, 1.f));
+            per_run(tr, t, 0, R->n_runs, MOC_MAX_RUNS);
+            if (int rc = launch_tile_step_runs(B, tr, s)) return rc;
+        } else {
+            for (int r0 = 0; r0 < R->n_runs; r0 += hp_per) {
+                const int nr = R->n_runs - r0 < hp_per ? R->n_runs - r0 : hp_per;
+                TileStepArgsRunsHp tr;
+                for (int r = 0; r < MOC_HP_RUNS; ++r) {
+                    // (the arithmetic of adam_coef on record r0 + r: the floats the run alone gets)
+                    moc_meta_t Mr = *M;
+                    with_hp(Mr, r0 + (r < nr ? r : 0));
+                    tr.adam_r[r] = adam_coef(&Mr, M->step + 1 + t, 1.f);
+                }
+                tr.s = common(t, r0, nr, tr.adam_r[0]);
+                per_run(tr, t, r0, nr, MOC_HP_RUNS);
+                if (int rc = launch_tile_step_runs(B, tr, s)) return rc;
+            }
+        }
         float* tmp = cur; cur = nxt; nxt = tmp;
         const int64_t ts = cur_stride; cur_stride = nxt_stride; nxt_stride = ts;
     }
     if (cur != M->W2) {   // odd number of steps: every run's current W2 lives in the scratch buffer
         if (hipMemcpy2DAsync(M->W2, sizeof(float) * (size_t)R->par_stride, cur, sizeof(float) * 4 * H, sizeof(float) * 4 * H,
                              (size_t)R->n_runs, hipMemcpyDeviceToDevice, s) != hipSuccess)
-            MOC_FAIL(MOC_ELAUNCH, "moc_train_steps_runs: copy-back of W2 failed");
+            MOC_FAIL(MOC_ELAUNCH, "%s: copy-back of W2 failed", who);
     }
     return MOC_OK;
+}
+
+extern "C" int moc_train_steps_runs(const moc_batch_t* B, const moc_meta_t* M, const moc_runs_t* R, const moc_meta_ws_t* ws,
+                                    const int64_t* labels, int slide0, int n, uint32_t use_bits, moc_stream_t stream) {
+    return train_steps_runs(B, M, R, ws, labels, slide0, n, use_bits, nullptr, stream, "moc_train_steps_runs");
+}
+
+extern "C" int moc_train_steps_runs_hp(const moc_batch_t* B, const moc_meta_t* M, const moc_runs_t* R, const moc_meta_ws_t* ws,
+                                       const int64_t* labels, int slide0, int n, uint32_t use_bits, const moc_adam_hp_t* hp,
+                                       moc_stream_t stream) {
+    const char* who = "moc_train_steps_runs_hp";
+    MOC_REQUIRE(hp, "%s: null hyper-parameter records", who);
+    MOC_REQUIRE(R && R->n_runs >= 1 && R->n_runs <= MOC_MAX_RUNS, "%s: 1 .. %d runs", who, MOC_MAX_RUNS);
+    for (int r = 0; r < R->n_runs; ++r) {
+        const moc_adam_hp_t& h = hp[r];
+        // (written so that a NaN fails: every comparison with one is false)
+        MOC_REQUIRE(h.lr >= 0.0 && h.lr <= 1.7976931348623157e308, "%s: run %d: lr = %g (finite, >= 0)", who, r, h.lr);
+        MOC_REQUIRE(h.eps >= 0.0 && h.eps <= 1.7976931348623157e308, "%s: run %d: eps = %g (finite, >= 0)", who, r, h.eps);
+        MOC_REQUIRE(h.weight_decay >= 0.0 && h.weight_decay <= 1.7976931348623157e308,
+                    "%s: run %d: weight_decay = %g (finite, >= 0)", who, r, h.weight_decay);
+        MOC_REQUIRE(h.beta1 >= 0.0 && h.beta1 < 1.0, "%s: run %d: beta1 = %g (0 <= beta < 1)", who, r, h.beta1);
+        MOC_REQUIRE(h.beta2 >= 0.0 && h.beta2 < 1.0, "%s: run %d: beta2 = %g (0 <= beta < 1)", who, r, h.beta2);
+    }
+    return train_steps_runs(B, M, R, ws, labels, slide0, n, use_bits, hp, stream, who);
 }
 
 // ------------------------------------------------------------------ a pass of meta-steps as ONE graph launch

@@ -546,7 +546,7 @@ def train(model, train_loader, optimizer, device, args):
 _run_sets = {}
 
 
-def train_runs(models, train_loaders, optimizers, device, args, generators=None):
+def train_runs(models, train_loaders, optimizers, device, args, generators=None, per_run_adam=False):
     """main_moc.py:378-410 for several independent runs at once -- what scripts/moc_train.sh:11-31 starts as one process per
     (fold, shot): `train(models[r], train_loaders[r], optimizers[r], device, args)` for every r, stepped in lockstep by one
     launch pair per meta-step (moc_amd.runs.TrainRuns; include/moc_hip.h moc_train_steps_runs).  Per run bit-identical to
@@ -555,16 +555,19 @@ def train_runs(models, train_loaders, optimizers, device, args, generators=None)
     passes may differ in length (runs.group_runs: one lockstep chain per length).  `args` may be a list of one namespace per
     run: run r then trains with args[r].topj / .topk / .discard_classifiers (a hyper-parameter grid; runs that name the same
     split object and hold equal generator states share one draw and one score pass per pass -- DESIGN.md section 9h).
+    `per_run_adam`: every run steps with its own optimizer's lr / betas / eps / weight_decay (re-read every pass) instead
+    of the runs having to share them -- the cells of an lr x weight-decay grid in one lockstep chain.
     -> the TrainRuns object (kept for the next pass: call again with the same lists)."""
     from .runs import TrainRuns
     hp = lambda a: (a.topj, a.topk, tuple(sorted(a.discard_classifiers or ())))
     key = (tuple(id(m) for m in models), tuple(id(o) for o in optimizers), tuple(id(l) for l in train_loaders),
-           tuple(hp(a) for a in args) if isinstance(args, (list, tuple)) else hp(args), tuple(len(l) for l in train_loaders))
+           tuple(hp(a) for a in args) if isinstance(args, (list, tuple)) else hp(args), tuple(len(l) for l in train_loaders),
+           bool(per_run_adam))
     ent = _run_sets.get(key)
     if ent is None:
         if len(_run_sets) > 2:
             _run_sets.clear()
-        ent = _run_sets[key] = (TrainRuns(models, optimizers, train_loaders, device, args, generators=generators),
+        ent = _run_sets[key] = (TrainRuns(models, optimizers, train_loaders, device, args, generators=generators, per_run_adam=per_run_adam),
                                 list(models), list(optimizers), list(train_loaders))
     rs = ent[0]
     rs.train_pass()

@@ -9,6 +9,7 @@ around the GPU callables of moc_amd.main_moc.
     python -m moc_amd.run_moc --folds 0,1,2,3,4 --shot 16 --seed 1 ...      # five folds in ONE process, stepped in lockstep
     python -m moc_amd.run_moc --shots 1,2,4,8,16 --folds 0,1,2,3,4 --seed 1 ...   # the launcher's whole grid in one process
     python -m moc_amd.run_moc --topjs 100,400 --topks 5,10 --discard_sets none topk+bottomk --folds 0,1,2,3,4 --seed 1 ...   # a hyper-parameter grid
+    python -m moc_amd.run_moc --seeds 1,2,3 --lrs 3e-4,1e-3,3e-3 --wds 0,1e-4 --folds 0,1,2,3,4 --shot 16 ...   # an optimizer grid
 
 Same flags and defaults as the reference, same result files (`zs_results_*`, `best_results_*`,
 `ablation_results_*`, `best_model_*.pt`, `summary_*.csv`) with the same keys.  Differences, all
@@ -100,6 +101,17 @@ def get_args(argv=None):
     p.add_argument("--topks", type=str, default=None, help="comma-separated topk values (see --topjs)")
     p.add_argument("--discard_sets", nargs="*", default=None,
                    help="discard sets, classifier names joined with + (topk+bottomk), `none` for the empty set (see --topjs)")
+    p.add_argument("--lr", type=float, default=1e-3, help="Adam's learning rate (main_moc.py:316 hard-codes 1e-3)")
+    p.add_argument("--weight_decay", type=float, default=1e-4, help="Adam's coupled weight decay (main_moc.py:316 hard-codes 1e-4)")
+    p.add_argument("--seeds", type=str, default=None,
+                   help="comma-separated seeds: train every cell of --seeds x --lrs x --wds (a list that is not given: the one "
+                        "--seed / --lr / --weight_decay) for every fold of --folds (or the one --fold) in this process.  Cell "
+                        "(S, LR, WD) of fold F writes into {result_dir}/seed{S}_lr{LR}_wd{WD}/ what `--fold F --seed S --lr LR "
+                        "--weight_decay WD --result_dir {that dir}` writes alone, and {result_dir}/opt_grid_summary.csv holds one "
+                        "line per (lr, wd).  The cells of a (seed, fold) start from one meta-learner and one mask stream: they "
+                        "share a score pass per epoch and step in one lockstep chain, each with its own Adam (moc_amd.runs)")
+    p.add_argument("--lrs", type=str, default=None, help="comma-separated learning rates (see --seeds)")
+    p.add_argument("--wds", type=str, default=None, help="comma-separated weight decays (see --seeds)")
     p.add_argument("--patch_maps", type=str, default=None, choices=list(PATCH_MAP_CHOICES),
                    help="after main(), write per-patch maps (moc_amd.patch_maps) of these splits with the best checkpoint to "
                         "{result_dir}/patch_maps_shot_S_fold_F/{split}/ (default: none; test with --patch_maps_from)")
@@ -462,13 +474,14 @@ def patch_maps_from(args, model, loaders, device):
     return res
 
 
-def main_runs(args_list, models, optimizers, loaders_list, device, generators=None):
+def main_runs(args_list, models, optimizers, loaders_list, device, generators=None, per_run_adam=False):
     """main() (main_moc.py:586-644) for several runs at once: the zero-shot evaluations run per run, the training passes of
     all runs in lockstep (moc_amd.main_moc.train_runs), and every epoch's evaluations in one pass for all runs' train and
     validation splits, then one more for the test splits of the runs whose validation AUC improved (the reference visits
     the test set only then) -- moc_amd.main_moc.evaluation_runs.  `args_list[r]` carries run r's fold / shot / result_dir;
     loaders_list[r] = (train, val, test) resident splits.  Every run prints, saves and returns what main() would for it
-    alone.  -> list of result dicts."""
+    alone.  `per_run_adam`: an optimizer grid -- every run steps with its own optimizer's hyper-parameters.
+    -> list of result dicts."""
     R = len(models)
     a0 = args_list[0]
     tag = (lambda a: f"[shot {a.shot} fold {a.fold}]") if len({a.shot for a in args_list}) > 1 else (lambda a: f"[fold {a.fold}]")
@@ -479,6 +492,10 @@ def main_runs(args_list, models, optimizers, loaders_list, device, generators=No
     if len(by_cfg) > 1:
         fold_tag = tag
         tag = lambda a: f"[topj {a.topj} topk {a.topk} {hgrid_discard_name(a.discard_classifiers)}] " + fold_tag(a)
+
+    if per_run_adam:
+        cell_tag = tag
+        tag = lambda a: f"[seed {a.seed} lr {a.lr:g} wd {a.weight_decay:g}] " + cell_tag(a)
 
     def evaluate(ms, lds):
         """evaluation_runs over (model, loader) pairs named by run index: its plan belongs to one `args`, so a grid evaluates
@@ -511,7 +528,8 @@ def main_runs(args_list, models, optimizers, loaders_list, device, generators=No
     M.pack_splits([ls[2] for ls in loaders_list])
     for epoch in range(getattr(a0, "epochs", 25)):
         print("Epoch: ", epoch)
-        M.train_runs(models, trains, optimizers, device, a0 if len(by_cfg) == 1 else list(args_list), generators=generators)
+        M.train_runs(models, trains, optimizers, device, a0 if len(by_cfg) == 1 else list(args_list), generators=generators,
+                     per_run_adam=per_run_adam)
         # all runs' train and validation splits in one pass, then the test splits of the runs that improved in another
         ev = evaluate(list(range(R)) + list(range(R)), trains + [ls[1] for ls in loaders_list])
         better = [r for r in range(R) if ev[R + r]["auc"] > st[r]["best_val"]]
@@ -614,7 +632,7 @@ def cli_folds(args):
         g.set_state(torch.get_rng_state())
         args_list.append(a)
         models.append(model)
-        optimizers.append(torch.optim.Adam(model.parameters(), lr=1e-3, weight_decay=1e-4))
+        optimizers.append(torch.optim.Adam(model.parameters(), lr=args.lr, weight_decay=args.weight_decay))
         loaders_list.append(loaders)
         gens.append(g)
     return main_runs(args_list, models, optimizers, loaders_list, device, generators=gens)
@@ -741,10 +759,144 @@ def cli_hgrid(args):
             g.set_state(torch.get_rng_state())
             args_list.append(a)
             models.append(model)
-            optimizers.append(torch.optim.Adam(model.parameters(), lr=1e-3, weight_decay=1e-4))
+            optimizers.append(torch.optim.Adam(model.parameters(), lr=args.lr, weight_decay=args.weight_decay))
             loaders_list.append(loaders)
             gens.append(g)
         out += main_runs(args_list, models, optimizers, loaders_list, device, generators=gens)
+    return out
+
+# ------------------------------------------------------------------ optimizer grids (--seeds / --lrs / --wds)
+OPT_GRID_FLAGS = "--seeds / --lrs / --wds"
+
+
+def optgrid_requested(args):
+    return any(getattr(args, n, None) is not None for n in ("seeds", "lrs", "wds"))
+
+
+def _number_list(flag, text, kind):
+    try:
+        out = [kind(v) for v in str(text).split(",") if v.strip() != ""]
+    except ValueError:
+        raise SystemExit(f"{flag}: not a comma-separated list of numbers: {text!r}")
+    if not out:
+        raise SystemExit(f"{flag}: a non-empty list is needed, got {text!r}")
+    if len(set(out)) != len(out):
+        raise SystemExit(f"{flag}: a value named twice")
+    return out
+
+
+def optgrid_cells(args):
+    """[(seed, lr, weight_decay)] of --seeds x --lrs x --wds, seed-major, then lr, the weight decay innermost; a list that
+    is not given is the one --seed / --lr / --weight_decay.  An empty or malformed list, a value named twice, a negative or
+    non-finite rate and a grid without any seed are refused."""
+    if args.seeds is None and args.seed is None:
+        raise SystemExit("--lrs / --wds need --seed or --seeds: the cells of a fold start from one meta-learner and one mask stream")
+    seeds = [int(args.seed)] if args.seeds is None else _number_list("--seeds", args.seeds, int)
+    lrs = [float(args.lr)] if args.lrs is None else _number_list("--lrs", args.lrs, float)
+    wds = [float(args.weight_decay)] if args.wds is None else _number_list("--wds", args.wds, float)
+    for flag, vals in (("--lrs", lrs), ("--wds", wds)):
+        if not all(np.isfinite(v) and v >= 0 for v in vals):
+            raise SystemExit(f"{flag}: finite values >= 0 are needed, got {vals}")
+    return [(s_, lr, wd) for s_ in seeds for lr in lrs for wd in wds]
+
+
+def optgrid_dir(result_dir, cell):
+    """Where the runs of cell (seed, lr, weight_decay) write: {result_dir}/seed{S}_lr{LR}_wd{WD}, the numbers as format(x, "g")."""
+    return os.path.join(result_dir, f"seed{cell[0]}_lr{format(cell[1], 'g')}_wd{format(cell[2], 'g')}")
+
+
+def check_optgrid_args(args):
+    """Refusals of an optimizer grid, from the command line alone (before any bag is loaded)."""
+    if not optgrid_requested(args):
+        return
+    if getattr(args, "shots", ""):
+        raise SystemExit(f"{OPT_GRID_FLAGS} do not combine with --shots: one --shot per grid")
+    if hgrid_requested(args):
+        raise SystemExit(f"{OPT_GRID_FLAGS} do not combine with --topjs / --topks / --discard_sets: one grid per command")
+    if patch_map_splits(args) or args.patch_maps_from:
+        raise SystemExit(f"{OPT_GRID_FLAGS} do not combine with --patch_maps / --patch_maps_from: run one cell at a time")
+    if args.loader_seed_draw:
+        raise SystemExit(f"{OPT_GRID_FLAGS} do not combine with --loader_seed_draw: the runs draw their masks from private "
+                         "generators (no DataLoader base-seed draw)")
+    if args.ablation_study != "none":
+        raise SystemExit(f"{OPT_GRID_FLAGS} do not combine with --ablation_study: the grid trains the meta-learner, the ablation "
+                         "study trains none")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit(f"{OPT_GRID_FLAGS} are one-GPU options (WORLD_SIZE > 1): run the grid without a launcher")
+    optgrid_cells(args)
+
+
+def optgrid_runs(args, cells, folds):
+    """The runs' namespaces: cells in the given order, fold-major inside one (hgrid_runs' order)."""
+    import copy
+    out = []
+    for cell in cells:
+        for fold in folds:
+            a = copy.copy(args)
+            a.fold, a.seed, a.lr, a.weight_decay = fold, cell[0], cell[1], cell[2]
+            a.result_dir = optgrid_dir(args.result_dir, cell)
+            out.append(a)
+    return out
+
+
+def write_optgrid_summary(result_dir, cells, folds, shot):
+    """{result_dir}/opt_grid_summary.csv: one line per (lr, weight_decay) in order of first appearance -- the number of runs
+    (seeds x folds) and the mean and population standard deviation of their best validation AUC and of the test AUC at it,
+    read from the cells' best_results_* files (`best_val`, `test_at_best_val`: the keys --summary reads them by).  -> path."""
+    by_hp = {}
+    for cell in cells:
+        for fold in folds:
+            with open(os.path.join(optgrid_dir(result_dir, cell), f"best_results_shot_{shot}_fold_{fold}.json")) as f:
+                r = json.load(f)
+            by_hp.setdefault((cell[1], cell[2]), []).append((r["best_val"], r["test_at_best_val"]))
+    rows = []
+    for (lr, wd), vals in by_hp.items():
+        v = np.asarray(vals, dtype=np.float64)
+        rows.append({"lr": format(lr, "g"), "weight_decay": format(wd, "g"), "runs": len(vals),
+                     "best_val_mean": v[:, 0].mean(), "best_val_std": v[:, 0].std(),
+                     "test_auc_mean": v[:, 1].mean(), "test_auc_std": v[:, 1].std()})
+    path = os.path.join(result_dir, "opt_grid_summary.csv")
+    pd.DataFrame(rows).to_csv(path, index=False)
+    return path
+
+
+def cli_optgrid(args):
+    """`--seeds / --lrs / --wds` (with --folds or the one --fold): every (cell, fold) run in this process."""
+    cells = optgrid_cells(args)
+    folds = folds_of_rank(args.folds, 0, 1) if args.folds else [int(args.fold)]
+    device = torch.device("cuda", torch.cuda.current_device())
+    torch.cuda.set_device(device)
+    from . import runs as RUNS
+    blocks = hgrid_blocks(len(cells), len(folds), RUNS.MAX_RUNS)
+    # the footprint of the largest block before a bag is loaded: the splits of a fold count once for all its cells
+    itemsize = 2 if args.bag_dtype in ("bf16", "fp16") else 4
+    C_ = _synthetic_classes(args) if args.synthetic else len(_label_map(args))
+    fps = {a.fold: split_footprints(a) for a in optgrid_runs(args, cells[:1], folds)}
+    need = grid_bytes([fps[f] for _ in blocks[0] for f in folds], FEATURE_DIM, itemsize, C_)
+    free = torch.cuda.mem_get_info(device)[0]
+    if need > free:
+        raise SystemExit(f"--seeds x --lrs x --wds: a block of {len(blocks[0])} cell(s) x {len(folds)} fold(s) needs about "
+                         f"{need / 2**30:.1f} GiB of device memory, {free / 2**30:.1f} GiB are free: name fewer folds")
+    out, share = [], {}
+    for block in blocks:
+        args_list, models, optimizers, loaders_list, gens = [], [], [], [], []
+        for a in optgrid_runs(args, [cells[i] for i in block], folds):
+            loaders = prepare(a, device, share=share, share_train=True)
+            assert all(isinstance(ld, M.ResidentBags) for ld in loaders), "an optimizer grid needs resident splits (--resident 1)"
+            # exactly what the cell's own `--fold F --seed S --lr LR --weight_decay WD` command does with the default generator:
+            # seed, build the meta-learner, and the masks follow from wherever that leaves the stream -- the (lr, wd) cells of a
+            # (seed, fold) start from equal parameters and equal generator states and share their masks
+            torch.manual_seed(a.seed)
+            model = M.senet(FEATURE_DIM, 4).to(device)
+            g = torch.Generator()
+            g.set_state(torch.get_rng_state())
+            args_list.append(a)
+            models.append(model)
+            optimizers.append(torch.optim.Adam(model.parameters(), lr=a.lr, weight_decay=a.weight_decay))
+            loaders_list.append(loaders)
+            gens.append(g)
+        out += main_runs(args_list, models, optimizers, loaders_list, device, generators=gens, per_run_adam=True)
+    print("optimizer grid summary:", write_optgrid_summary(args.result_dir, cells, folds, args.shot))
     return out
 
 
@@ -753,10 +905,13 @@ def cli(argv=None):
     if args.summary:
         summary(args)
         return None
+    check_optgrid_args(args)
     check_hgrid_args(args)
     check_patch_map_args(args)
     if not torch.cuda.is_available():
         raise RuntimeError("moc_amd needs a GPU: there is no CPU fallback")
+    if optgrid_requested(args):
+        return cli_optgrid(args)
     if hgrid_requested(args):
         return cli_hgrid(args)
     if args.folds or args.shots:
@@ -784,7 +939,7 @@ def cli(argv=None):
     if args.seed is not None:
         torch.manual_seed(args.seed)
     model = M.senet(FEATURE_DIM, 4).to(device)                                                   # main_moc.py:315
-    optimizer = torch.optim.Adam(model.parameters(), lr=1e-3, weight_decay=1e-4)         # main_moc.py:316
+    optimizer = torch.optim.Adam(model.parameters(), lr=args.lr, weight_decay=args.weight_decay)   # main_moc.py:316 (1e-3, 1e-4)
     loaders = (train_loader, val_loader, test_loader)
     if args.patch_maps_from:
         return patch_maps_from(args, model, loaders, device)

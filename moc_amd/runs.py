@@ -11,7 +11,8 @@ state, its own stream of row masks -- `torch.rand(N) > 0.5` per slide drawn from
 reference's runs are separate processes, each with its own default generator).  Per run the result is bit-identical to
 training it alone with `main_moc.train` from the same generator state (tests/test_gpu_runs.py).
 
-What the runs share: the classifier bank, the hyper-parameters of Adam, storage type and width.  topj / topk /
+What the runs share: the classifier bank, the hyper-parameters of Adam (unless `per_run_adam`: then every run steps with its
+own optimizer's lr / betas / eps / weight_decay, still in one chain -- DESIGN.md section 9i), storage type and width.  topj / topk /
 discard_classifiers are common when `args` is one namespace and per run when it is a list of R of them (a hyper-parameter
 grid: DESIGN.md section 9h).  The models' parameter tensors and the optimizers' moments are re-seated as views into one arena per kind
 (state_dict() / load_state_dict() keep working; the tensors' values are preserved).
@@ -39,7 +40,7 @@ from concurrent.futures import ThreadPoolExecutor
 import torch
 
 from . import engine
-from ._lib import MocRuns, check, lib, ptr
+from ._lib import MocAdamHp, MocRuns, check, lib, ptr
 from .engine import HIDDEN, MetaState, SlideBatch
 
 MAX_RUNS = 32           # runs of one TrainRuns (five shots x five folds and some); one moc_train_steps_runs call: 16
@@ -75,6 +76,30 @@ def mask_groups(keys):
     return leader
 
 
+def adam_hp(group):
+    """An optimizer param group's Adam hyper-parameters as (lr, beta1, beta2, eps, weight_decay), Python floats."""
+    b1, b2 = group["betas"]
+    return (float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]))
+
+
+def hp_records(hps):
+    """[(lr, beta1, beta2, eps, weight_decay)] -> the host array of moc_adam_hp_t that moc_train_steps_runs_hp reads."""
+    arr = (MocAdamHp * len(hps))()
+    for rec, hp in zip(arr, hps):
+        rec.lr, rec.beta1, rec.beta2, rec.eps, rec.weight_decay = hp
+    return arr
+
+
+def steps_runs_hp(batch_c, meta_c, runs_c, ws_c, labels_ptr, slide0, n, use_bits, records, stream):
+    """moc_train_steps_runs_hp; `records`: hp_records(...) of runs_c.n_runs runs, or None.  A refusal -- the library launches
+    nothing then -- is a RuntimeError with the library's text."""
+    rc = lib().moc_train_steps_runs_hp(C.byref(batch_c), C.byref(meta_c), C.byref(runs_c), C.byref(ws_c), labels_ptr,
+                                       slide0, n, use_bits, records, stream)
+    if rc != 0:
+        raise RuntimeError(f"moc_train_steps_runs_hp failed (code {rc}): {lib().moc_last_error().decode(errors='replace')}")
+    return rc
+
+
 def consecutive_blocks(items):
     """[a, a+1, a+2, b, b+1] -> [(a, 3), (b, 2)]: blocks of consecutive integers, in the given order.  Pure."""
     out = []
@@ -90,8 +115,11 @@ class TrainRuns:
     """R (model, optimizer, resident train split) triples trained in lockstep.  `generators`: one CPU torch.Generator
     per run -- the run's mask stream (default: fresh generators seeded from the default generator, in run order)."""
 
-    def __init__(self, models, optimizers, splits, device, args, generators=None):
+    def __init__(self, models, optimizers, splits, device, args, generators=None, per_run_adam=False):
         from . import main_moc as M
+        # per_run_adam: every run steps with its OWN optimizer's lr / betas / eps / weight_decay (moc_train_steps_runs_hp) --
+        # the cells of an lr x weight-decay grid stay in one lockstep chain; default: the runs must share them
+        self.per_run_adam = bool(per_run_adam)
         R = len(models)
         assert 1 <= R <= MAX_RUNS and len(optimizers) == R and len(splits) == R, f"1 .. {MAX_RUNS} runs"
         per_run = isinstance(args, (list, tuple))
@@ -187,13 +215,14 @@ class TrainRuns:
         self.W2_alt = torch.empty((R, 4, H), **f32)
         offs = (0, H * D, H * D + H, H * D + H + 4 * H)
         shapes = ((H, D), (H,), (4, H), (4,))
-        group0, run_steps = None, []
+        group0, run_steps, self._adam_groups = None, [], []
         for r, (model, opt) in enumerate(zip(self.models, self.optimizers)):
             meta = MetaState(model, opt)                      # (validates the pair; creates Adam's state if it is new)
             g = meta._group
             hp = (float(g["lr"]), tuple(float(b) for b in g["betas"]), float(g["eps"]), float(g["weight_decay"]))
             group0 = group0 or hp
-            assert hp == group0, "train_runs: the runs must share Adam's hyper-parameters"
+            assert self.per_run_adam or hp == group0, "train_runs: the runs must share Adam's hyper-parameters"
+            self._adam_groups.append(g)
             run_steps.append(int(meta.c.step))
             for p, o, shp in zip(meta.params, offs, shapes):
                 cnt = p.numel()
@@ -462,6 +491,9 @@ class TrainRuns:
                      for r in range(grp["r0"], grp["r0"] + grp["runs"].n_runs)}
             assert len(steps) == 1, "train_runs: the runs of a chain no longer agree on the Adam step count"
             grp["step"] = steps.pop()
+            if self.per_run_adam:                             # re-read every pass, as MetaState.refresh does: a scheduler's or
+                grp["hp"] = hp_records([adam_hp(self._adam_groups[r])    # a user's edit between two passes is seen
+                                        for r in range(grp["r0"], grp["r0"] + grp["runs"].n_runs)])
         main = engine.stream_obj()
         ready = None
         if len(self.groups) > 1:
@@ -483,6 +515,9 @@ class TrainRuns:
             mc.lr, mc.beta1, mc.beta2, mc.eps, mc.weight_decay = (self.meta.c.lr, self.meta.c.beta1, self.meta.c.beta2,
                                                                   self.meta.c.eps, self.meta.c.weight_decay)
             mc.step = grp["step"]
+            if self.per_run_adam:                             # the records of THIS chain's runs: r0 ... (not run 0 ...)
+                return lib().moc_train_steps_runs_hp(C.byref(bc), C.byref(mc), C.byref(grp["runs"]), C.byref(ws), ptr(self.labels),
+                                                     grp["slide0"], grp["n"], grp["use"], grp["hp"], raw_stream)
             return lib().moc_train_steps_runs(C.byref(bc), C.byref(mc), C.byref(grp["runs"]), C.byref(ws), ptr(self.labels),
                                               grp["slide0"], grp["n"], grp["use"], raw_stream)
         main_raw = engine._stream()
@@ -501,7 +536,7 @@ class TrainRuns:
         else:
             rcs = [group_call(grp, raw_of(grp)) for grp in self.groups]
         for rc in rcs:
-            check(rc, "moc_train_steps_runs")
+            check(rc, "moc_train_steps_runs_hp" if self.per_run_adam else "moc_train_steps_runs")
         for grp in self.groups:
             if grp["stream"] is not None:
                 ev = torch.cuda.Event()
