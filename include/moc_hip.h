@@ -496,6 +496,23 @@ int moc_gated_attention_backward(const float* h, int64_t N, int L, const float* 
                                  float* dab, float* ds, float* dcol, float* dbc, void* workspace,
                                  size_t workspace_bytes, moc_stream_t stream);
 
+/* f3: the per-patch logits of the adapter heads, one pass over the bag
+ * (models/model_adapters.py:185-193 Conch_CLIP_Ada.forward; :330-405 Conch_MOE_CLIP_Ada.forward with the soft router,
+ * use_switch_gate=False) -- everything in front of the top-j pooling.  unit(v) = v / ||v|| (a zero row gives NaN):
+ *   E == 1:  a = relu(W2 relu(W1 x));  logits = unit(ratio a + (1 - ratio) x) Wc
+ *   E >= 2:  f = unit(x);  w = softmax_E(G f);  a_e = relu(W2_e relu(W1_e f));  s = unit(sum_e w_e a_e);
+ *            logits = unit(ratio s + (1 - ratio) f) Wc       (ratio is the module's stored clip_ratio / E)
+ * X [N, c] device fp32 row-major, 16-byte aligned.  W1, W2: HOST arrays of E device pointers, W1[e] [h, c] and W2[e] [c, h]
+ * (nn.Linear layout, no bias), each 16-byte aligned.  G [E, c] (16-byte aligned; null if and only if E == 1).  Wc [c, C].
+ * logits [N, C] fp32, written.  Built for c = 512, h = 128, 1 <= E <= 8, 1 <= C <= 64; anything else is refused.
+ * The bf16-term images of the weights are rebuilt in `workspace` on every call (moc_adapter_workspace bytes of device
+ * memory, 16-byte aligned; 0 for shapes outside the limits): nothing is cached between calls.
+ * Additive to ABI 20: the version number is unchanged. */
+size_t moc_adapter_workspace(int64_t N, int c, int h, int E, int C);
+int moc_adapter_logits(const float* X, int64_t N, int c, const float* const* W1, const float* const* W2, int h, int E,
+                       const float* G /*nullable*/, const float* Wc, int C, float ratio, float* logits,
+                       void* workspace, size_t workspace_bytes, moc_stream_t stream);
+
 /* a10-a15 fused: `n` consecutive meta-steps (one slide each, slides slide0..slide0+n-1 in
  * order, one Adam step per slide: main_moc.py:380-410), parameters and Adam moments
  * updated in place.  Per-slide loss/pooled land in ws->loss / ws->pooled. */

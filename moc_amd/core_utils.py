@@ -2,8 +2,10 @@
 signatures (reference utils/core_utils.py): Accuracy_Logger,
 EarlyStopping, train_loop, validate, summary and a `train` for the max-instance MIL models.
 A model is anything whose forward returns the 5-tuple (logits, Y_prob, Y_hat, _, _) -- moc_amd.model_mil
-on the HIP path.  Loaders yield (data, label) with batch size 1.  CLAM / ViLa variants, tensorboard and
-the SVM loss are outside the MOC path and not reproduced."""
+on the HIP path.  Loaders yield (data, label) with batch size 1.  The CLAM variants (train_loop_clam,
+validate_clam and `train` for model_type clam_sb / clam_mb / transmil) are here too, driving
+moc_amd.model_clam on the gated-attention kernel; the ViLa variants, tensorboard and the SVM loss are
+outside the MOC path and not reproduced."""
 from __future__ import annotations
 
 import os

@@ -1122,3 +1122,33 @@ def gated_attention_backward(h, Wa, ba, Wb, bb, Wc, A_raw, gA=None, gM=None):
     dh = dab @ X
     dW = dab.t() @ h                                               # [S, L]: dWa over dWb (over M)
     return dh, dW[:D], dcol[:D], dW[D:2 * D], dcol[D:2 * D], dcol[2 * D:].view(K, D), dbc
+
+
+ADAPTER_C, ADAPTER_H, ADAPTER_MAX_E, ADAPTER_MAX_CLASSES = 512, 128, 8, 64      # what moc_adapter_logits is built for
+
+
+def adapter_logits(feat: torch.Tensor, W1s, W2s, router, classifier: torch.Tensor, ratio: float) -> torch.Tensor:
+    """SURVEY.md section 8 row f3 (models/model_adapters.py:185-193, :330-405 with the soft router): the per-patch logits
+    [N, C] of a CLIP-Adapter (one (W1, W2) pair, router None) or a MoE-adapter bag (E pairs, router [E, c]) in one pass
+    over feat [N, 512] (include/moc_hip.h moc_adapter_logits).  W1s[e] [128, 512], W2s[e] [512, 128] (nn.Linear layout),
+    classifier [512, C]; `ratio` is the mixing weight the module stores (clip_ratio, or clip_ratio / E).  No gradient."""
+    W1s, W2s = list(W1s), list(W2s)
+    ts = [feat, classifier] + W1s + W2s + ([router] if router is not None else [])
+    assert all(t.is_cuda and t.dtype == torch.float32 for t in ts), "adapter_logits: fp32 tensors on the GPU (no CPU fallback)"
+    assert len(W1s) == len(W2s) >= 1 and (router is None) == (len(W1s) == 1), "adapter_logits: one router row per expert, none for one"
+    feat, classifier = feat.detach().contiguous(), classifier.detach().contiguous()
+    W1s, W2s = [w.detach().contiguous() for w in W1s], [w.detach().contiguous() for w in W2s]
+    router = router.detach().contiguous() if router is not None else None
+    N, c = feat.shape
+    E, h, Cc = len(W1s), W1s[0].shape[0], classifier.shape[1]
+    assert all(w.shape == (h, c) for w in W1s) and all(w.shape == (c, h) for w in W2s) and classifier.shape[0] == c
+    assert router is None or router.shape == (E, c)
+    dev = feat.device
+    logits = torch.empty((N, Cc), dtype=torch.float32, device=dev)
+    nbytes = lib().moc_adapter_workspace(N, c, h, E, Cc)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    p1, p2 = (C.c_void_p * E)(*[w.data_ptr() for w in W1s]), (C.c_void_p * E)(*[w.data_ptr() for w in W2s])
+    check(lib().moc_adapter_logits(ptr(feat), N, c, C.cast(p1, C.c_void_p), C.cast(p2, C.c_void_p), h, E, ptr(router),
+                                   ptr(classifier), Cc, C.c_float(float(ratio)), ptr(logits), ptr(ws), nbytes, _stream()),
+          "moc_adapter_logits")
+    return logits

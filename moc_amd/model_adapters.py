@@ -2,8 +2,12 @@
 reference's class names, constructor arguments, parameter names and forward signatures (SURVEY.md
 section 8, row f3; reference models/model_adapters.py).  Every forward ends in the same top-j mean
 pooling over the N patches (reference :173-183 and its copies): that runs on the HIP path
-(pool_autograd.topk_mean_pool -> moc_topk_mean) with autograd through the pooled rows; the adapter
-layers themselves are plain torch GEMMs.  forward(feat [N, c_in]) -> pooled logits [1, C]."""
+(pool_autograd.topk_mean_pool -> moc_topk_mean) with autograd through the pooled rows.  By default the
+adapter layers themselves are plain torch GEMMs over the whole bag.  Conch_CLIP_Ada and
+Conch_MOE_CLIP_Ada can instead score the bag in one HIP pass (class attribute `fused`, off by default;
+`forward_fused`: engine.adapter_logits -> moc_adapter_logits) and run their torch layers, with autograd,
+on the at most topj * C pooled rows only -- the pooling sends gradient nowhere else, so the value and
+every parameter gradient are dense autograd's.  forward(feat [N, c_in]) -> pooled logits [1, C]."""
 from __future__ import annotations
 
 import math
@@ -12,6 +16,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import engine
 from .pool_autograd import topk_mean_pool
 
 
@@ -43,6 +48,32 @@ class _PooledHead(nn.Module):
 
     def _zero_shot(self, feat, topj):
         return self.topj_pooling(_unit(feat) @ self.classifier, topj=topj)
+
+    def _fusable(self, feat, weights, n_experts):
+        """What moc_adapter_logits is built for (forward_fused takes the torch path otherwise)."""
+        cls = self.classifier
+        return (torch.is_tensor(feat) and feat.is_cuda and feat.dtype == torch.float32 and feat.dim() == 2
+                and feat.shape[0] >= 1 and feat.shape[1] == engine.ADAPTER_C and feat.is_contiguous()
+                and feat.data_ptr() % 16 == 0 and not feat.requires_grad
+                and 1 <= n_experts <= engine.ADAPTER_MAX_E
+                and all(w.is_cuda and w.dtype == torch.float32 and w.device == feat.device for w in weights)
+                and all(w.shape == ((engine.ADAPTER_H, engine.ADAPTER_C) if i % 2 == 0 else (engine.ADAPTER_C, engine.ADAPTER_H))
+                        for i, w in enumerate(weights))
+                and torch.is_tensor(cls) and cls.is_cuda and cls.device == feat.device and cls.dtype == torch.float32
+                and cls.dim() == 2 and cls.shape[0] == engine.ADAPTER_C and 1 <= cls.shape[1] <= engine.ADAPTER_MAX_CLASSES)
+
+    def _pool_fused(self, feat, logits, topj):
+        """`logits` [N, C] (no gradient) rank the rows as topj_pooling does (moc_topk_mean: lowest row on ties); the
+        module's own layers (`_row_logits`) then run with autograd on the unique pooled rows -- at most topj * C -- and
+        the per-class mean of those is returned: [1, C]."""
+        n, c = logits.shape
+        cols = logits.t().contiguous()
+        _, idx, _ = engine.topk_mean(cols, cols, int(topj), want_idx=True)
+        kk = min(int(topj), n)
+        rows, inv = torch.unique(idx[0, :, :kk].reshape(-1).long(), return_inverse=True)
+        sub = self._row_logits(feat[rows])                                  # [U, C], U <= topj * C
+        picked = sub[inv.view(c, kk), torch.arange(c, device=feat.device).unsqueeze(1)]
+        return picked.mean(dim=1).unsqueeze(0)
 
 
 class Linear_Adapter(nn.Module):
@@ -101,9 +132,31 @@ class Conch_CLIP_Ada(_PooledHead):
         self.adapter = _bottleneck(c_in, reduction)
         self.topj, self.classifier, self.num_classes, self.clip_ratio = topj, classifier_tensor, num_classes, clip_ratio
 
-    def forward(self, feat):
+    fused = False      # True: forward goes through forward_fused
+
+    def _row_logits(self, feat):
         mixed = self.adapter(feat) * self.clip_ratio + feat * (1 - self.clip_ratio)
-        return self.topj_pooling(_unit(mixed) @ self.classifier, topj=self.topj)
+        return _unit(mixed) @ self.classifier
+
+    def forward(self, feat):
+        if self.fused:
+            return self.forward_fused(feat)
+        return self.topj_pooling(self._row_logits(feat), topj=self.topj)
+
+    def forward_fused(self, feat):
+        """The same pooled logits [1, C] and the same parameter gradients as the torch path, with the bag scored in one
+        HIP pass (moc_adapter_logits) and the torch layers re-run, with autograd, on the pooled rows only.
+        Takes the torch path instead, silently, when
+          - `feat` is not a contiguous, 16-byte aligned fp32 [N >= 1, 512] tensor on the GPU, or requires grad (the
+            fused path forms no gradient with respect to the bag);
+          - the bottleneck is not 512 -> 128 -> 512 fp32 on the same device;
+          - `classifier` is not a [512, C <= 64] fp32 tensor on that device."""
+        w = [self.adapter[0].weight, self.adapter[2].weight]
+        if not self._fusable(feat, w, 1):
+            return self.topj_pooling(self._row_logits(feat), topj=self.topj)
+        with torch.no_grad():
+            logits = engine.adapter_logits(feat, w[:1], w[1:], None, self.classifier, self.clip_ratio)
+        return self._pool_fused(feat, logits, self.topj)
 
     def forward_disable_ada(self, feat):
         return self._zero_shot(feat, self.topj)
@@ -190,14 +243,47 @@ class Conch_MOE_CLIP_Ada(_PooledHead):
         for i in range(self.ada_num):
             _kaiming(getattr(self, f"adapter_{i}"))
 
-    def forward(self, feat):
+    fused = False      # True: forward goes through forward_fused
+
+    def _row_logits(self, feat, with_balance=False):
         feat = _unit(feat)
         weight, balance = self.ada_router(feat)                                        # [N, E]
         experts = torch.stack([getattr(self, f"adapter_{i}")(feat) for i in range(self.ada_num)], dim=-1)
         mixed = _unit((experts * weight.unsqueeze(-2)).sum(-1))
-        pooled = self.topj_pooling(_unit(mixed * self.clip_ratio + feat * (1 - self.clip_ratio)) @ self.classifier,
-                                   topj=self.topj)
+        logits = _unit(mixed * self.clip_ratio + feat * (1 - self.clip_ratio)) @ self.classifier
+        return (logits, balance) if with_balance else logits
+
+    def _forward_dense(self, feat):
+        logits, balance = self._row_logits(feat, with_balance=True)
+        pooled = self.topj_pooling(logits, topj=self.topj)
         return (pooled, balance) if self.use_balance_loss else pooled
+
+    def forward(self, feat):
+        if self.fused:
+            return self.forward_fused(feat)
+        return self._forward_dense(feat)
+
+    def forward_fused(self, feat):
+        """The same pooled logits [1, C] and the same parameter gradients as the torch path, with the bag scored in one
+        HIP pass (moc_adapter_logits, soft router) and the torch layers re-run, with autograd, on the pooled rows only.
+        Takes the torch path instead, silently, when
+          - `use_switch_gate` or `use_balance_loss` is set (the hard top-1 gate and the balance loss, a statistic of
+            the whole bag, are not built into the kernel);
+          - `feat` is not a contiguous, 16-byte aligned fp32 [N >= 1, 512] tensor on the GPU, or requires grad (the
+            fused path forms no gradient with respect to the bag);
+          - there are more than 8 experts, or a bottleneck is not 512 -> 128 -> 512 fp32 on the same device;
+          - `classifier` is not a [512, C <= 64] fp32 tensor on that device."""
+        nets = [getattr(self, f"adapter_{i}") for i in range(self.ada_num)]
+        w = [m.weight for net in nets for m in (net[0], net[2])]
+        gate = self.ada_router.gate.weight
+        if (self.use_switch_gate or self.use_balance_loss or self.ada_router.use_switch_gate or self.ada_router.use_balance_loss
+                or not self._fusable(feat, w, self.ada_num)
+                or not (gate.is_cuda and gate.device == feat.device and gate.dtype == torch.float32
+                        and gate.shape == (self.ada_num, engine.ADAPTER_C))):
+            return self._forward_dense(feat)
+        with torch.no_grad():
+            logits = engine.adapter_logits(feat, w[0::2], w[1::2], gate, self.classifier, self.clip_ratio)
+        return self._pool_fused(feat, logits, self.topj)
 
     def forward_disable_ada(self, feat):
         return self._zero_shot(feat, self.topj)
