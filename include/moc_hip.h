@@ -224,6 +224,32 @@ int moc_scores(const moc_batch_t* B, const void* bank, moc_stream_t stream);
  * reports it, whatever else the GPU is running.  bench.py's `roofline` uses it. */
 int moc_scores_timed(const moc_batch_t* B, const void* bank, moc_stream_t stream, void* start_event, void* stop_event);
 
+/* a2 for several NARROW banks in one read of the bags (additive in ABI 20): prompt-bank selection.  A bank of at most 16
+ * columns is one n-tile of the score kernel's image; up to moc_scores_banks_max of them laid side by side are an image its
+ * main loop multiplies as it is, and a per-n-tile row epilogue writes bank g's statistics into bank g's own arrays -- bit
+ * for bit what moc_scores writes over a batch with that bank alone (a column's accumulation chain does not depend on which
+ * other columns share the MFMA; the epilogue is the one-n-tile epilogue on the bank's own window of the tile).
+ * From B the entry takes X, dtype, D, the slide layout (row_off, x_off, total_rows, n_slides, max_rows) and the mask lists
+ * (mask, kept, n_kept: run moc_mask_compact first); B->stats, B->sel_flag, B->C, B->Ce, B->topj and B->topk are ignored.
+ * An evaluation pass: static walk over the whole chip, full statistics layout -- a batch with tile_ticket / cu_reserved
+ * set or with MOC_STATS_COMPACT is refused (MOC_EINVAL), as are a null pointer, n_banks outside 1 .. 4, a Ce outside
+ * C < Ce <= 16 and more banks than moc_scores_banks_max; MOC_EUNSUPPORTED where not even one bank's image fits in LDS
+ * beside the epilogue tiles and one slide's metadata (moc_scores_banks_max == 0).  Nothing is launched on a refusal. */
+int    moc_scores_banks_max(int D, int dtype);             /* banks one launch serves for this D / storage: the streaming
+                                                              kernel's n-tile limits (four on fp32 bags, three on 16-bit
+                                                              bags) and 160 KiB of LDS; 0 = none */
+size_t moc_bank_set_bytes(int D, int n_banks, int dtype);  /* n_banks one-n-tile images back to back */
+typedef struct moc_bank_set {
+    int32_t  n_banks;            /* 1 .. moc_scores_banks_max */
+    int32_t  C;                  /* the same for every bank */
+    int32_t  Ce[4];              /* per bank, C < Ce <= 16 */
+    float*   stats[4];           /* per bank [2C+3, B->total_rows], full layout */
+    uint8_t* sel_flag[4];        /* per bank [B->total_rows], cleared by the pass as moc_scores does */
+    const void* image;           /* moc_bank_set_bytes: bank g's image (moc_prepare_bank with its own Ce, fg_from_ext) at
+                                    g * moc_bank_bytes(D, 16, dtype) */
+} moc_bank_set_t;
+int moc_scores_banks(const moc_batch_t* B, const moc_bank_set_t* S, moc_stream_t stream);
+
 /* a2 from a cache (round 4, opt-in): the statistics of a row depend only on the row and the frozen bank, so a resident
  * split can keep the statistics of ALL its rows (`stats_all` [rows of stats, all_rows], laid out like `stats` and indexed
  * by the row's position in B->X: the output of an UNMASKED moc_scores over the split with the same B->flags layout) and a

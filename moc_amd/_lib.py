@@ -60,6 +60,12 @@ class MocRuns(C.Structure):
     _fields_ = [("n_runs", C.c_int32), ("slide_stride", C.c_int32), ("par_stride", C.c_int64), ("image_stride", C.c_int64)]
 
 
+class MocBankSet(C.Structure):
+    """moc_bank_set_t: up to four narrow banks of one moc_scores_banks launch."""
+    _fields_ = [("n_banks", C.c_int32), ("C", C.c_int32), ("Ce", C.c_int32 * 4), ("stats", _p * 4), ("sel_flag", _p * 4),
+                ("image", _p)]
+
+
 class MocAdamHp(C.Structure):
     """moc_adam_hp_t: one run's Adam hyper-parameters (moc_train_steps_runs_hp), the optimizer's unrounded Python floats."""
     _fields_ = [(n, C.c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay")]
@@ -80,6 +86,9 @@ SIGNATURES = {
     "moc_scores": (C.c_int, [_BP, _p, _p]),
     "moc_scores_timed": (C.c_int, [_BP, _p, _p, _p, _p]),
     "moc_scores_from_cache": (C.c_int, [_BP, _p, C.c_int64, _p]),
+    "moc_scores_banks_max": (C.c_int, [C.c_int, C.c_int]),
+    "moc_bank_set_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "moc_scores_banks": (C.c_int, [_BP, C.POINTER(MocBankSet), _p]),
     "moc_row_stats": (C.c_int, [_p, C.c_int64, C.c_int, C.c_int, _p, _p]),
     "moc_select": (C.c_int, [_BP, _p]),
     "moc_gather_candidates": (C.c_int, [_BP, _p, _p]),

@@ -13,7 +13,7 @@ from typing import Sequence
 import torch
 
 from . import _lib
-from ._lib import MocBatch, MocMeta, MocMetaWs, MocRuns, check, lib, ptr
+from ._lib import MocBankSet, MocBatch, MocMeta, MocMetaWs, MocRuns, check, lib, ptr
 
 HIDDEN = 64
 # MOC_STEP_GRAPH=1: a pass of meta-steps as one hipGraph launch (moc_train_steps_graph) instead of 2 n + 1 stream
@@ -212,6 +212,59 @@ class Bank:
         return hit[0]
 
 
+BANK_SET_MAX_CE = 16        # a bank of a BankSet is ONE n-tile of the score kernel's image
+
+
+def plan_bank_passes(D: int, dtype: torch.dtype, n_banks: int):
+    """The cuts of `n_banks` narrow banks into score passes: [(first bank, banks), ...], each of at most
+    moc_scores_banks_max(D, storage) banks, in order.  Pure (the limit is host arithmetic of the library: no GPU)."""
+    per = int(lib().moc_scores_banks_max(int(D), _dtype_code(dtype)))
+    assert per >= 1, f"no multi-bank score pass at D={D} on {dtype} bags (one bank's image does not fit in LDS)"
+    assert n_banks >= 1, "no bank given"
+    return [(g0, min(per, n_banks - g0)) for g0 in range(0, n_banks, per)]
+
+
+def bank_work_row_bytes(C_: int) -> int:
+    """Bytes per bag row of ONE bank's work arrays (SlideBatch.scores_banks: stats, sel_flag, sel_idx, sel_row, cand, and the
+    mixed scores of the evaluation forward) -- what a chunk of slides costs per bank beside the bags themselves."""
+    return 4 * (2 * C_ + 3) + 1 + 4 + 8 + 4 * (2 * C_ + 2) + 4 * C_
+
+
+class BankSet:
+    """Several classifier banks of one class count, each at most 16 columns wide, as moc_scores_banks takes them: bank g's
+    image (moc_prepare_bank with its own Ce and fg_from_ext) at g * moc_bank_bytes(D, 16, storage) of one array, and the
+    list cut into passes of at most moc_scores_banks_max banks (plan_bank_passes).
+    banks: [(W [D, C], W_ext [D, Ce][, fg_from_ext]), ...]."""
+
+    def __init__(self, banks, dtype: torch.dtype, device):
+        banks = [tuple(b) for b in banks]
+        assert banks and all(len(b) in (2, 3) for b in banks), "BankSet: a list of (W, W_ext[, fg_from_ext])"
+        W0 = banks[0][0]
+        self.D, self.C, self.dtype = int(W0.size(0)), int(W0.size(1)), dtype
+        self.Ce = []
+        for g, b in enumerate(banks):
+            W, We = b[0], b[1]
+            assert W.dim() == 2 and We.dim() == 2 and W.size(0) == self.D and We.size(0) == self.D, f"BankSet: bank {g}: bad shapes"
+            assert W.size(1) == self.C, f"BankSet: banks of different C ({self.C} and {W.size(1)} classes) do not share a pass"
+            assert We.size(1) > self.C, "logits should have more bg classes"
+            assert We.size(1) <= BANK_SET_MAX_CE, \
+                f"BankSet: bank {g} has Ce={We.size(1)} > {BANK_SET_MAX_CE} columns; wide banks keep zs_evaluation / evaluation per bank"
+            self.Ce.append(int(We.size(1)))
+        self.n_banks = len(banks)
+        self.passes = plan_bank_passes(self.D, dtype, self.n_banks)
+        code = _dtype_code(dtype)
+        self.tile_bytes = int(lib().moc_bank_bytes(self.D, BANK_SET_MAX_CE, code))
+        assert lib().moc_bank_set_bytes(self.D, self.n_banks, code) == self.n_banks * self.tile_bytes
+        self.image = torch.empty(self.n_banks * self.tile_bytes, dtype=torch.uint8, device=device)
+        self._keep = []
+        for g, b in enumerate(banks):
+            Wd = b[0].detach().to(device=device, dtype=torch.float32).contiguous()
+            Wed = b[1].detach().to(device=device, dtype=torch.float32).contiguous()
+            check(lib().moc_prepare_bank(ptr(Wd), ptr(Wed), self.D, self.C, self.Ce[g], code, int(bool(b[2])) if len(b) == 3 else 0,
+                                         self.image.data_ptr() + g * self.tile_bytes, _stream()), "moc_prepare_bank")
+            self._keep.append((Wd, Wed))
+
+
 class SlideBatch:
     """Slides packed back to back in one device array + every work array of phase A.
 
@@ -395,6 +448,33 @@ class SlideBatch:
         check(lib().moc_mask_compact(C.byref(self.c), _stream()), "moc_mask_compact")
         check(lib().moc_scores(C.byref(self.c), ptr(bank.image), _stream()), "moc_scores")
 
+    def scores_banks(self, bank_set: "BankSet"):
+        """The score pass for every bank of `bank_set` in one read of the bags per group of banks (moc_scores_banks): -> one
+        light batch per bank (BankView) that shares this batch's X, layout and mask lists and owns its statistics, flags,
+        selection and candidate arrays, with its bank's C and Ce -- bit for bit what scores(bank) leaves in a batch of that
+        bank alone; moc_select, moc_gather_candidates, moc_meta_forward, moc_topk_mean_multi and moc_pool_loss run on it
+        unchanged.  The views are kept with this batch and handed out again for a set of the same (C, Ce) list."""
+        assert bank_set.D == self.D and bank_set.dtype == self.X.dtype, "scores_banks: the bank set is for another D / storage"
+        assert self.c.tile_ticket is None and self.c.cu_reserved is None, "scores_banks: an evaluation pass (static walk, whole chip)"
+        key = (bank_set.C, tuple(bank_set.Ce))
+        if getattr(self, "_bank_views_key", None) != key:
+            self._bank_views = [BankView(self, bank_set.C, ce) for ce in bank_set.Ce]
+            self._bank_views_key = key
+        views = self._bank_views
+        check(lib().moc_mask_compact(C.byref(self.c), _stream()), "moc_mask_compact")
+        c = MocBatch.from_buffer_copy(self.c)
+        c.flags = 0                                   # (a cached plan's batch may carry the layout of its last phase A)
+        for g0, n in bank_set.passes:
+            S = MocBankSet(n_banks=n, C=bank_set.C, image=bank_set.image.data_ptr() + g0 * bank_set.tile_bytes)
+            for i in range(n):
+                S.Ce[i], S.stats[i], S.sel_flag[i] = bank_set.Ce[g0 + i], ptr(views[g0 + i].stats), ptr(views[g0 + i].sel_flag)
+            check(lib().moc_scores_banks(C.byref(c), C.byref(S), _stream()), "moc_scores_banks")
+        for v in views:
+            v.c.mask, v.c.max_rows = self.c.mask, self.c.max_rows
+            v._layout(False)
+            v._n_sel_stale()
+        return views
+
     def select(self):
         self._n_sel_stale()
         check(lib().moc_select(C.byref(self.c), _stream()), "moc_select")
@@ -429,6 +509,38 @@ class SlideBatch:
             t["tile_ws"] = torch.empty(nb, dtype=torch.uint8, device=dev) if nb else None
             self._ws = (t, MocMetaWs(**{k: ptr(v) for k, v in t.items()}, tile_ws_bytes=nb))
         return self._ws
+
+
+class BankView(SlideBatch):
+    """One bank's batch behind SlideBatch.scores_banks: the parent's X, slide layout and mask lists (shared, not copied), and
+    its own statistics, flags, selection and candidate arrays with this bank's C and Ce.  An evaluation batch: no H1 / gates."""
+
+    eval_only = True
+
+    def __init__(self, parent: SlideBatch, C_: int, Ce: int):
+        dev, T, n = parent.device, parent.total, parent.n_slides
+        self.parent = parent
+        self.X, self.sizes, self.device = parent.X, parent.sizes, dev
+        self.n_slides, self.total, self.D = n, T, parent.D
+        self.C, self.Ce, self.topj, self.topk = int(C_), int(Ce), parent.topj, parent.topk
+        self.discard_bits = parent.discard_bits
+        self.row_off_host, self._row_off_c, self.row_off, self.x_off = parent.row_off_host, parent._row_off_c, parent.row_off, parent.x_off
+        self.mask, self.kept, self.n_kept, self.kept_rows_host = parent.mask, parent.kept, parent.n_kept, parent.kept_rows_host
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.stats = torch.empty((2 * self.C + 3, T), dtype=torch.float32, device=dev)
+        self.sel_flag = torch.empty(T, dtype=torch.uint8, device=dev)
+        self.sel_idx = torch.empty(T, **i32)
+        self.sel_row = torch.empty(T, dtype=torch.int64, device=dev)
+        self.n_sel = torch.empty(n, **i32)
+        self.cand = torch.empty((2 * self.C + 2, T), dtype=torch.float32, device=dev)
+        self.c = MocBatch.from_buffer_copy(parent.c)
+        self.c.C, self.c.Ce, self.c.flags = self.C, self.Ce, 0
+        self.c.stats, self.c.sel_flag, self.c.sel_idx = ptr(self.stats), ptr(self.sel_flag), ptr(self.sel_idx)
+        self.c.sel_row, self.c.n_sel, self.c.cand = ptr(self.sel_row), ptr(self.n_sel), ptr(self.cand)
+        self.c.n_sel_host = None
+        self.ticket = self.cu_reserved = None
+        self._ws = None
+        self.stats_cache = None
 
 
 def build_stats_cache(X: torch.Tensor, sizes, starts, bank: "Bank", topj: int, topk: int):

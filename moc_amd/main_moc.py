@@ -850,6 +850,29 @@ def _pool_loss_slabs(batch, topks, lab, n):
     return out
 
 
+def _sweep_configs(batch, meta, lab, parts, topks):
+    """evaluation_sweep's loop over a batch whose statistics exist (flags cleared by the score pass): per (topj, discard)
+    of `parts` the selection, the candidates, the meta forward and the pooled logits | loss of every topk, appended to
+    parts[(topj, discard)].  Leaves the batch's topj / discard_bits changed: the caller restores them."""
+    n = batch.n_slides
+    tensors, _ = batch.meta_ws()
+    for ci, (j, d) in enumerate(parts):
+        batch.c.topj, batch.c.discard_bits = j, engine._lib.discard_bits(d)
+        if ci > 0:
+            # the selectors only SET flags: the score pass cleared them for the first configuration, the
+            # sweep clears what the configuration before this one selected
+            batch.sel_flag.zero_()
+        batch.select()
+        batch.gather_candidates()
+        engine.meta_forward(batch, meta, 0, n, engine.eval_use_bits(d), keep_hidden=False)
+        mixed = tensors["mixed"]
+        if batch.C <= 2 or batch.C > 16:
+            slabs = _pool_slabs(mixed, mixed, topks, lab, n, seg_off=batch.row_off, seg_len=batch.n_sel)
+        else:
+            slabs = _pool_loss_slabs(batch, topks, lab, n)
+        parts[(j, d)].append(slabs.cpu())
+
+
 def evaluation_sweep(model, loader, device, args, topjs, topks, discard_sets=None):
     """{(topj, topk, tuple(discard)): evaluation(model, loader, device, args')} for every combination, args' = args with
     those three fields -- the same floats -- from ONE score pass per chunk: the statistics depend on none of the three.  Per
@@ -883,21 +906,7 @@ def evaluation_sweep(model, loader, device, args, topjs, topks, discard_sets=Non
                     batch._n_sel_stale()
                     engine.check(engine.lib().moc_mask_compact(engine.C.byref(batch.c), engine._stream()), "moc_mask_compact")
                     engine.check(engine.lib().moc_scores(engine.C.byref(batch.c), engine.ptr(bank.image), engine._stream()), "moc_scores")
-                    for ci, (j, d) in enumerate(parts):
-                        batch.c.topj, batch.c.discard_bits = j, engine._lib.discard_bits(d)
-                        if ci > 0:
-                            # the selectors only SET flags: the score pass cleared them for the first configuration, the
-                            # sweep clears what the configuration before this one selected
-                            batch.sel_flag.zero_()
-                        batch.select()
-                        batch.gather_candidates()
-                        engine.meta_forward(batch, meta, 0, n, engine.eval_use_bits(d), keep_hidden=False)
-                        mixed = tensors["mixed"]
-                        if batch.C <= 2 or batch.C > 16:
-                            slabs = _pool_slabs(mixed, mixed, topks, lab, n, seg_off=batch.row_off, seg_len=batch.n_sel)
-                        else:
-                            slabs = _pool_loss_slabs(batch, topks, lab, n)
-                        parts[(j, d)].append(slabs.cpu())
+                    _sweep_configs(batch, meta, lab, parts, topks)
                 finally:
                     batch.c.topj, batch.c.discard_bits, batch.c.flags = keep
                     batch._n_sel_stale()
@@ -966,6 +975,233 @@ def zs_evaluation_sweep(loader, device, args, topks, pooling_funcs=ZS_POOLING_FU
             out[(f.__name__, k)] = _metrics(allv[i, :, :-1].contiguous(), labels, allv[i, :, -1].tolist(), len(loader.dataset),
                                             real_len, args)
     return out
+
+
+# ---- bank sweeps: several prompt banks of one class count from ONE read of the bags per group of banks ------------------
+_ZS_KINDS = {topj_pooling: "topj", delta_softmax_classifier_pooling: "delta_softmax",
+             delta_diff_classifier_pooling: "delta_diff", bottomk_irrel_classifier_pooling: "bottomk"}
+
+
+def _zs_columns(st, C_, kind):
+    """(keys, vals, smallest, key_shared) of a fused zero-shot pooling function over the full statistics layout."""
+    if kind == "topj":
+        return st[:C_], st[:C_], False, False
+    if kind == "delta_softmax":
+        return st[C_:2 * C_], st[:C_], False, False
+    if kind == "delta_diff":
+        return st[2 * C_:2 * C_ + 1], st[:C_], False, True
+    return st[2 * C_ + 1:2 * C_ + 2], st[:C_], True, True      # bottomk: K rows of smallest background mass
+
+
+def _bank_checks(who, loader, banks):
+    """The refusals of the bank forms, before any launch -> the banks as (W, W_ext) tuples."""
+    assert isinstance(loader, ResidentBags), f"{who}: resident splits only (main_moc.ResidentBags)"
+    assert not loader.loader_seed_draw, f"{who}: loader_seed_draw splits are not swept"
+    banks = [(b[0], b[1]) for b in banks]
+    assert banks, f"{who}: no bank given"
+    Cs = sorted({int(W.size(1)) for W, _ in banks})
+    assert len(Cs) == 1, f"{who}: banks of different C ({Cs}) do not share a score pass; group them by class count"
+    for g, (W, We) in enumerate(banks):
+        assert W.dim() == 2 and We.dim() == 2 and W.size(0) == We.size(0) == loader.X.size(1), f"{who}: bank {g}: bad shapes"
+        assert We.size(1) <= engine.BANK_SET_MAX_CE, \
+            (f"{who}: bank {g} has Ce={We.size(1)} columns; the multi-bank score pass takes banks of at most "
+             f"{engine.BANK_SET_MAX_CE} (one n-tile each) -- wide banks keep zs_evaluation / evaluation per bank")
+    return banks
+
+
+def _chunks_banks(sizes, D, itemsize, n_banks, C_):
+    """_chunks for a pass over `n_banks` banks: MAX_BATCH_BYTES bounds a chunk's bags once and, separately, its per-bank
+    work arrays n_banks times (engine.bank_work_row_bytes a row and bank).  Pure."""
+    per_row_work = n_banks * engine.bank_work_row_bytes(C_)
+    out, cur, bag_b, work_b = [], [], 0, 0
+    for i, n in enumerate(sizes):
+        nb, nw = n * D * itemsize, n * per_row_work
+        if cur and (bag_b + nb > MAX_BATCH_BYTES or work_b + nw > MAX_BATCH_BYTES):
+            out.append(cur)
+            cur, bag_b, work_b = [], 0, 0
+        cur.append(i)
+        bag_b += nb
+        work_b += nw
+    if cur:
+        out.append(cur)
+    return out
+
+
+def _bank_batches(loader, device, args, entries, discard):
+    """Per chunk of the split: (one scored light batch per entry of the bank set, device labels, label list)."""
+    X, sizes, x_starts, labels = _collect(loader, device, args)
+    bank_set = engine.BankSet(entries, X.dtype, device)
+    for ids in _chunks_banks(sizes, X.size(1), X.element_size(), bank_set.n_banks, bank_set.C):
+        parent = _sub_batch(X, sizes, x_starts, ids, bank_set.C, bank_set.Ce[0], args.topj, args.topk, discard)
+        views = parent.scores_banks(bank_set)
+        lab_list = [labels[i] for i in ids]
+        yield views, torch.tensor(lab_list, dtype=torch.int64).to(device, non_blocking=True), lab_list
+
+
+def _ext_is_fg(W, We):
+    return bool(torch.equal(We[:, :W.size(1)].to(device=W.device, dtype=torch.float32), W.to(torch.float32)))
+
+
+def zs_evaluation_banks(loader, device, args, banks, pooling_func=topj_pooling):
+    """[zs_evaluation(loader, device, args, pooling_func) after set_classifier_bank(*banks[g]) for every g] -- the same
+    floats -- from one read of the bags per group of banks (engine.BankSet: banks of one class count, at most 16 columns
+    each).  The four fused pooling functions; the module's bank globals are not touched."""
+    banks = _bank_checks("zs_evaluation_banks", loader, banks)
+    assert pooling_func in _ZS_KINDS, "zs_evaluation_banks: only the four fused pooling functions (others: zs_evaluation per bank)"
+    kind = _ZS_KINDS[pooling_func]
+    entries = [(W, We, kind == "bottomk") for W, We in banks]        # (zs_evaluation's own image for this function)
+    outs, labels = [[] for _ in banks], []
+    with torch.no_grad():
+        real_len = loader.dataset.real_len()
+        set_len = loader.dataset.repeat_num
+        loader.dataset.repeat_num = real_len
+        try:
+            for views, lab, lab_list in _bank_batches(loader, device, args, entries, []):
+                for g, v in enumerate(views):
+                    tensors, _ = v.meta_ws()
+                    keys, vals, small, shared = _zs_columns(v.stats, v.C, kind)
+                    p = engine.topk_mean(keys, vals, args.topk, smallest=small, key_shared=shared, seg_off=v.row_off)
+                    tensors["pooled"].copy_(p)
+                    engine.loss_only(v, lab, 0, v.n_slides)
+                    outs[g].append(torch.cat([tensors["pooled"], tensors["loss"].unsqueeze(1)], 1).cpu())
+                labels.extend(lab_list)
+        finally:
+            loader.dataset.repeat_num = set_len
+    res = []
+    for parts in outs:
+        allv = torch.cat(parts, 0)
+        res.append(_metrics(allv[:, :-1].contiguous(), labels, allv[:, -1].tolist(), len(loader.dataset), real_len, args))
+    return res
+
+
+def zs_evaluation_sweep_banks(loader, device, args, banks, topks, pooling_funcs=ZS_POOLING_FUNCS):
+    """[zs_evaluation_sweep(loader, device, args, topks, pooling_funcs) under banks[g] for every g] -- the same floats --
+    from one read of the bags per group of banks.  For bottomk_irrel_classifier_pooling under a bank whose
+    W_ext[:, :C] is not W, the fg_from_ext image is one more entry of the set, not a pass of its own."""
+    topks = _sweep_checks("zs_evaluation_sweep_banks", loader, topks)
+    banks = _bank_checks("zs_evaluation_sweep_banks", loader, banks)
+    funcs = list(pooling_funcs)
+    assert funcs and all(f in _ZS_KINDS for f in funcs), \
+        "zs_evaluation_sweep_banks: only the four fused pooling functions (others: zs_evaluation, one call each)"
+    entries, jobs = [], []                                          # jobs: (entry, bank, its functions)
+    for g, (W, We) in enumerate(banks):
+        own_ext = [f for f in funcs if _ZS_KINDS[f] == "bottomk" and not _ext_is_fg(W, We)]
+        shared = [f for f in funcs if f not in own_ext]
+        for from_ext, fs in ((False, shared), (True, own_ext)):
+            if fs:
+                jobs.append((len(entries), g, fs))
+                entries.append((W, We, from_ext))
+    parts = [{f: [] for f in funcs} for _ in banks]
+    labels = []
+    with torch.no_grad():
+        real_len = loader.dataset.real_len()
+        set_len = loader.dataset.repeat_num
+        loader.dataset.repeat_num = real_len
+        try:
+            for views, lab, lab_list in _bank_batches(loader, device, args, entries, []):
+                for e, g, fs in jobs:
+                    v = views[e]
+                    for f in fs:
+                        keys, vals, small, shared = _zs_columns(v.stats, v.C, _ZS_KINDS[f])
+                        parts[g][f].append(_pool_slabs(keys, vals, topks, lab, v.n_slides, small, shared, seg_off=v.row_off).cpu())
+                labels.extend(lab_list)
+        finally:
+            loader.dataset.repeat_num = set_len
+    res = []
+    for g in range(len(banks)):
+        out = {}
+        for f in funcs:
+            allv = torch.cat(parts[g][f], 1)
+            for i, k in enumerate(topks):
+                out[(f.__name__, k)] = _metrics(allv[i, :, :-1].contiguous(), labels, allv[i, :, -1].tolist(), len(loader.dataset),
+                                                real_len, args)
+        res.append(out)
+    return res
+
+
+def _bank_models(who, models, n_banks):
+    """One model for all banks, or one per bank (checkpoints trained under their own banks) -> a list of n_banks."""
+    if isinstance(models, nn.Module):
+        models = [models]
+    models = list(models)
+    assert len(models) in (1, n_banks), f"{who}: one model, or one per bank ({n_banks}); got {len(models)}"
+    models = models * n_banks if len(models) == 1 else models
+    for m in models:
+        if m.training:
+            m.eval()
+    return models
+
+
+def evaluation_banks(models, loader, device, args, banks):
+    """[evaluation(models[g], loader, device, args) under banks[g] for every g] -- the same floats -- from one read of the
+    bags per group of banks.  `models`: one model, or one per bank."""
+    banks = _bank_checks("evaluation_banks", loader, banks)
+    models = _bank_models("evaluation_banks", models, len(banks))
+    outs, labels = [[] for _ in banks], []
+    with torch.no_grad():
+        real_len = loader.dataset.real_len()
+        set_len = len(loader.dataset)
+        loader.dataset.repeat_num = real_len
+        try:
+            metas = [MetaState(m) for m in models]
+            use = engine.eval_use_bits(args.discard_classifiers)
+            for views, lab, lab_list in _bank_batches(loader, device, args, [(W, We, False) for W, We in banks],
+                                                      args.discard_classifiers):
+                for g, v in enumerate(views):
+                    n = v.n_slides
+                    tensors, _ = v.meta_ws()
+                    # the rest of phase_a(for_eval=True) behind the score pass, then evaluation()'s two launches
+                    v._layout(False, cand_from_stats=engine.CAND_FROM_STATS and v.C > 4)
+                    v.select()
+                    v.gather_candidates()
+                    engine.meta_forward(v, metas[g], 0, n, use, keep_hidden=False)
+                    engine.pool_loss(v, lab, 0, n)
+                    outs[g].append(torch.cat([tensors["pooled"], tensors["loss"].unsqueeze(1)], 1).cpu())
+                labels.extend(lab_list)
+        finally:
+            loader.dataset.repeat_num = set_len
+    res = []
+    for parts in outs:
+        allv = torch.cat(parts, 0)
+        res.append(_metrics(allv[:, :-1].contiguous(), labels, allv[:, -1].tolist(), len(loader.dataset), real_len, args))
+    return res
+
+
+def evaluation_sweep_banks(models, loader, device, args, banks, topjs, topks, discard_sets=None):
+    """[evaluation_sweep(models[g], loader, device, args, topjs, topks, discard_sets) under banks[g] for every g] -- the
+    same floats: per bank, once its statistics exist, evaluation_sweep's own loop."""
+    topks = _sweep_checks("evaluation_sweep_banks", loader, topks)
+    banks = _bank_checks("evaluation_sweep_banks", loader, banks)
+    models = _bank_models("evaluation_sweep_banks", models, len(banks))
+    topjs = [int(j) for j in topjs]
+    assert topjs and min(topjs) >= 1, "evaluation_sweep_banks: topj must be >= 1"
+    sets = [tuple(d) for d in ([args.discard_classifiers or ()] if discard_sets is None else discard_sets)]
+    assert sets, "evaluation_sweep_banks: no discard set given"
+    parts = [{(j, d): [] for j in topjs for d in sets} for _ in banks]
+    labels = []
+    with torch.no_grad():
+        real_len = loader.dataset.real_len()
+        set_len = len(loader.dataset)
+        loader.dataset.repeat_num = real_len
+        try:
+            metas = [MetaState(m) for m in models]
+            for views, lab, lab_list in _bank_batches(loader, device, args, [(W, We, False) for W, We in banks], []):
+                for g, v in enumerate(views):
+                    v._layout(False, cand_from_stats=engine.CAND_FROM_STATS and v.C > 4)
+                    _sweep_configs(v, metas[g], lab, parts[g], topks)
+                labels.extend(lab_list)
+        finally:
+            loader.dataset.repeat_num = set_len
+    res = []
+    for g in range(len(banks)):
+        out = {}
+        for (j, d), chunks in parts[g].items():
+            allv = torch.cat(chunks, 1)
+            for i, k in enumerate(topks):
+                out[(j, k, d)] = _metrics(allv[i, :, :-1].contiguous(), labels, allv[i, :, -1].tolist(), len(loader.dataset),
+                                          real_len, args)
+        res.append(out)
+    return res
 
 
 # plans of evaluation_runs, least recently used first.  A caller that evaluates one fixed set every epoch and a varying

@@ -12,6 +12,12 @@ DIR/sensitivity.csv (one row per cell: kind, topj, topk, discard, loss, acc, auc
 
 The work is main_moc.evaluation_sweep / zs_evaluation_sweep: every cell is exactly what evaluation() / zs_evaluation()
 returns with those arguments.
+
+`--banks NAME=W.pt,W_ext.pt [NAME=...]` adds the prompt-bank axis: every bank (saved tensors [D, C] and [D, Ce], one class
+count, at most 16 columns each) gets the tables above from ONE read of the bags per group of banks
+(main_moc.evaluation_sweep_banks / zs_evaluation_sweep_banks).  `--ckpt` then takes one checkpoint for all banks or exactly
+one per bank, in the banks' order.  DIR/<NAME>/ holds what the sweep writes for that bank alone, DIR/bank_summary.csv one
+row per (bank, cell): the columns of sensitivity.csv behind a `bank` column.
 """
 from __future__ import annotations
 
@@ -54,9 +60,22 @@ def discard_name(d):
     return "+".join(d) if d else "none"
 
 
+def parse_bank(text):
+    """`NAME=W.pt,W_ext.pt` -> (NAME, W.pt, W_ext.pt)."""
+    name, eq, files = str(text).partition("=")
+    parts = files.split(",")
+    if not eq or not name or len(parts) != 2 or not all(parts) or os.sep in name or name in (".", ".."):
+        raise argparse.ArgumentTypeError(f"a bank is NAME=W.pt,W_ext.pt (NAME becomes a directory name), got {text!r}")
+    return name, parts[0], parts[1]
+
+
 def get_args(argv=None):
     p = argparse.ArgumentParser(description="topj x topk x discard sensitivity tables of a MOC checkpoint from one score pass")
-    p.add_argument("--ckpt", default=None, help="a saved senet state_dict (best_model_*.pt); not needed for --zs alone")
+    p.add_argument("--ckpt", default=None, nargs="+",
+                   help="a saved senet state_dict (best_model_*.pt); not needed for --zs alone.  With --banks: one for all "
+                        "banks, or one per bank")
+    p.add_argument("--banks", default=None, nargs="+", type=parse_bank, metavar="NAME=W.pt,W_ext.pt",
+                   help="prompt banks to compare: saved [D, C] and [D, Ce] tensors, one class count, Ce <= 16")
     p.add_argument("--out", required=True, help="output directory (sensitivity.json, sensitivity.csv)")
     p.add_argument("--topjs", type=_int_list, default=None, help="comma-separated topj values, e.g. 100,200,400,800")
     p.add_argument("--topks", type=_int_list, required=True, help=f"comma-separated topk values, each <= {MAX_TOPK}")
@@ -74,6 +93,10 @@ def get_args(argv=None):
     p.add_argument("--bag_dtype", default="fp32", choices=["fp32", "bf16", "fp16"])
     p.add_argument("--disable_tqdm", action="store_true")
     a = p.parse_args(argv)
+    if a.banks is None and a.ckpt is not None:
+        if len(a.ckpt) != 1:
+            p.error("--ckpt takes one checkpoint (several only with --banks: one per bank)")
+        a.ckpt = a.ckpt[0]
     if a.ckpt is None and not a.zs:
         p.error("--ckpt is needed (only --zs alone runs without a checkpoint)")
     if a.ckpt is not None and a.topjs is None:
@@ -104,10 +127,63 @@ def check_args(a):
             raise SystemExit(f"{a.slides}: a sensitivity table needs slide_id and label columns")
     elif not a.split:
         raise SystemExit("the dataset / synthetic modes need --split {train,val,test}")
+    if a.banks is not None:
+        return None                      # (check_bank_args loads the banks' checkpoints)
     if a.ckpt is None:
         return None
     from .predict import load_checkpoints
     return load_checkpoints([a.ckpt])[0]
+
+
+MAX_BANK_CE = 16       # engine.BANK_SET_MAX_CE (kept literal here, as MAX_TOPK is)
+
+
+def check_bank_args(a):
+    """--banks: refusals from the command line and the files alone, before any GPU work -> ([(name, W, W_ext)] host
+    tensors, the checkpoints' state_dicts: none, one, or one per bank)."""
+    names = [n for n, _, _ in a.banks]
+    dup = sorted({n for n in names if names.count(n) > 1})
+    if dup:
+        raise SystemExit(f"--banks: duplicate bank name {dup[0]!r} (a name is its bank's output directory)")
+    for _, fw, fe in a.banks:
+        for f in (fw, fe):
+            if not os.path.isfile(f):
+                raise SystemExit(f"--banks: {f}: no such file")
+    n_ckpt = len(a.ckpt or ())
+    if n_ckpt not in (0, 1, len(a.banks)):
+        raise SystemExit(f"--ckpt: one checkpoint for all banks or one per bank ({len(a.banks)}); got {n_ckpt}")
+    banks = []
+    for name, fw, fe in a.banks:
+        W, We = (torch.load(f, map_location="cpu") for f in (fw, fe))
+        if not (torch.is_tensor(W) and torch.is_tensor(We) and W.dim() == 2 and We.dim() == 2 and W.size(0) == We.size(0)
+                and We.size(1) > W.size(1)):
+            raise SystemExit(f"--banks: {name}: need saved tensors W [D, C] and W_ext [D, Ce] with Ce > C")
+        if We.size(1) > MAX_BANK_CE:
+            raise SystemExit(f"--banks: {name}: Ce={We.size(1)} columns; the bank axis takes banks of at most {MAX_BANK_CE} "
+                             "(wide banks: one plain sweep per bank)")
+        banks.append((name, W.float(), We.float()))
+    Cs = sorted({int(W.size(1)) for _, W, _ in banks})
+    if len(Cs) != 1:
+        raise SystemExit(f"--banks: banks of different C ({Cs}) do not share a score pass; run one sweep per class count")
+    sds = []
+    if n_ckpt:
+        from .predict import load_checkpoints
+        sds = load_checkpoints(list(a.ckpt))
+    return banks, sds
+
+
+def write_bank_summary(out_dir, names, eval_tables=None, zs_tables=None):
+    """DIR/bank_summary.csv: one row per (bank, cell) -- sensitivity.csv's columns behind `bank`, banks in the given order.
+    A pure function of its arguments (no GPU).  -> the rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    rows = []
+    for g, name in enumerate(names):
+        for r in flatten(eval_tables[g] if eval_tables else None, zs_tables[g] if zs_tables else None):
+            rows.append({"bank": name, **r})
+    df = pd.DataFrame(rows, columns=["bank", "kind", "topj", "topk", "discard", "loss", "acc", "auc"])
+    df["topj"] = df["topj"].astype("Int64")
+    df.to_csv(os.path.join(out_dir, "bank_summary.csv"), index=False, float_format="%.17g")
+    return rows
 
 
 def flatten(eval_table=None, zs_table=None):
@@ -147,6 +223,7 @@ def write_sensitivity(out_dir, eval_table=None, zs_table=None, info=None):
 def cli(argv=None):
     a = get_args(argv)
     sd = check_args(a)
+    bank_files = check_bank_args(a) if a.banks is not None else None
     if not torch.cuda.is_available():
         raise RuntimeError("moc_amd needs a GPU: there is no CPU fallback")
     from . import main_moc as M
@@ -162,6 +239,8 @@ def cli(argv=None):
             setattr(ra, k, getattr(a, k))
         loader = run_moc.prepare(ra, device)[SPLITS.index(a.split)]
         a.n_classes = ra.n_classes
+    if bank_files is not None:
+        return _cli_banks(a, M, loader, device, *bank_files)
     eval_table = zs_table = None
     if sd is not None:
         D = int(sd["model.0.weight"].shape[-1])
@@ -177,6 +256,32 @@ def cli(argv=None):
     n = len(eval_table or {}) + len(zs_table or {})
     print(f"sweep: {n} cells over {len(loader.dataset)} slides -> {a.out}")
     return eval_table, zs_table
+
+
+def _cli_banks(a, M, loader, device, banks, sds):
+    """The --banks run: -> ({name: evaluation table} or None, {name: zero-shot table} or None)."""
+    names = [n for n, _, _ in banks]
+    tensors = [(W.to(device), We.to(device)) for _, W, We in banks]
+    eval_tables = zs_tables = None
+    if sds:
+        models = []
+        for sd in sds:
+            m = M.senet(int(sd["model.0.weight"].shape[-1]), 4).to(device)
+            m.load_state_dict(sd)
+            models.append(m)
+        eval_tables = M.evaluation_sweep_banks(models, loader, device, a, tensors, a.topjs, a.topks, a.discard_sets)
+    if a.zs:
+        zs_tables = M.zs_evaluation_sweep_banks(loader, device, a, tensors, a.topks)
+    info = {k: getattr(a, k) for k in ("slides", "data_dir", "synthetic", "dataset", "shot", "fold", "split", "root",
+                                       "topjs", "topks", "zs", "bag_dtype")}
+    info["discard_sets"] = [discard_name(d) for d in a.discard_sets]
+    for g, (name, fw, fe) in enumerate(a.banks):
+        ck = None if not a.ckpt else a.ckpt[g if len(a.ckpt) > 1 else 0]
+        write_sensitivity(os.path.join(a.out, name), eval_tables[g] if eval_tables else None, zs_tables[g] if zs_tables else None,
+                          dict(info, ckpt=ck, bank=name, bank_files=[fw, fe]))
+    rows = write_bank_summary(a.out, names, eval_tables, zs_tables)
+    print(f"sweep: {len(rows)} cells over {len(names)} banks x {len(loader.dataset)} slides -> {a.out}")
+    return (dict(zip(names, eval_tables)) if eval_tables else None, dict(zip(names, zs_tables)) if zs_tables else None)
 
 
 if __name__ == "__main__":
