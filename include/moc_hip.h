@@ -134,7 +134,8 @@ typedef struct moc_batch {
                                     copy behind phase A whose event has completed), or NULL.  The train steps then take
                                     a slide's S as a kernel argument instead of loading it -- one dependent round trip
                                     less at the head of the forward (arguments -> sel_row -> rows), exact grids, fewer
-                                    record keys per lane in the step.  The same results either way.                   */
+                                    record keys per lane in the step.  The same results either way.  Ignored by
+                                    moc_train_steps_graph: a captured pass serves later passes too, with other counts.  */
 } moc_batch_t;
 
 /* The meta-learner ("senet", main_moc.py:299-312) and its Adam state
@@ -558,6 +559,8 @@ int moc_train_steps(const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws
  *   - all calls on one handle must be ordered on one stream (the counter lives in stream order);
  *   - M->step is read on every call: if it is not where the handle left it (another optimizer stepped, a checkpoint
  *     was loaded), the device counter is put right first; new hyper-parameters or an exhausted table rebuild the table;
+ *   - B->n_sel_host is ignored: a captured pass reads the device n_sel, whichever pass it was captured in (the
+ *     stream-launch fall-back below does use it);
  *   - shapes outside the one-launch steps, n > max_steps, or a runtime that refuses capture / instantiation fall back
  *     to moc_train_steps (moc_step_graph_stats tells which path ran).
  * The caller advances M->step by n afterwards, as with moc_train_steps. */

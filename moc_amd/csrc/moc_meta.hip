@@ -2022,107 +2022,18 @@ int launch_pool(const moc_batch_t* B, const moc_meta_ws_t* ws, int slide0, int n
                                 slide0, n, B->C, B->topk, 0, ws->pooled, ws->topk_idx, ws->topk_cnt, s);
 }
 
-int launch_finish(const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws_t* ws, const int64_t* labels,
-                  int slide0, int n, int train, int apply_adam, uint32_t use_bits, const AdamCoef& k, hipStream_t s) {
-    FinishArgs a = {};
-    a.row_off = B->row_off; a.sel_row = B->sel_row; a.n_sel = B->n_sel; a.cand = B->cand;
-    a.H1 = ws->H1; a.gates = ws->gates; a.pooled = ws->pooled; a.topk_idx = ws->topk_idx; a.topk_cnt = ws->topk_cnt;
-    a.labels = labels; a.loss = ws->loss; a.pred = ws->pred;
-    a.W2 = M->W2; a.b2 = M->b2; a.b1 = M->b1;
-    a.m_W2 = M->m_W2; a.m_b2 = M->m_b2; a.m_b1 = M->m_b1; a.v_W2 = M->v_W2; a.v_b2 = M->v_b2; a.v_b1 = M->v_b1;
-    a.g_W2 = M->g_W2; a.g_b2 = M->g_b2; a.g_b1 = M->g_b1;
-    a.pair_dh = ws->pair_dh; a.pair_row = ws->pair_row; a.n_pair = ws->n_pair;
-    a.stride = B->total_rows; a.C = B->C; a.K = B->topk; a.slide0 = slide0; a.train = train;
-    a.apply_adam = apply_adam; a.use_bits = use_bits; a.adam = k;
-    const size_t smem = train ? (size_t)B->C * B->topk * (4 * sizeof(float) + sizeof(int)) +
-                                (size_t)(FIN_CHUNK + 4) * H * sizeof(float) : 0;
-    MOC_REQUIRE(smem <= 159 * 1024, "finish: C*topk = %d too large", B->C * B->topk);
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)finish_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
-        attr_set = true;
-    }
-    finish_kernel<<<n, 256, smem, s>>>(a);
-    MOC_CHECK_LAUNCH("moc_finish");
-    return MOC_OK;
-}
-
-bool fused_ok(const moc_batch_t* B, int train) {
-    return B->topk <= 16 && B->C <= 16 && s_bound(B) <= 64 * 16 * PS_VPT && (!train || B->C * B->topk <= 64);
-}
-
-// pooling + loss (+ pair gradients and the small-parameter step) for slides [slide0, slide0+n)
-int launch_pool_finish(const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws_t* ws, const int64_t* labels,
-                       int slide0, int n, int train, int apply_adam, uint32_t use_bits, const AdamCoef& k,
-                       hipStream_t s) {
-    if (!fused_ok(B, train)) {
-        if (int rc = launch_pool(B, ws, slide0, n, s)) return rc;
-        return launch_finish(B, M, ws, labels, slide0, n, train, apply_adam, use_bits, k, s);
-    }
-    FinishArgs a = {};
-    a.row_off = B->row_off; a.sel_row = B->sel_row; a.n_sel = B->n_sel; a.cand = B->cand;
-    a.H1 = ws->H1; a.gates = ws->gates; a.pooled = ws->pooled; a.mixed_in = ws->mixed;
-    a.labels = labels; a.loss = ws->loss; a.pred = ws->pred;
-    a.W2 = M->W2; a.b2 = M->b2; a.b1 = M->b1;
-    a.m_W2 = M->m_W2; a.m_b2 = M->m_b2; a.m_b1 = M->m_b1; a.v_W2 = M->v_W2; a.v_b2 = M->v_b2; a.v_b1 = M->v_b1;
-    a.g_W2 = M->g_W2; a.g_b2 = M->g_b2; a.g_b1 = M->g_b1;
-    a.pair_dh = ws->pair_dh; a.pair_row = ws->pair_row; a.n_pair = ws->n_pair;
-    a.stride = B->total_rows; a.C = B->C; a.K = B->topk; a.slide0 = slide0; a.train = train;
-    a.apply_adam = apply_adam; a.use_bits = use_bits; a.adam = k;
-    a.X = (const unsigned char*)B->X; a.D = B->D; a.xdt = B->dtype;   /* storage code: 0 f32, 1 bf16, 2 f16 */
-    a.base_host = -1; a.seg_host = 0;
-    if (n == 1 && B->row_off_host) {
-        a.base_host = B->row_off_host[slide0];
-        a.seg_host = (int)(B->row_off_host[slide0 + 1] - a.base_host);
-    }
-    const size_t C = B->C, K = B->topk, PK = train ? C * K : 0;
-    const int cap = C <= 8 ? PS_CAP_MAX : PS_CAP_MAX / 2;
-    const size_t smem = C * cap * 8 + C * 16 * 8 + C * 4 * 3 + C * K * 4 + PK * (4 * 4 + 2 * H * 4) + 4 * H * 4;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)pool_step_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
-    pool_step_kernel<<<n, 1024, smem, s>>>(a, ws->pooled, ws->topk_idx, ws->topk_cnt, cap);
-    MOC_CHECK_LAUNCH("moc_pool_step");
-    return MOC_OK;
-}
-
+// ---- the step kernels' dynamic LDS, by shape
 size_t fused_step_smem(const moc_batch_t* B, int cap) {
     const size_t C = B->C, K = B->topk, PK = C * K;
     return C * cap * 8 + C * 16 * 8 + C * 4 * 3 + C * K * 4 + PK * (4 * 4 + 2 * H * 4) + 4 * H * 4 + PK * 8 + 16 +
            PK * (size_t)B->D * 4;
 }
-
-// the one-launch step (pool_w1_step_kernel) applies when the pairs' rows fit in LDS
-bool fused_step_ok(const moc_batch_t* B, const moc_meta_ws_t* ws) {
-    if (!fused_ok(B, 1) || !ws->W2_alt) return false;
-    if (B->D > 1024 || (int64_t)B->C * B->topk * B->D > FS_MAX_XS) return false;
-    const int cap = B->C <= 8 ? PS_CAP_MAX : PS_CAP_MAX / 2;
-    return fused_step_smem(B, cap) <= FS_MAX_DYN_LDS;
-}
-
-// the one-launch step over the forward's tile records (pool_w1_step_tiles_kernel): the shapes of pool_w1_step_kernel, when
-// the caller has given the record arrays
 // (+ 1 KiB at the very end: the prefetch's sink)
 constexpr size_t TILES_SINK = 1024;
 size_t tiles_step_smem(const moc_batch_t* B, int cap) {
     const size_t C = B->C, K = B->topk, P = C * K, CL = 64;
     return TILES_SINK + P * 32 + P * 256 * 4 + (P + 4) * 4 + P * 16 + C * cap * 8 + C * 8 + P * 8 + C * CL * 4 + C * 16 * 4 + C * 4 * 4 + P * 4 + P * 4 + 16 + 64;
 }
-}  // namespace
-bool moc_meta_internal::tiles_ok(const moc_batch_t* B, const moc_meta_ws_t* ws) {
-    static const bool off = getenv("MOC_TILE_RECORDS") && atoi(getenv("MOC_TILE_RECORDS")) == 0;   // diagnostic: the round-3 step
-    if (off || !ws->tile_ws || !B->row_off_host || !fused_step_ok(B, ws)) return false;
-    if (moc_cdiv(s_bound(B), 16) * TILE_R > 16 * 64) return false;       // a class's records: at most sixteen keys per lane
-    if (ws->tile_ws_bytes < (int64_t)tile_bytes(tile_slots(B->total_rows, B->n_slides, B->C))) return false;
-    const int cap = B->C <= 8 ? PS_CAP_MAX : PS_CAP_MAX / 2;
-    return tiles_step_smem(B, cap) <= (size_t)FS_MAX_DYN_LDS;
-}
-namespace {
-
-// the wide one-launch step (pool_w1_step_wide_kernel): C <= 64, K <= 16, S <= 8192, every pair's D/16-column
-// piece in LDS
 int wide_cap(const moc_batch_t* B) {
     int cap = 1024;
     while (cap > 64 && (size_t)B->C * cap * 8 > 64 * 1024) cap >>= 1;
@@ -2146,33 +2057,125 @@ int wide_pch(const moc_batch_t* B) {
     while (pch > WD_PCH_MIN && wide_smem(B, pch) > (size_t)FS_MAX_DYN_LDS) pch -= 32;
     return pch < WD_PCH_MIN ? WD_PCH_MIN : pch;
 }
-bool fused_wide_ok(const moc_batch_t* B, const moc_meta_ws_t* ws) {
-    if (!ws->W2_alt || B->topk > 16 || B->C > 64) return false;      // (S > 8192: pooling by topk_mean_kernel first)
-    if (B->D % 512 != 0 || B->D > 1024) return false;        // D/16 = 32 or 64 columns per workgroup
-    return wide_smem(B, WD_PCH_MIN) <= (size_t)FS_MAX_DYN_LDS;
+}  // namespace
+
+// The ONE place that says which step kernel a shape gets, and why.
+StepPlan moc_meta_internal::step_plan(const moc_batch_t* B, const moc_meta_ws_t* ws, bool exchange, int train) {
+    static const bool tiles_off = getenv("MOC_TILE_RECORDS") && atoi(getenv("MOC_TILE_RECORDS")) == 0;   // diagnostic: the round-3 step
+    StepPlan p = {};
+    const int sb = s_bound(B);
+    p.cap = B->C <= 8 ? PS_CAP_MAX : PS_CAP_MAX / 2;
+    p.pool_one = B->topk <= 16 && B->C <= 16 && sb <= 64 * 16 * PS_VPT && (!train || B->C * B->topk <= 64);
+    if (!train || !ws->W2_alt) return p;                    // the one-launch steps ping-pong W2
+    const size_t lds = FS_MAX_DYN_LDS, narrow = fused_step_smem(B, p.cap), tiles = tiles_step_smem(B, p.cap);
+    // narrow (pool_w1_step_kernel): pool_step_kernel's shapes, when the pairs' rows fit in LDS
+    if (p.pool_one && B->D <= 1024 && (int64_t)B->C * B->topk * B->D <= FS_MAX_XS && narrow <= lds) {
+        p.kind = STEP_NARROW; p.smem = narrow;
+        // over the forward's tile records (pool_w1_step_tiles_kernel): the caller has given the record arrays, a class's
+        // records are at most sixteen keys per lane; its workgroups exchange nothing
+        const bool records = ws->tile_ws && B->row_off_host &&
+                             ws->tile_ws_bytes >= (int64_t)tile_bytes(tile_slots(B->total_rows, B->n_slides, B->C));
+        if (!exchange && !tiles_off && records && moc_cdiv(sb, 16) * TILE_R <= 16 * 64 && tiles <= lds) {
+            p.kind = STEP_TILES; p.smem = tiles;
+        }
+        return p;
+    }
+    // wide (pool_w1_step_wide_kernel): C <= 64, K <= 16, D/16 = 32 or 64 columns per workgroup, every pair's piece in LDS
+    if (B->topk <= 16 && B->C <= 64 && B->D % 512 == 0 && B->D <= 1024 && wide_smem(B, WD_PCH_MIN) <= lds) {
+        p.kind = STEP_WIDE; p.pch = wide_pch(B); p.wide_cap = wide_cap(B);
+        p.wide_region = (int)wide_region(B, p.pch); p.smem = wide_smem(B, p.pch);
+        // pooling inside the kernel: every one of the 16 workgroups ranks all C classes for itself -- fine for a few
+        // ten thousand scores, not for EBRAINS-30's 30 x 7,500 (measured: 88 us against 11.4 + 28 with one workgroup per
+        // class in topk_mean_kernel first); beyond 8,192 rows it does not fit the registers at all
+        p.external = sb > 8192 || (int64_t)B->C * sb > 49152;
+    }
+    return p;
 }
-// 0: three launches, 1: pool_w1_step_kernel, 2: pool_w1_step_wide_kernel
-int fused_step_mode(const moc_batch_t* B, const moc_meta_ws_t* ws) {
-    return fused_step_ok(B, ws) ? 1 : fused_wide_ok(B, ws) ? 2 : 0;
+
+namespace {
+
+// Raises the dynamic-LDS limit of every step kernel that needs it: once per process (the batched runs call the training
+// entries from pool threads) and outside any stream capture -- every entry calls it before its first launch.
+int step_attrs() {
+    static std::once_flag once;
+    static char failed[96] = "";                              // the first kernel whose limit could not be raised, and to what
+    std::call_once(once, [] {
+        auto raise = [](const char* name, const void* f, int bytes) {
+            if (!failed[0] && hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess)
+                snprintf(failed, sizeof(failed), "%s to %d bytes", name, bytes);
+        };
+        raise("finish_kernel", (const void*)finish_kernel, 159 * 1024);
+        raise("pool_step_kernel", (const void*)pool_step_kernel, 160 * 1024);
+        raise("pool_w1_step_kernel", (const void*)pool_w1_step_kernel, FS_MAX_DYN_LDS);
+        raise("pool_w1_step_wide_kernel", (const void*)pool_w1_step_wide_kernel, FS_MAX_DYN_LDS);
+#define MOC_TILES_ATTR(VQ)                                                                                                    \
+        raise("pool_w1_step_tiles_kernel", (const void*)pool_w1_step_tiles_kernel<VQ, TileStepArgs>, FS_MAX_DYN_LDS);        \
+        raise("pool_w1_step_tiles_kernel(runs)", (const void*)pool_w1_step_tiles_kernel<VQ, TileStepArgsRuns>, FS_MAX_DYN_LDS); \
+        raise("pool_w1_step_tiles_kernel(runs_hp)", (const void*)pool_w1_step_tiles_kernel<VQ, TileStepArgsRunsHp>, FS_MAX_DYN_LDS)
+        MOC_TILES_ATTR(4); MOC_TILES_ATTR(8); MOC_TILES_ATTR(12); MOC_TILES_ATTR(16);
+#undef MOC_TILES_ATTR
+    });
+    if (failed[0]) MOC_FAIL(MOC_ELAUNCH, "moc_fused_step: cannot raise the dynamic LDS limit of %s", failed);
+    return MOC_OK;
+}
+
+// what finish_kernel, pool_step_kernel and the one-launch steps all read; each launcher adds only its own fields
+FinishArgs finish_args(const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws_t* ws, const int64_t* labels, int slide0,
+                       int train, int apply_adam, uint32_t use_bits, const AdamCoef& k) {
+    FinishArgs a = {};
+    a.row_off = B->row_off; a.sel_row = B->sel_row; a.n_sel = B->n_sel; a.cand = B->cand;
+    a.H1 = ws->H1; a.gates = ws->gates; a.pooled = ws->pooled;
+    a.labels = labels; a.loss = ws->loss; a.pred = ws->pred;
+    a.W2 = M->W2; a.b2 = M->b2; a.b1 = M->b1;
+    a.m_W2 = M->m_W2; a.m_b2 = M->m_b2; a.m_b1 = M->m_b1; a.v_W2 = M->v_W2; a.v_b2 = M->v_b2; a.v_b1 = M->v_b1;
+    a.g_W2 = M->g_W2; a.g_b2 = M->g_b2; a.g_b1 = M->g_b1;
+    a.stride = B->total_rows; a.C = B->C; a.K = B->topk; a.slide0 = slide0; a.train = train;
+    a.apply_adam = apply_adam; a.use_bits = use_bits; a.adam = k;
+    return a;
+}
+// ... and of the kernels that pool for themselves: the scores, the rows, and one slide's extent where the host knows it
+void finish_rows(FinishArgs& a, const moc_batch_t* B, const moc_meta_ws_t* ws, int slide, bool one_slide) {
+    a.mixed_in = ws->mixed;
+    a.X = (const unsigned char*)B->X; a.D = B->D; a.xdt = B->dtype;   /* storage code: 0 f32, 1 bf16, 2 f16 */
+    a.base_host = -1; a.seg_host = 0;
+    if (one_slide && B->row_off_host) {
+        a.base_host = B->row_off_host[slide];
+        a.seg_host = (int)(B->row_off_host[slide + 1] - a.base_host);
+    }
+}
+
+int launch_finish(const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws_t* ws, const int64_t* labels,
+                  int slide0, int n, int train, int apply_adam, uint32_t use_bits, const AdamCoef& k, hipStream_t s) {
+    FinishArgs a = finish_args(B, M, ws, labels, slide0, train, apply_adam, use_bits, k);
+    a.topk_idx = ws->topk_idx; a.topk_cnt = ws->topk_cnt;
+    a.pair_dh = ws->pair_dh; a.pair_row = ws->pair_row; a.n_pair = ws->n_pair;
+    const size_t smem = train ? (size_t)B->C * B->topk * (4 * sizeof(float) + sizeof(int)) +
+                                (size_t)(FIN_CHUNK + 4) * H * sizeof(float) : 0;
+    MOC_REQUIRE(smem <= 159 * 1024, "finish: C*topk = %d too large", B->C * B->topk);
+    finish_kernel<<<n, 256, smem, s>>>(a);
+    MOC_CHECK_LAUNCH("moc_finish");
+    return MOC_OK;
+}
+
+// pooling + loss (+ pair gradients and the small-parameter step) for slides [slide0, slide0+n)
+int launch_pool_finish(const StepPlan& p, const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws_t* ws, const int64_t* labels,
+                       int slide0, int n, int train, int apply_adam, uint32_t use_bits, const AdamCoef& k, hipStream_t s) {
+    if (!p.pool_one) {
+        if (int rc = launch_pool(B, ws, slide0, n, s)) return rc;
+        return launch_finish(B, M, ws, labels, slide0, n, train, apply_adam, use_bits, k, s);
+    }
+    FinishArgs a = finish_args(B, M, ws, labels, slide0, train, apply_adam, use_bits, k);
+    finish_rows(a, B, ws, slide0, n == 1);
+    a.pair_dh = ws->pair_dh; a.pair_row = ws->pair_row; a.n_pair = ws->n_pair;
+    const size_t C = B->C, K = B->topk, PK = train ? C * K : 0;
+    const size_t smem = C * p.cap * 8 + C * 16 * 8 + C * 4 * 3 + C * K * 4 + PK * (4 * 4 + 2 * H * 4) + 4 * H * 4;
+    pool_step_kernel<<<n, 1024, smem, s>>>(a, ws->pooled, ws->topk_idx, ws->topk_cnt, p.cap);
+    MOC_CHECK_LAUNCH("moc_pool_step");
+    return MOC_OK;
 }
 
 // device-resident Adam coefficients for graph replay: the step's coefficients are tab[ctr[0] + pos]
 struct StepTab { const AdamCoef* tab; const int32_t* ctr; int pos; };
-
-void fused_step_attrs() {
-    // (outside any stream capture: raise the dynamic LDS limits of the two one-launch step kernels once)
-    static bool done = false;
-    if (done) return;
-    (void)hipFuncSetAttribute((const void*)pool_w1_step_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, FS_MAX_DYN_LDS);
-    (void)hipFuncSetAttribute((const void*)pool_w1_step_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, FS_MAX_DYN_LDS);
-#define MOC_TILES_ATTR(VQ)                                                                                                         \
-    (void)hipFuncSetAttribute((const void*)pool_w1_step_tiles_kernel<VQ, TileStepArgs>, hipFuncAttributeMaxDynamicSharedMemorySize, FS_MAX_DYN_LDS); \
-    (void)hipFuncSetAttribute((const void*)pool_w1_step_tiles_kernel<VQ, TileStepArgsRuns>, hipFuncAttributeMaxDynamicSharedMemorySize, FS_MAX_DYN_LDS); \
-    (void)hipFuncSetAttribute((const void*)pool_w1_step_tiles_kernel<VQ, TileStepArgsRunsHp>, hipFuncAttributeMaxDynamicSharedMemorySize, FS_MAX_DYN_LDS)
-    MOC_TILES_ATTR(4); MOC_TILES_ATTR(8); MOC_TILES_ATTR(12); MOC_TILES_ATTR(16);
-#undef MOC_TILES_ATTR
-    done = true;
-}
 
 // the argument block of pool_w1_step_tiles_kernel for slide `slide` of B (one run)
 void tile_region(const moc_batch_t* B, int slide, int64_t* slot0, int* tcap, int* tb) {
@@ -2189,13 +2192,13 @@ void tile_region(const moc_batch_t* B, int slide, int64_t* slot0, int* tcap, int
     *slot0 = ((base >> 4) + slide) * (int64_t)B->C * TILE_R;
 }
 
-TileStepArgs tile_step_args(const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws_t* ws, const int64_t* labels, int slide,
+TileStepArgs tile_step_args(const StepPlan& p, const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws_t* ws, const int64_t* labels, int slide,
                             uint32_t use_bits, const AdamCoef& k, float* W2out, int apply_adam, const StepTab* tab) {
     const TileWs T = tile_carve(ws->tile_ws, tile_slots(B->total_rows, B->n_slides, B->C));
     TileStepArgs ta = {};
     ta.tkey = T.key; ta.trho = T.rho; ta.trid = T.rid; ta.tlam = T.lam; ta.tsc = T.sc;
     tile_region(B, slide, &ta.slot0, &ta.cap, &ta.ntile_bound);
-    ta.C = B->C; ta.K = B->topk; ta.D = B->D; ta.slide0 = slide; ta.PS_CAP = B->C <= 8 ? PS_CAP_MAX : PS_CAP_MAX / 2;
+    ta.C = B->C; ta.K = B->topk; ta.D = B->D; ta.slide0 = slide; ta.PS_CAP = p.cap;
     ta.xdt = B->dtype; ta.n_sel = B->n_sel; ta.labels = labels;
     ta.W1 = M->W1; ta.m_W1 = M->m_W1; ta.v_W1 = M->v_W1; ta.W2 = M->W2;
     ta.b1 = M->b1; ta.m_b1 = M->m_b1; ta.v_b1 = M->v_b1; ta.b2 = M->b2; ta.m_b2 = M->m_b2; ta.v_b2 = M->v_b2;
@@ -2203,7 +2206,7 @@ TileStepArgs tile_step_args(const moc_batch_t* B, const moc_meta_t* M, const moc
     ta.base = B->row_off_host[slide]; ta.adam = k;
     ta.row_off = B->row_off; ta.prefetch_next = 0;
     ta.S_host = B->n_sel_host ? B->n_sel_host[slide] : -1;
-    ta.sink_off = (int)(tiles_step_smem(B, ta.PS_CAP) - TILES_SINK);
+    ta.sink_off = (int)(p.smem - TILES_SINK);
     if (tab) { ta.adam_tab = tab->tab; ta.adam_ctr = tab->ctr; ta.adam_pos = tab->pos; }
     ta.apply_adam = apply_adam; ta.use_bits = use_bits; ta.img_dt = B->dtype;
     ta.H1 = ws->H1; ta.X = (const unsigned char*)B->X;
@@ -2218,11 +2221,10 @@ TileStepArgs tile_step_args(const moc_batch_t* B, const moc_meta_t* M, const moc
 // launches it -- for ONE meta-learner (the common argument block alone) or for tr.s.n_runs of them (grid.z; the per-run
 // scalars behind the common block); the largest tile bound of any run picks the keys per lane
 template <typename ArgsT>
-int launch_tile_step_as(const moc_batch_t* B, const ArgsT& args, int runs, int tb, hipStream_t s) {
+int launch_tile_step_as(const StepPlan& p, const moc_batch_t* B, const ArgsT& args, int runs, int tb, hipStream_t s) {
     const TileStepArgs& ta = tile_common(args);
-    const size_t sm = tiles_step_smem(B, ta.PS_CAP);
     const dim3 grid(B->D / 256 + (ta.tail_inside ? 0 : 1), H, runs);   // D / 256 column blocks of W1 (+ the tail workgroup), per hidden unit
-#define MOC_TILES_LAUNCH(VQ) pool_w1_step_tiles_kernel<VQ, ArgsT><<<grid, 256, sm, s>>>(args)
+#define MOC_TILES_LAUNCH(VQ) pool_w1_step_tiles_kernel<VQ, ArgsT><<<grid, 256, p.smem, s>>>(args)
     const int vq = moc_cdiv((int64_t)tb * TILE_R, 64);                 // keys per lane of a class wave
     if (vq <= 4) MOC_TILES_LAUNCH(4);
     else if (vq <= 8) MOC_TILES_LAUNCH(8);
@@ -2232,79 +2234,49 @@ int launch_tile_step_as(const moc_batch_t* B, const ArgsT& args, int runs, int t
     MOC_CHECK_LAUNCH("moc_fused_step(tiles)");
     return MOC_OK;
 }
-int launch_tile_step(const moc_batch_t* B, const TileStepArgs& ta, hipStream_t s) {
-    return launch_tile_step_as(B, ta, 1, ta.ntile_bound, s);
-}
 template <typename RunsT>
-int launch_tile_step_runs(const moc_batch_t* B, const RunsT& tr, hipStream_t s) {
+int launch_tile_step_runs(const StepPlan& p, const moc_batch_t* B, const RunsT& tr, hipStream_t s) {
     int tb = tr.s.ntile_bound;
     for (int r = 0; r < tr.s.n_runs; ++r) tb = tr.ntb_r[r] > tb ? tr.ntb_r[r] : tb;
-    return launch_tile_step_as(B, tr, tr.s.n_runs, tb, s);
+    return launch_tile_step_as(p, B, tr, tr.s.n_runs, tb, s);
 }
 
-// next_slide: the slide the step after this one works on, in the same work arrays (-1: none / unknown) -- the tile-record
-// step pulls its selected rows toward the Infinity Cache
-int launch_fused_step(const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws_t* ws, const int64_t* labels,
+// whether the tile-record step pulls the next slide's selected rows toward the Infinity Cache (diagnostic: MOC_STEP_PREFETCH=0)
+bool step_prefetch_on() {
+    static const bool on = !(getenv("MOC_STEP_PREFETCH") && atoi(getenv("MOC_STEP_PREFETCH")) == 0);
+    return on;
+}
+// The one-launch step of plan p.  next_slide: the slide the step after this one works on, in the same work arrays (-1: none /
+// unknown) -- the tile-record step prefetches its rows.  x: the gradient exchange, which the tile-record kernel has not got.
+int launch_fused_step(const StepPlan& p, const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws_t* ws, const int64_t* labels,
                       int slide, uint32_t use_bits, const AdamCoef& k, float* W2out, hipStream_t s,
                       int apply_adam = 1, const P2pArgs* x = nullptr, const StepTab* tab = nullptr, int next_slide = -1) {
+    MOC_REQUIRE(p.one_launch() && !(p.tiles() && x), "moc_fused_step: plan of kind %d%s", (int)p.kind, x ? " with a gradient exchange" : "");
+    if (p.tiles()) {                                       // over the forward's tile records (the forward was told to leave them)
+        TileStepArgs ta = tile_step_args(p, B, M, ws, labels, slide, use_bits, k, W2out, apply_adam, tab);
+        if (step_prefetch_on() && next_slide == slide + 1 && next_slide < B->n_slides && B->C < 4) ta.prefetch_next = 1;
+        return launch_tile_step_as(p, B, ta, 1, ta.ntile_bound, s);
+    }
     FusedArgs g = {};
     if (x) g.x = *x;
+    g.f = finish_args(B, M, ws, labels, slide, 1, apply_adam, use_bits, k);
     FinishArgs& a = g.f;
+    finish_rows(a, B, ws, slide, true);
     if (tab) { a.adam_tab = tab->tab; a.adam_ctr = tab->ctr; a.adam_pos = tab->pos; }
-    a.row_off = B->row_off; a.sel_row = B->sel_row; a.n_sel = B->n_sel; a.cand = B->cand;
-    a.H1 = ws->H1; a.gates = ws->gates; a.pooled = ws->pooled; a.mixed_in = ws->mixed;
-    a.labels = labels; a.loss = ws->loss; a.pred = ws->pred;
-    a.W2 = M->W2; a.b2 = M->b2; a.b1 = M->b1;
-    a.m_W2 = M->m_W2; a.m_b2 = M->m_b2; a.m_b1 = M->m_b1; a.v_W2 = M->v_W2; a.v_b2 = M->v_b2; a.v_b1 = M->v_b1;
-    a.stride = B->total_rows; a.C = B->C; a.K = B->topk; a.slide0 = slide; a.train = 1;
-    a.apply_adam = apply_adam; a.use_bits = use_bits; a.adam = k;
-    a.g_W2 = M->g_W2; a.g_b2 = M->g_b2; a.g_b1 = M->g_b1; g.g_W1 = M->g_W1;
-    a.X = (const unsigned char*)B->X; a.D = B->D; a.xdt = B->dtype;   /* storage code: 0 f32, 1 bf16, 2 f16 */
-    a.base_host = -1; a.seg_host = 0;
-    if (B->row_off_host) {
-        a.base_host = B->row_off_host[slide];
-        a.seg_host = (int)(B->row_off_host[slide + 1] - a.base_host);
-    }
-    g.W1 = M->W1; g.m_W1 = M->m_W1; g.v_W1 = M->v_W1; g.W1img = (unsigned char*)M->W1_image;
+    g.g_W1 = M->g_W1; g.W1 = M->W1; g.m_W1 = M->m_W1; g.v_W1 = M->v_W1; g.W1img = (unsigned char*)M->W1_image;
     g.W2out = W2out; g.img_dt = B->dtype;
-    if (!fused_step_ok(B, ws)) {                           // wide shapes
-        static bool wide_attr = false;
-        if (!wide_attr) {
-            if (hipFuncSetAttribute((const void*)pool_w1_step_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, FS_MAX_DYN_LDS) != hipSuccess)
-                MOC_FAIL(MOC_ELAUNCH, "moc_fused_step: cannot raise the dynamic LDS limit to %d bytes", FS_MAX_DYN_LDS);
-            wide_attr = true;
-        }
-        // pooling inside the kernel: every one of the 16 workgroups ranks all C classes for itself -- fine for a few
-        // ten thousand scores, not for EBRAINS-30's 30 x 7,500 (measured: 88 us against 11.4 + 28 with one workgroup per
-        // class in topk_mean_kernel first); beyond 8,192 rows it does not fit the registers at all
-        const int external = s_bound(B) > 8192 || (int64_t)B->C * s_bound(B) > 49152;
-        if (external) {
+    if (p.kind == STEP_WIDE) {
+        if (p.external) {                                  // pooling by topk_mean_kernel first
             if (int rc = launch_pool(B, ws, slide, 1, s)) return rc;
             a.topk_idx = ws->topk_idx; a.topk_cnt = ws->topk_cnt;
         }
-        const int pch = wide_pch(B);
-        pool_w1_step_wide_kernel<<<H / 4, 1024, wide_smem(B, pch), s>>>(g, ws->pooled, ws->topk_idx, ws->topk_cnt, wide_cap(B),
-                                                                         (int)wide_region(B, pch), external, pch);
+        pool_w1_step_wide_kernel<<<H / 4, 1024, p.smem, s>>>(g, ws->pooled, ws->topk_idx, ws->topk_cnt, p.wide_cap, p.wide_region,
+                                                             p.external, p.pch);
         MOC_CHECK_LAUNCH("moc_fused_step(wide)");
         return MOC_OK;
     }
-    const int cap = B->C <= 8 ? PS_CAP_MAX : PS_CAP_MAX / 2;
-    if (g.x.world <= 1 && tiles_ok(B, ws)) {               // over the forward's tile records (the forward was told to leave them)
-        fused_step_attrs();
-        TileStepArgs ta = tile_step_args(B, M, ws, labels, slide, use_bits, k, W2out, apply_adam, tab);
-        static const bool prefetch = !(getenv("MOC_STEP_PREFETCH") && atoi(getenv("MOC_STEP_PREFETCH")) == 0);   // diagnostic: off
-        if (prefetch && next_slide == slide + 1 && next_slide < B->n_slides && B->C < 4) ta.prefetch_next = 1;
-        return launch_tile_step(B, ta, s);
-    }
-    const size_t smem = fused_step_smem(B, cap);
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)pool_w1_step_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, FS_MAX_DYN_LDS) != hipSuccess)
-            MOC_FAIL(MOC_ELAUNCH, "moc_fused_step: cannot raise the dynamic LDS limit to %d bytes", FS_MAX_DYN_LDS);
-        attr_set = true;
-    }
     // 32 workgroups of two hidden units each, unless the gradient is exchanged inside the kernel (16 channels)
-    pool_w1_step_kernel<<<g.x.world > 1 ? H / 4 : H / 2, 1024, smem, s>>>(g, ws->pooled, ws->topk_idx, ws->topk_cnt, cap);
+    pool_w1_step_kernel<<<g.x.world > 1 ? H / 4 : H / 2, 1024, p.smem, s>>>(g, ws->pooled, ws->topk_idx, ws->topk_cnt, p.cap);
     MOC_CHECK_LAUNCH("moc_fused_step");
     return MOC_OK;
 }
@@ -2335,9 +2307,10 @@ extern "C" int moc_pool_loss(const moc_batch_t* B, const moc_meta_ws_t* ws, cons
     MOC_REQUIRE(slide0 >= 0 && n >= 1 && slide0 + n <= B->n_slides, "moc_pool_loss: bad slide range");
     MOC_REQUIRE(B->C <= 256, "moc_pool_loss: C > 256");
     hipStream_t s = (hipStream_t)stream;
+    (void)step_attrs();   // (pool_step_kernel's limit is among them; a training kernel's failure is not this entry's error)
     moc_meta_t none = {};
     AdamCoef k = {};
-    return launch_pool_finish(B, &none, ws, labels, slide0, n, 0, 0, 0, k, s);
+    return launch_pool_finish(step_plan(B, ws, false, 0), B, &none, ws, labels, slide0, n, 0, 0, 0, k, s);
 }
 
 extern "C" int moc_ce_loss(const float* pooled, const int64_t* labels, int n, int C, float* loss, int32_t* pred,
@@ -2357,15 +2330,17 @@ extern "C" int moc_train_grad(const moc_batch_t* B, const moc_meta_t* M, const m
     if (int rc = check_meta(B, M, ws, "moc_train_grad", false, true)) return rc;
     MOC_REQUIRE(labels && slide >= 0 && slide < B->n_slides, "moc_train_grad: bad labels/slide");
     hipStream_t s = (hipStream_t)stream;
+    if (int rc = step_attrs()) return rc;
+    const StepPlan p = step_plan(B, ws, false);
     AdamCoef k = {};
     k.grad_scale = 1.f;
     // forward (fresh W1 image: the parameters may have been stepped by moc_adam_step), pooling +
     // loss + pair gradients, W1 gradient -- everything one meta-step does short of the update
     if (int rc = launch_w1_images(B, M, nullptr, s)) return rc;
-    if (int rc = launch_forward(B, M, ws, slide, 1, use_bits, s, true)) return rc;
-    if (fused_step_mode(B, ws)) return launch_fused_step(B, M, ws, labels, slide, use_bits, k, nullptr, s, 0);
-    if (int rc = launch_pool_finish(B, M, ws, labels, slide, 1, 1, 0, use_bits, k, s)) return rc;
-    return launch_w1(B, M, ws, 0, k, s, fused_ok(B, 1));
+    if (int rc = launch_forward(B, M, ws, slide, 1, use_bits, s, p.tiles())) return rc;
+    if (p.one_launch()) return launch_fused_step(p, B, M, ws, labels, slide, use_bits, k, nullptr, s, 0);
+    if (int rc = launch_pool_finish(p, B, M, ws, labels, slide, 1, 1, 0, use_bits, k, s)) return rc;
+    return launch_w1(B, M, ws, 0, k, s, p.pool_one);
 }
 
 extern "C" int moc_senet_backward(const void* X, int dtype, int64_t S, int D, const float* H1, const float* gates,
@@ -2415,19 +2390,20 @@ extern "C" int moc_train_steps_dp(const moc_batch_t* B, const moc_meta_t* M, con
                                M->g_W1 + (int64_t)H * M->D <= grad_flat + grad_count),
                 "moc_train_steps_dp: the gradient tensors must live in grad_flat[%lld]", (long long)grad_count);
     hipStream_t s = (hipStream_t)stream;
+    if (int rc = step_attrs()) return rc;
+    const StepPlan p = step_plan(B, ws, false);
     if (int rc = launch_w1_images(B, M, nullptr, s)) return rc;      // afterwards the Adam kernel keeps it in sync
-    const bool fused = fused_step_mode(B, ws) != 0;
     const int img_dt = B->dtype;
     AdamCoef kg = {};
     kg.grad_scale = 1.f;
     for (int t = 0; t < n; ++t) {
         const int b = slide0 + t;
-        if (int rc = launch_forward(B, M, ws, b, 1, use_bits, s, fused)) return rc;
-        if (fused) {
-            if (int rc = launch_fused_step(B, M, ws, labels, b, use_bits, kg, nullptr, s, 0)) return rc;
+        if (int rc = launch_forward(B, M, ws, b, 1, use_bits, s, p.tiles())) return rc;
+        if (p.one_launch()) {
+            if (int rc = launch_fused_step(p, B, M, ws, labels, b, use_bits, kg, nullptr, s, 0)) return rc;
         } else {
-            if (int rc = launch_pool_finish(B, M, ws, labels, b, 1, 1, 0, use_bits, kg, s)) return rc;
-            if (int rc = launch_w1(B, M, ws, 0, kg, s, fused_ok(B, 1))) return rc;
+            if (int rc = launch_pool_finish(p, B, M, ws, labels, b, 1, 1, 0, use_bits, kg, s)) return rc;
+            if (int rc = launch_w1(B, M, ws, 0, kg, s, p.pool_one)) return rc;
         }
         if (allreduce) {   // the ONE collective of a step: sum of the flat gradient over the ranks
             const int rc = allreduce(grad_flat, grad_flat, (size_t)grad_count, 7 /* ncclFloat32 */, 0 /* ncclSum */, comm, stream);
@@ -2447,7 +2423,7 @@ extern "C" int moc_p2p_step_supported(int C, int topk, int D, int topj) {
     moc_meta_ws_t ws = {};
     float dummy;
     ws.W2_alt = &dummy;
-    return C >= 1 && topk >= 1 && D >= 1 && topj >= 1 && fused_step_mode(&B, &ws) != 0 ? 1 : 0;
+    return C >= 1 && topk >= 1 && D >= 1 && topj >= 1 && step_plan(&B, &ws, true).one_launch() ? 1 : 0;
 }
 
 extern "C" int moc_train_steps_p2p(const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws_t* ws,
@@ -2459,12 +2435,15 @@ extern "C" int moc_train_steps_p2p(const moc_batch_t* B, const moc_meta_t* M, co
     MOC_REQUIRE(comm, "moc_train_steps_p2p: null communicator");
     // Which step kernel runs is decided from the run's constants alone (as moc_p2p_step_supported does), never from
     // this rank's bag sizes: the narrow and the wide kernel assign W1 elements to workgroups differently, and the
-    // per-workgroup arrival flags of the exchange only mean something when every rank runs the same one.
+    // per-workgroup arrival flags of the exchange only mean something when every rank runs the same one.  (An exchange
+    // plan is never the tile-record kind, at any world size: the forward below leaves no records.)
     moc_batch_t Bu = *B;
     Bu.max_rows = 0x7fffffff;
-    MOC_REQUIRE(fused_step_mode(&Bu, ws) != 0, "moc_train_steps_p2p: shape outside the one-launch steps (K <= 16, C <= 64, "
+    const StepPlan p = step_plan(&Bu, ws, true);
+    MOC_REQUIRE(p.one_launch(), "moc_train_steps_p2p: shape outside the one-launch steps (K <= 16, C <= 64, "
                 "D in {512, 1024} beyond C = 16); use moc_train_steps_dp");
     hipStream_t s = (hipStream_t)stream;
+    if (int rc = step_attrs()) return rc;
     if (int rc = launch_w1_images(B, M, nullptr, s)) return rc;
     moc_meta_t Mt = *M;
     float* cur = M->W2;
@@ -2478,7 +2457,7 @@ extern "C" int moc_train_steps_p2p(const moc_batch_t* B, const moc_meta_t* M, co
         const AdamCoef k = adam_coef(M, M->step + 1 + t, 1.f / (float)x.world);
         Mt.W2 = cur;
         if (int rc = launch_forward(B, &Mt, ws, b, 1, use_bits, s)) return rc;
-        if (int rc = launch_fused_step(&Bu, &Mt, ws, labels, b, use_bits, k, nxt, s, 1, &x)) return rc;
+        if (int rc = launch_fused_step(p, &Bu, &Mt, ws, labels, b, use_bits, k, nxt, s, 1, &x)) return rc;
         float* tmp = cur; cur = nxt; nxt = tmp;
     }
     if (cur != M->W2) {
@@ -2490,7 +2469,7 @@ extern "C" int moc_train_steps_p2p(const moc_batch_t* B, const moc_meta_t* M, co
 
 struct moc_step_graph;
 namespace {
-int issue_fused_pass(const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws_t* ws, const int64_t* labels,
+int issue_fused_pass(const StepPlan& p, const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws_t* ws, const int64_t* labels,
                      int slide0, int n, uint32_t use_bits, hipStream_t s, const moc_step_graph* G);
 }
 
@@ -2501,14 +2480,16 @@ extern "C" int moc_train_steps(const moc_batch_t* B, const moc_meta_t* M, const 
     if (int rc = check_meta(B, M, ws, "moc_train_steps", true, false)) return rc;
     MOC_REQUIRE(labels && slide0 >= 0 && n >= 1 && slide0 + n <= B->n_slides, "moc_train_steps: bad labels/slide range");
     hipStream_t s = (hipStream_t)stream;
-    if (fused_step_mode(B, ws)) return issue_fused_pass(B, M, ws, labels, slide0, n, use_bits, s, nullptr);
+    if (int rc = step_attrs()) return rc;
+    const StepPlan p = step_plan(B, ws, false);
+    if (p.one_launch()) return issue_fused_pass(p, B, M, ws, labels, slide0, n, use_bits, s, nullptr);
     if (int rc = launch_w1_images(B, M, nullptr, s)) return rc;      // afterwards the W1 update keeps it in sync
     for (int t = 0; t < n; ++t) {
         const int b = slide0 + t;
         const AdamCoef k = adam_coef(M, M->step + 1 + t, 1.f);
         if (int rc = launch_forward(B, M, ws, b, 1, use_bits, s)) return rc;
-        if (int rc = launch_pool_finish(B, M, ws, labels, b, 1, 1, 1, use_bits, k, s)) return rc;
-        if (int rc = launch_w1(B, M, ws, 1, k, s, fused_ok(B, 1))) return rc;
+        if (int rc = launch_pool_finish(p, B, M, ws, labels, b, 1, 1, 1, use_bits, k, s)) return rc;
+        if (int rc = launch_w1(B, M, ws, 1, k, s, p.pool_one)) return rc;
     }
     return MOC_OK;
 }
@@ -2520,8 +2501,19 @@ extern "C" int moc_train_steps(const moc_batch_t* B, const moc_meta_t* M, const 
 // parameters, Adam moments; the same kernels, the same operation order: bit-identical to running it alone.
 extern "C" int moc_train_runs_mode(const moc_batch_t* B, const moc_meta_ws_t* ws) {
     if (!B || !ws) return 0;
-    if (tiles_ok(B, ws)) return 1;
-    return fused_step_mode(B, ws) != 0 ? 2 : 0;
+    const StepPlan p = step_plan(B, ws, false);
+    return p.tiles() ? 1 : p.one_launch() ? 2 : 0;
+}
+
+// M advanced to run r: every tensor by r * par_stride, the W1 image by r * image_stride
+static moc_meta_t meta_of_run(const moc_meta_t* M, const moc_runs_t* R, int r) {
+    moc_meta_t Mr = *M;
+    const int64_t po = (int64_t)r * R->par_stride;
+    Mr.W1 += po; Mr.b1 += po; Mr.W2 += po; Mr.b2 += po;
+    Mr.m_W1 += po; Mr.m_b1 += po; Mr.m_W2 += po; Mr.m_b2 += po;
+    Mr.v_W1 += po; Mr.v_b1 += po; Mr.v_W2 += po; Mr.v_b2 += po;
+    Mr.W1_image = (unsigned char*)M->W1_image + (int64_t)r * R->image_stride;
+    return Mr;
 }
 
 // `hp` == nullptr: the runs share M's hyper-parameters (moc_train_steps_runs: one AdamCoef per launch, the argument block
@@ -2537,35 +2529,31 @@ static int train_steps_runs(const moc_batch_t* B, const moc_meta_t* M, const moc
     MOC_REQUIRE(R->par_stride >= (int64_t)H * B->D + H + 4 * H + 4 && R->image_stride >= (int64_t)moc_w1_image_bytes(B->D, B->dtype),
                 "%s: parameter / image stride smaller than one meta-learner", who);
     hipStream_t s = (hipStream_t)stream;
+    if (int rc = step_attrs()) return rc;
+    const StepPlan p = step_plan(B, ws, false);
     // run r's hyper-parameters as a moc_meta_t that adam_coef reads: M's, or record r
     auto with_hp = [&](moc_meta_t& Mr, int r) {
         if (!hp) return;
         Mr.lr = hp[r].lr; Mr.beta1 = hp[r].beta1; Mr.beta2 = hp[r].beta2; Mr.eps = hp[r].eps; Mr.weight_decay = hp[r].weight_decay;
     };
-    if (!tiles_ok(B, ws)) {
+    if (!p.tiles()) {
         // Shapes outside the tile-record step (wide banks: EBRAINS-30, the 64-way shape; C > 16, C K > 64, more than 4,096
         // selectable rows): every run's pass through moc_train_steps' own launches, one run after the other on this stream --
         // the same kernels on the same tensors as the run alone, so the same bits.  What the caller still gains is phase A
         // over all runs' slides in one pass and (moc_amd.runs: one group per run) the runs' chains side by side on streams
         // of their own, each of which keeps a few dozen CUs busy.  The one-launch steps only (W2_alt set): the three-launch
         // step's scratch is one per batch.
-        MOC_REQUIRE(fused_step_mode(B, ws) != 0, "%s: this shape needs ws->W2_alt (the one-launch steps)", who);
+        MOC_REQUIRE(p.one_launch(), "%s: this shape needs ws->W2_alt (the one-launch steps)", who);
         for (int r = 0; r < R->n_runs; ++r) {
-            moc_meta_t Mr = *M;
+            moc_meta_t Mr = meta_of_run(M, R, r);
             with_hp(Mr, r);
-            const int64_t po = (int64_t)r * R->par_stride;
-            Mr.W1 += po; Mr.b1 += po; Mr.W2 += po; Mr.b2 += po;
-            Mr.m_W1 += po; Mr.m_b1 += po; Mr.m_W2 += po; Mr.m_b2 += po;
-            Mr.v_W1 += po; Mr.v_b1 += po; Mr.v_W2 += po; Mr.v_b2 += po;
             Mr.g_W1 = Mr.g_b1 = Mr.g_W2 = Mr.g_b2 = nullptr;
-            Mr.W1_image = (unsigned char*)M->W1_image + (int64_t)r * R->image_stride;
             moc_meta_ws_t wr = *ws;
-            wr.W2_alt = ws->W2_alt + (int64_t)r * 4 * H;
-            if (int rc = issue_fused_pass(B, &Mr, &wr, labels, slide0 + r * R->slide_stride, n, use_bits, s, nullptr)) return rc;
+            wr.W2_alt = ws->W2_alt + (int64_t)r * 4 * H;    // (another address, the same plan)
+            if (int rc = issue_fused_pass(p, B, &Mr, &wr, labels, slide0 + r * R->slide_stride, n, use_bits, s, nullptr)) return rc;
         }
         return MOC_OK;
     }
-    fused_step_attrs();
     if (int rc = launch_w1_images(B, M, R, s)) return rc;
     moc_meta_t Mt = *M;
     float* cur = M->W2;
@@ -2573,24 +2561,18 @@ static int train_steps_runs(const moc_batch_t* B, const moc_meta_t* M, const moc
     int64_t cur_stride = R->par_stride, nxt_stride = 4 * H;
     // four runs or more: throughput, not one run's latency, is what a launch is about -- no tail workgroups
     static const int tail_env = getenv("MOC_RUNS_TAIL_INSIDE") ? atoi(getenv("MOC_RUNS_TAIL_INSIDE")) : -1;   // diagnostic override
-    static const bool prefetch = !(getenv("MOC_STEP_PREFETCH") && atoi(getenv("MOC_STEP_PREFETCH")) == 0);   // diagnostic: off
     // the common block of the step launch of runs [r0, r0 + nr) at step t: M's tensors and both W2 buffers advanced to run r0
     auto common = [&](int t, int r0, int nr, const AdamCoef& k) {
-        const int64_t po = (int64_t)r0 * R->par_stride;
-        moc_meta_t Mr = Mt;
-        Mr.W1 += po; Mr.b1 += po; Mr.b2 += po;
-        Mr.m_W1 += po; Mr.m_b1 += po; Mr.m_W2 += po; Mr.m_b2 += po;
-        Mr.v_W1 += po; Mr.v_b1 += po; Mr.v_W2 += po; Mr.v_b2 += po;
-        Mr.W2 = cur + (int64_t)r0 * cur_stride;
-        Mr.W1_image = (unsigned char*)M->W1_image + (int64_t)r0 * R->image_stride;
-        TileStepArgs ta = tile_step_args(B, &Mr, ws, labels, slide0 + t + r0 * R->slide_stride, use_bits, k,
+        moc_meta_t Mr = meta_of_run(M, R, r0);
+        Mr.W2 = cur + (int64_t)r0 * cur_stride;             // the ping-pong buffer this step reads
+        TileStepArgs ta = tile_step_args(p, B, &Mr, ws, labels, slide0 + t + r0 * R->slide_stride, use_bits, k,
                                          nxt + (int64_t)r0 * nxt_stride, 1, nullptr);
         ta.n_runs = nr; ta.slide_stride = R->slide_stride;
         ta.tail_inside = tail_env >= 0 ? tail_env : (R->n_runs >= 4 ? 1 : 0);
         ta.par_stride = R->par_stride; ta.img_stride = R->image_stride; ta.w2_stride = cur_stride; ta.w2out_stride = nxt_stride;
         // (launches of four runs or more are bound by workgroup slots, not by one run's latency: the prefetch cost eight
         // batched runs 3.6 %)
-        if (prefetch && t + 1 < n && B->C < 4 && R->n_runs < 4) ta.prefetch_next = 1;
+        if (step_prefetch_on() && t + 1 < n && B->C < 4 && R->n_runs < 4) ta.prefetch_next = 1;
         return ta;
     };
     // the per-run scalars of runs [r0, r0 + nr) behind it (the arrays' unused entries: zero)
@@ -2610,12 +2592,12 @@ static int train_steps_runs(const moc_batch_t* B, const moc_meta_t* M, const moc
     for (int t = 0; t < n; ++t) {
         const int b = slide0 + t;
         Mt.W2 = cur;
-        if (int rc = launch_forward(B, &Mt, ws, b, 1, use_bits, s, true, R, cur_stride)) return rc;
+        if (int rc = launch_forward(B, &Mt, ws, b, 1, use_bits, s, p.tiles(), R, cur_stride)) return rc;
         if (!hp) {
             TileStepArgsRuns tr;
             tr.s = common(t, 0, R->n_runs, adam_coef(M, M->step + 1 + t, 1.f));
             per_run(tr, t, 0, R->n_runs, MOC_MAX_RUNS);
-            if (int rc = launch_tile_step_runs(B, tr, s)) return rc;
+            if (int rc = launch_tile_step_runs(p, B, tr, s)) return rc;
         } else {
             for (int r0 = 0; r0 < R->n_runs; r0 += hp_per) {
                 const int nr = R->n_runs - r0 < hp_per ? R->n_runs - r0 : hp_per;
@@ -2628,7 +2610,7 @@ static int train_steps_runs(const moc_batch_t* B, const moc_meta_t* M, const moc
                 }
                 tr.s = common(t, r0, nr, tr.adam_r[0]);
                 per_run(tr, t, r0, nr, MOC_HP_RUNS);
-                if (int rc = launch_tile_step_runs(B, tr, s)) return rc;
+                if (int rc = launch_tile_step_runs(p, B, tr, s)) return rc;
             }
         }
         float* tmp = cur; cur = nxt; nxt = tmp;
@@ -2722,7 +2704,7 @@ struct GraphKey {            // everything a captured pass bakes into its kernel
 static_assert(sizeof(GraphKey) <= 512, "GraphKey outgrew moc_step_graph::Entry::key");
 
 void graph_key(GraphKey* k, const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws_t* ws, const int64_t* labels,
-               int slide0, int n, uint32_t use_bits, int mode) {
+               int slide0, int n, uint32_t use_bits, const StepPlan& p) {
     memset(k, 0, sizeof(*k));
     k->X = B->X; k->row_off = B->row_off; k->sel_row = B->sel_row; k->n_sel = B->n_sel; k->cand = B->cand; k->labels = labels;
     k->W1 = M->W1; k->b1 = M->b1; k->W2 = M->W2; k->b2 = M->b2; k->mW1 = M->m_W1; k->mb1 = M->m_b1; k->mW2 = M->m_W2;
@@ -2736,14 +2718,13 @@ void graph_key(GraphKey* k, const moc_batch_t* B, const moc_meta_t* M, const moc
         for (int i = slide0; i <= slide0 + n; ++i) { h ^= (uint64_t)B->row_off_host[i]; h *= 1099511628211ull; }
     k->off_hash = B->row_off_host ? h : 0;
     k->dtype = B->dtype; k->D = B->D; k->n_slides = B->n_slides; k->C = B->C; k->topk = B->topk; k->s_bound = s_bound(B);
-    k->mode = mode;
-    k->external = mode == 2 && (s_bound(B) > 8192 || (int64_t)B->C * s_bound(B) > 49152);
+    k->mode = p.mode(); k->external = p.external;
     k->slide0 = slide0; k->n = n; k->use_bits = use_bits;
     k->Ce = B->Ce; k->topj = B->topj; k->flags = B->flags;
 }
 
 // the 2 n + 1 launches of a fused-step pass; `tab` != null: coefficients from the device table (capture)
-int issue_fused_pass(const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws_t* ws, const int64_t* labels,
+int issue_fused_pass(const StepPlan& p, const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws_t* ws, const int64_t* labels,
                      int slide0, int n, uint32_t use_bits, hipStream_t s, const moc_step_graph* G) {
     if (int rc = launch_w1_images(B, M, nullptr, s)) return rc;      // afterwards the W1 update keeps it in sync
     // two launches per meta-step: forward, then pooling + loss + backward + the whole Adam step.
@@ -2758,8 +2739,8 @@ int issue_fused_pass(const moc_batch_t* B, const moc_meta_t* M, const moc_meta_w
         if (G) { st.tab = G->tab; st.ctr = G->ctr; st.pos = t; }
         else k = adam_coef(M, M->step + 1 + t, 1.f);
         Mt.W2 = cur;
-        if (int rc = launch_forward(B, &Mt, ws, b, 1, use_bits, s, true)) return rc;
-        if (int rc = launch_fused_step(B, &Mt, ws, labels, b, use_bits, k, nxt, s, 1, nullptr, G ? &st : nullptr, t + 1 < n ? b + 1 : -1)) return rc;
+        if (int rc = launch_forward(B, &Mt, ws, b, 1, use_bits, s, p.tiles())) return rc;
+        if (int rc = launch_fused_step(p, B, &Mt, ws, labels, b, use_bits, k, nxt, s, 1, nullptr, G ? &st : nullptr, t + 1 < n ? b + 1 : -1)) return rc;
         float* tmp = cur; cur = nxt; nxt = tmp;
     }
     if (cur != M->W2) {   // odd number of steps: the current W2 lives in the scratch buffer
@@ -2835,7 +2816,10 @@ extern "C" int moc_train_steps_graph(moc_step_graph_t* G, const moc_batch_t* B, 
     // pass (moc_host_max_kept): a different number every pass.  A captured pass must not depend on it, so the graph is
     // built for the largest SLIDE of the range -- an upper bound of every pass's kept rows (surplus workgroups leave at
     // once on n_sel).
+    // Nor on a pass's selected-row counts: n_sel_host would bake one pass's S, forward grid and tile bound into the graph, and
+    // GraphKey has no field for them -- a captured pass always reads the device n_sel.
     moc_batch_t Bg = *B;
+    Bg.n_sel_host = nullptr;
     if (B->row_off_host) {
         int64_t mx = 1;
         for (int i = slide0; i < slide0 + n; ++i) {
@@ -2846,13 +2830,13 @@ extern "C" int moc_train_steps_graph(moc_step_graph_t* G, const moc_batch_t* B, 
     }
     const moc_batch_t* Bo = B;     // as handed in: for the stream-launch fall-back
     B = &Bg;
-    const int mode = fused_step_mode(B, ws);
-    if (!mode || G->eager_only || n > G->cap) {            // shapes of the three-launch step, or a handle that gave up
+    const StepPlan p = step_plan(B, ws, false);
+    if (!p.one_launch() || G->eager_only || n > G->cap) {            // shapes of the three-launch step, or a handle that gave up
         G->eager_calls++;
         G->dev_rel = -1;
         return moc_train_steps(Bo, M, ws, labels, slide0, n, use_bits, stream);
     }
-    fused_step_attrs();
+    if (int rc = step_attrs()) return rc;                  // (before any capture)
     if (G->has_last && G->last_stream != s) {              // the previous pass ran elsewhere: order the two on the device
         if (hipStreamWaitEvent(s, G->last_done, 0) != hipSuccess) MOC_FAIL(MOC_ELAUNCH, "moc_train_steps_graph: stream wait");
     }
@@ -2885,7 +2869,7 @@ extern "C" int moc_train_steps_graph(moc_step_graph_t* G, const moc_batch_t* B, 
     {   // diagnostic: the table-reading kernels as plain stream launches (separates what the table costs from what the graph costs)
         static const char* mode_env = getenv("MOC_STEP_GRAPH_MODE");
         if (mode_env && strcmp(mode_env, "table") == 0) {
-            if (int rc = issue_fused_pass(B, M, ws, labels, slide0, n, use_bits, s, G)) return rc;
+            if (int rc = issue_fused_pass(p, B, M, ws, labels, slide0, n, use_bits, s, G)) return rc;
             G->eager_calls++;
             G->dev_rel = rel + n;
             G->has_last = hipEventRecord(G->last_done, s) == hipSuccess;
@@ -2895,7 +2879,7 @@ extern "C" int moc_train_steps_graph(moc_step_graph_t* G, const moc_batch_t* B, 
     }
     // ---- find or capture the pass
     GraphKey key;
-    graph_key(&key, B, M, ws, labels, slide0, n, use_bits, mode);
+    graph_key(&key, B, M, ws, labels, slide0, n, use_bits, p);
     moc_step_graph::Entry* hit = nullptr;
     for (int i = 0; i < G->n_entries; ++i)
         if (memcmp(G->e[i].key, &key, sizeof(key)) == 0) { hit = &G->e[i]; break; }
@@ -2906,7 +2890,7 @@ extern "C" int moc_train_steps_graph(moc_step_graph_t* G, const moc_batch_t* B, 
         hipError_t he = hipStreamBeginCapture(G->cap_stream, hipStreamCaptureModeRelaxed);
         if (he != hipSuccess) rc = MOC_ELAUNCH;
         else {
-            rc = issue_fused_pass(B, M, ws, labels, slide0, n, use_bits, G->cap_stream, G);
+            rc = issue_fused_pass(p, B, M, ws, labels, slide0, n, use_bits, G->cap_stream, G);
             he = hipStreamEndCapture(G->cap_stream, &graph);          // (always: leaves the stream out of capture mode)
             if (rc == MOC_OK && (he != hipSuccess || !graph)) rc = MOC_ELAUNCH;
         }

@@ -1120,13 +1120,12 @@ FwdArgs fwd_args(const moc_batch_t* B, const moc_meta_t* M, int slide0, uint32_t
 // that names an instantiation of it: a mode's three kernels get their LDS attribute on its first launch.
 template <int MODE, bool DENSE>
 int launch_f128(const FwdArgs& a, dim3 grid, int dtype, hipStream_t s, const char* who) {
-    static bool attr = false;
-    if (!attr) {
+    static std::once_flag attr;                               // (the batched runs launch from pool threads)
+    std::call_once(attr, [] {
         (void)hipFuncSetAttribute((const void*)meta_forward128_kernel<MODE + 0, DENSE>, hipFuncAttributeMaxDynamicSharedMemorySize, f128_lds(f128_kc(0)));
         (void)hipFuncSetAttribute((const void*)meta_forward128_kernel<MODE + 1, DENSE>, hipFuncAttributeMaxDynamicSharedMemorySize, f128_lds(f128_kc(1)));
         (void)hipFuncSetAttribute((const void*)meta_forward128_kernel<MODE + 2, DENSE>, hipFuncAttributeMaxDynamicSharedMemorySize, f128_lds(f128_kc(2)));
-        attr = true;
-    }
+    });
     if (dtype == MOC_F16) meta_forward128_kernel<MODE + 1, DENSE><<<grid, 256, f128_lds(f128_kc(1)), s>>>(a);
     else if (dtype == MOC_BF16) meta_forward128_kernel<MODE + 0, DENSE><<<grid, 256, f128_lds(f128_kc(0)), s>>>(a);
     else meta_forward128_kernel<MODE + 2, DENSE><<<grid, 256, f128_lds(f128_kc(2)), s>>>(a);
@@ -1137,15 +1136,14 @@ int launch_f128(const FwdArgs& a, dim3 grid, int dtype, hipStream_t s, const cha
 // The column-split kernel (fp32 bags, D <= 1024) for the batch's D and candidate source.  The only place that names an
 // instantiation of it.  (The runs forward never has cand_mode != 0: check_meta refuses MOC_CAND_FROM_STATS to a training entry.)
 int launch_ksplit(const FwdArgs& a, dim3 grid, hipStream_t s, const char* who) {
-    static bool attr = false;
-    if (!attr) {
+    static std::once_flag attr;
+    std::call_once(attr, [] {
 #define MOC_KS_ATTR(DQ)                                                                                                                                  \
     (void)hipFuncSetAttribute((const void*)meta_forward_ksplit_kernel<DQ, false>, hipFuncAttributeMaxDynamicSharedMemorySize, fks_lds_bytes(DQ * 256)); \
     (void)hipFuncSetAttribute((const void*)meta_forward_ksplit_kernel<DQ, true>, hipFuncAttributeMaxDynamicSharedMemorySize, fks_lds_bytes(DQ * 256))
         MOC_KS_ATTR(2); MOC_KS_ATTR(3); MOC_KS_ATTR(4);
 #undef MOC_KS_ATTR
-        attr = true;
-    }
+    });
     const int lds = fks_lds_bytes(a.D);
 #define MOC_KS_LAUNCH(DQ)                                                                        \
     do {                                                                                         \
@@ -1187,7 +1185,8 @@ int moc_meta_internal::launch_forward(const moc_batch_t* B, const moc_meta_t* M,
 #endif
     a.H1 = ws->H1; a.gates = ws->gates; a.mixed = ws->mixed;
     if (n == 1 && B->row_off_host) a.base_host = B->row_off_host[slide0];
-    if (emit_tiles && n == 1 && a.base_host >= 0 && tiles_ok(B, ws)) {
+    if (emit_tiles) {                                      // the caller's plan says the tile-record step follows
+        MOC_REQUIRE(n == 1 && B->row_off_host && ws->tile_ws, "moc_meta_forward: tile records need one slide, row_off_host and ws->tile_ws");
         a.tile_on = 1;
         a.tile = tile_carve(ws->tile_ws, tile_slots(B->total_rows, B->n_slides, B->C));
         a.tile_cap = moc_cdiv(B->row_off_host[slide0 + 1] - a.base_host, 16);

@@ -1,6 +1,7 @@
 // What the two halves of phase B share: moc_meta_forward.hip (the meta forward) and moc_meta.hip (the step).  Private to
 // those two sources; nothing here is exported from the library.
 #pragma once
+#include <mutex>   // std::call_once: both halves raise their kernels' LDS limits once, from any thread
 #include "moc_common.h"
 
 namespace moc_meta_internal __attribute__((visibility("hidden"))) {
@@ -118,8 +119,25 @@ __device__ __forceinline__ void w1_image_store(int dt, unsigned char* img, int D
     else w1_image_store_f32(img, D, h, d, w);
 }
 
+// ------------------------------------------------------------------ which step kernel runs (moc_meta.hip)
+// Decided ONCE per training call by step_plan, the only reader of the step kernels' shape limits; the launchers take the
+// plan and the forward is told (emit_tiles) what it implies.  What depends on the slide stays per step.
+enum StepKind { STEP_THREE = 0, STEP_NARROW, STEP_TILES, STEP_WIDE };   // three launches | pool_w1_step{,_tiles,_wide}_kernel
+struct StepPlan {
+    StepKind kind;
+    bool pool_one;                               // pooling + loss in one kernel (pool_step_kernel): the three-launch step, evaluation
+    int cap;                                     // PS_CAP: candidate list entries per class
+    size_t smem;                                 // dynamic LDS of the one-launch kernel
+    int pch, wide_region, wide_cap, external;    // wide: pairs per chunk, its LDS region, its list cap, pooling by topk_mean_kernel first
+    bool one_launch() const { return kind != STEP_THREE; }
+    bool tiles() const { return kind == STEP_TILES; }
+    int mode() const { return kind == STEP_THREE ? 0 : kind == STEP_WIDE ? 2 : 1; }   // as GraphKey records it
+};
+// exchange: a P2pArgs will be passed to the step (never the tile-record kind); train = 0: pooling + loss only
+StepPlan step_plan(const moc_batch_t* B, const moc_meta_ws_t* ws, bool exchange, int train = 1);
+
 // ------------------------------------------------------------------ the forward's host side, as the step calls it
-// (moc_meta_forward.hip, but for tiles_ok: moc_meta.hip, the step's own limits)
+// (moc_meta_forward.hip)
 // the argument checks every entry over a meta-learner and its work arrays starts with
 int check_meta(const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws_t* ws, const char* who, bool need_adam,
                bool need_grad, bool need_h1 = true);
@@ -127,10 +145,8 @@ int check_meta(const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws_t* w
 int launch_w1_images(const moc_batch_t* B, const moc_meta_t* M, const moc_runs_t* R, hipStream_t s);
 // the most selected rows a slide of the batch can have
 int s_bound(const moc_batch_t* B);
-// whether the one-launch step over tile records serves this shape
-bool tiles_ok(const moc_batch_t* B, const moc_meta_ws_t* ws);
-// The forward of slides [slide0, slide0 + n) into ws.  emit_tiles: the one-launch step over tile records follows (training
-// step of one slide): leave the records.  runs != nullptr: the training forward of runs->n_runs meta-learners in one launch
+// The forward of slides [slide0, slide0 + n) into ws.  emit_tiles (StepPlan::tiles()): the one-launch step over tile records
+// follows (training step of one slide): leave the records.  runs != nullptr: the training forward of runs->n_runs meta-learners in one launch
 // (moc_train_steps_runs), `M->W2` / `w2_stride` = where their current W2 lives.
 int launch_forward(const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws_t* ws, int slide0, int n, uint32_t use_bits,
                    hipStream_t s, bool emit_tiles = false, const moc_runs_t* runs = nullptr, int64_t w2_stride = 0);

@@ -127,3 +127,55 @@ def test_train_dp_matches_minibatch_oracle(gpu_device, exchange, world, C, shape
     for rank in range(world):
         ev = out[rank][2]
         assert abs(ev["loss"] - ev_ref["loss"]) < 1e-4 and ev["acc"] == ev_ref["acc"] and abs(ev["auc"] - ev_ref["auc"]) < 2e-3
+
+
+def test_one_rank_exchange_step_does_not_read_tile_records(gpu_device):
+    """moc_train_steps_p2p launches its forward without tile records, so its step must not pool from them -- at any world
+    size, one rank included, and whatever the work arrays carry.  A one-rank communicator and work arrays WITH record
+    arrays (zero-filled: empty records, so a step that read them would pool nothing and end with other numbers) against
+    moc_train_steps on an identical model without them: the same narrow kernel, grid and coefficient floats -- equal bits."""
+    import copy
+    import ctypes as C
+    from moc_amd import _lib, engine as E, main_moc as M, synth
+    dev = gpu_device
+    Cc, D, j, K, sizes = 2, 512, 100, 10, [300, 120, 40]
+    n = len(sizes)                                                  # odd: the W2 copy-back runs
+    W, We = synth.make_bank(77, D, Cc)
+    bags, labels = synth.make_slide_set(7700, sizes, D, We, Cc)
+    batch = E.SlideBatch(torch.cat(bags).to(dev).contiguous(), sizes, Cc, Cc + 4, j, K)
+    batch.phase_a(E.Bank.get(W.to(dev), We.to(dev), torch.float32, dev))
+    lab = torch.tensor(labels, dtype=torch.int64, device=dev)
+    t, ws = batch.meta_ws()
+    nb = _lib.lib().moc_tile_ws_bytes(batch.total, n, Cc)
+    records = torch.zeros(nb, dtype=torch.uint8, device=dev)
+    ws_rec, ws_none = _lib.MocMetaWs.from_buffer_copy(ws), _lib.MocMetaWs.from_buffer_copy(ws)
+    ws_rec.tile_ws, ws_rec.tile_ws_bytes = records.data_ptr(), nb
+    ws_none.tile_ws, ws_none.tile_ws_bytes = None, 0
+    assert _lib.lib().moc_train_runs_mode(C.byref(batch.c), C.byref(ws_rec)) == 1, "the shape must be one the tile-record step serves"
+    torch.manual_seed(5)
+    models = [M.senet(D, 4).to(dev)]
+    models.append(copy.deepcopy(models[0]))
+    W1_before = models[0].model[0].weight.detach().clone()
+    opts = [torch.optim.Adam(m.parameters(), lr=1e-3, weight_decay=1e-4) for m in models]
+    metas = [E.MetaState(m, o) for m, o in zip(models, opts)]
+    use_bits = E.train_use_bits([])
+    comm = C.c_void_p()
+    _lib.check(_lib.lib().moc_p2p_create(1, 0, E.HIDDEN * D + E.HIDDEN + 4 * E.HIDDEN + 4, C.byref(comm)), "moc_p2p_create")
+    try:
+        _lib.check(_lib.lib().moc_train_steps_p2p(C.byref(batch.c), C.byref(metas[0].c), C.byref(ws_rec), lab.data_ptr(), 0, n,
+                                                  use_bits, comm, E._stream()), "moc_train_steps_p2p")
+        torch.cuda.synchronize()
+        assert _lib.lib().moc_p2p_error(comm) == 0
+        loss_x = t["loss"][:n].cpu().clone()
+    finally:
+        _lib.lib().moc_p2p_destroy(comm)
+    t["loss"].zero_()
+    _lib.check(_lib.lib().moc_train_steps(C.byref(batch.c), C.byref(metas[1].c), C.byref(ws_none), lab.data_ptr(), 0, n,
+                                          use_bits, E._stream()), "moc_train_steps")
+    torch.cuda.synchronize()
+    assert torch.equal(loss_x, t["loss"][:n].cpu()) and bool((loss_x > 0).all())
+    for px, py in zip(models[0].parameters(), models[1].parameters()):
+        assert torch.equal(px, py), "the one-rank exchange step and moc_train_steps ended with different parameters"
+        for key in ("exp_avg", "exp_avg_sq"):
+            assert torch.equal(opts[0].state[px][key], opts[1].state[py][key]), key
+    assert not torch.equal(W1_before, models[0].model[0].weight.detach())         # (the steps did move W1)

@@ -139,3 +139,29 @@ def _graph_vs_oracle(dev, E, M, O):
     assert E.MetaState.cached(model, opt).graph_stats()[1] == 3
     H.assert_adam_params_close(H.flat_params(model), H.flat_params(ref_model), H.flat_state(ref_opt, "exp_avg_sq"),
                                step=12, grad_noise=1e-6, what="graph path, 3 epochs")
+
+
+def test_captured_pass_ignores_n_sel_host(gpu_device, monkeypatch):
+    """The C ABI on its own: a captured pass that IS handed moc_batch_t.n_sel_host (engine.train_steps never does) must not
+    bake that pass's selected-row counts -- S, the forward's grid, the step's tile bound -- into the graph: a replay serves
+    another pass, with other counts.  publish_n_sel is made to hand the pinned copy over whatever `allow` says."""
+    from moc_amd import engine as E
+    sizes, handed, counts = [900, 1300, 700], [], []
+    publish = E.SlideBatch.publish_n_sel
+
+    def always(self, allow=True):
+        torch.cuda.synchronize()                       # the copy's event has completed
+        handed.append(publish(self, True))
+        counts.append(self.n_sel.cpu().tolist())        # (by pass)
+        return handed[-1]
+
+    with monkeypatch.context() as mp:
+        mp.setattr(E.SlideBatch, "publish_n_sel", always)
+        g = _run(gpu_device, True, 2, sizes, torch.float32, [3] * 4)
+    e = _run(gpu_device, False, 2, sizes, torch.float32, [3] * 4)
+    _same(g, e)
+    assert g[2][1] == 4 and g[2][2] == 0, g[2]          # four graph launches, no stream-launch pass
+    assert len(handed) == 4 and any(handed), handed     # the pinned copy was handed over
+    # ... and the counts moved between passes i and i + 2, which share a set of work arrays and so a captured graph (two
+    # sets alternate; with one set every pass replays pass 0's graph and the same comparison holds): a stale capture would show
+    assert len(counts) == 4 and any(counts[i] != counts[i + 2] for i in (0, 1)), counts
