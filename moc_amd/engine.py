@@ -5,6 +5,7 @@ device buffers and the stream; every kernel is ours.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import weakref
@@ -376,12 +377,16 @@ class SlideBatch:
         self.c.flags = ((_lib.MOC_STATS_COMPACT if compact else 0) | (_lib.MOC_CAND_FROM_STATS if cand_from_stats else 0) |
                         (self.c.flags & (_lib.MOC_SELECT_PER_COLUMN | _lib.MOC_FORWARD_ROWS64 | _lib.MOC_FORWARD_FOUR_WAVES | _lib.MOC_FORWARD_ROWS16)))
 
+    def _eval_layout(self, compact: bool):
+        """The layout of an evaluation pass -- only meta_forward follows (no train step, no ablation mix): candidates
+        straight from the statistics."""
+        self._layout(compact, cand_from_stats=CAND_FROM_STATS and self.C > 4)
+
     def phase_a(self, bank: Bank, for_eval: bool = False):
         assert bank.D == self.D and bank.C == self.C and bank.Ce == self.Ce and bank.dtype == self.X.dtype
         # wide banks: C + 5 statistics per row instead of 2C + 3 (the selector and the candidate gather re-form the
         # softmax columns); phase A is the only reader of its own statistics, so the layout is its private choice.
-        # for_eval: only meta_forward follows (no train step, no ablation mix): candidates straight from the statistics
-        self._layout(COMPACT_STATS and self.Ce > 16, cand_from_stats=bool(for_eval) and CAND_FROM_STATS and self.C > 4)
+        (self._eval_layout if for_eval else self._layout)(COMPACT_STATS and self.Ce > 16)
         self._n_sel_stale()
         if SCORE_EVENTS is None and self.stats_cache is None:
             check(lib().moc_phase_a(C.byref(self.c), ptr(bank.image), _stream()), "moc_phase_a")
@@ -474,6 +479,38 @@ class SlideBatch:
             v._layout(False)
             v._n_sel_stale()
         return views
+
+    def scores_for_eval(self, bank: Bank):
+        """The evaluation layout, the kept-row lists and the score pass, nothing else: the first two launches of
+        phase_a(for_eval=True) as two entries -- for a caller that selects several times over one set of statistics."""
+        self._eval_layout(COMPACT_STATS and self.Ce > 16)
+        self._n_sel_stale()
+        check(lib().moc_mask_compact(C.byref(self.c), _stream()), "moc_mask_compact")
+        check(lib().moc_scores(C.byref(self.c), ptr(bank.image), _stream()), "moc_scores")
+
+    def select_for_eval(self, topj: int | None = None, discard=(), clear: bool = False):
+        """Over statistics that exist, in the layout they were written in: the evaluation layout, the selection and the
+        candidates -- the rest of phase_a(for_eval=True) behind a score pass.  topj given: select with that topj and
+        discard set instead of the batch's (see borrowed).  clear: the flags an earlier selection over these statistics
+        left are cleared first (the selectors only SET flags; the score pass cleared them for the first)."""
+        self._eval_layout(bool(self.c.flags & _lib.MOC_STATS_COMPACT))
+        if topj is not None:
+            self.c.topj, self.c.discard_bits = topj, _lib.discard_bits(discard)
+        if clear:
+            self.sel_flag.zero_()
+        self.select()
+        self.gather_candidates()
+
+    @contextlib.contextmanager
+    def borrowed(self):
+        """For a caller that changes the topj, discard set or layout of a batch it does not own (a cached plan's): they
+        are what they were afterwards."""
+        keep = (self.c.topj, self.c.discard_bits, self.c.flags)
+        try:
+            yield self
+        finally:
+            self.c.topj, self.c.discard_bits, self.c.flags = keep
+            self._n_sel_stale()
 
     def select(self):
         self._n_sel_stale()
@@ -1079,6 +1116,15 @@ def loss_only(batch: SlideBatch, labels: torch.Tensor, slide0: int, n: int):
     t, _ = batch.meta_ws()
     check(lib().moc_ce_loss(ptr(t["pooled"][slide0:]), ptr(labels[slide0:]), n, batch.C,
                             ptr(t["loss"][slide0:]), ptr(t["pred"][slide0:]), _stream()), "moc_ce_loss")
+
+
+def ce_loss(pooled: torch.Tensor, labels: torch.Tensor):
+    """(loss [n] float32, pred [n] int32): CE + argmax of the rows of `pooled` [n, C] (float32, contiguous)."""
+    n, Cc = pooled.shape
+    loss = torch.empty(n, dtype=torch.float32, device=pooled.device)
+    pred = torch.empty(n, dtype=torch.int32, device=pooled.device)
+    check(lib().moc_ce_loss(ptr(pooled), ptr(labels), n, Cc, ptr(loss), ptr(pred), _stream()), "moc_ce_loss")
+    return loss, pred
 
 
 def train_steps(batch: SlideBatch, meta: MetaState, labels: torch.Tensor, slide0: int, n: int, use_bits: int):

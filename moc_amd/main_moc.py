@@ -30,6 +30,7 @@ How the loops map onto the GPU
 """
 from __future__ import annotations
 
+import contextlib
 import os
 
 import numpy as np
@@ -650,6 +651,93 @@ def _metrics(pooled_cpu, labels, losses, n_div, real_len, args):
     return {"loss": test_loss, "acc": correct / real_len, "auc": auc}
 
 
+@contextlib.contextmanager
+def _every_slide_once(*loaders, restore="len"):
+    """The scope of every evaluation pass: no gradients, and each loader's dataset visits every slide once
+    (repeat_num = real_len()) -> real_len() of the first.  On exit, an exception included, repeat_num is put back, last
+    loader first, in one of two ways -- both the reference's, both observable:
+      "len":  to what len(dataset) was (evaluation, main_moc.py:470, :499): a split that came with None leaves with real_len();
+      "attr": to what the attribute was (zs_evaluation, main_moc.py:418, :437): None stays None.
+    The metrics' divisor is len(dataset) AFTER the exit."""
+    assert restore in ("len", "attr")
+    saved = []
+    with torch.no_grad():
+        for ld in loaders:
+            ds = ld.dataset
+            saved.append((ds, ds.repeat_num if restore == "attr" else len(ds)))
+            ds.repeat_num = ds.real_len()
+        try:
+            yield loaders[0].dataset.real_len()
+        finally:
+            for ds, was in reversed(saved):
+                ds.repeat_num = was
+
+
+class _Chunks:
+    """The host side of a pass: per key the chunks' [n, C + 1] rows (pooled | loss; slabs=True: [n_K, n, C + 1], one slab
+    per topk) and the labels of the slides, in visit order -> the pass's rows, or its metrics."""
+
+    def __init__(self, keys=(None,), slabs=False):
+        self.parts, self.labels, self.dim = {k: [] for k in keys}, [], int(slabs)
+
+    def rows(self, key=None, of=None):
+        """(pooled [N, C], labels, losses) of a key; `of`: these rows only."""
+        v = torch.cat(self.parts[key], 0)
+        if of is None:
+            return v[:, :-1].contiguous(), self.labels, v[:, -1].tolist()
+        return v[of, :-1].contiguous(), [self.labels[i] for i in of.tolist()], v[of, -1].tolist()
+
+    def metrics(self, key, loader, real_len, args):
+        """_metrics of a key's rows; slabs: one dict per topk."""
+        n_div = len(loader.dataset)
+        if not self.dim:
+            return _metrics(*self.rows(key), n_div, real_len, args)
+        v = torch.cat(self.parts[key], 1)
+        return [_metrics(s[:, :-1].contiguous(), self.labels, s[:, -1].tolist(), n_div, real_len, args) for s in v]
+
+
+_ZS_KINDS = {topj_pooling: "topj", delta_softmax_classifier_pooling: "delta_softmax",
+             delta_diff_classifier_pooling: "delta_diff", bottomk_irrel_classifier_pooling: "bottomk"}
+
+
+def _zs_columns(st, C_, kind):
+    """(keys, vals, smallest, key_shared) of a fused zero-shot pooling function over the full statistics layout."""
+    if kind == "topj":
+        return st[:C_], st[:C_], False, False
+    if kind == "delta_softmax":
+        return st[C_:2 * C_], st[:C_], False, False
+    if kind == "delta_diff":
+        return st[2 * C_:2 * C_ + 1], st[:C_], False, True
+    return st[2 * C_ + 1:2 * C_ + 2], st[:C_], True, True      # bottomk: K rows of smallest background mass
+
+
+def _host_rows(batch):
+    """A chunk's pooled logits | loss on the host, [n, C + 1]: the one device->host transfer of the chunk."""
+    t, _ = batch.meta_ws()
+    return torch.cat([t["pooled"], t["loss"].unsqueeze(1)], 1).cpu()
+
+
+def _zs_step(batch, kind, lab, topk):
+    """A chunk of a fused zero-shot pass, over a batch whose statistics exist (full layout)."""
+    t, _ = batch.meta_ws()
+    keys, vals, small, shared = _zs_columns(batch.stats, batch.C, kind)
+    t["pooled"].copy_(engine.topk_mean(keys, vals, topk, smallest=small, key_shared=shared, seg_off=batch.row_off))
+    engine.loss_only(batch, lab, 0, batch.n_slides)
+    return _host_rows(batch)
+
+
+def _eval_step(batch, meta, lab, use_bits, bank=None):
+    """A chunk of evaluation(): from `bank`, phase A as evaluation issues it; bank=None: the batch's statistics exist (a
+    bank set's score pass), the rest of that phase A follows them.  Then the meta forward and the pooling."""
+    if bank is not None:
+        batch.phase_a(bank, for_eval=True)
+    else:
+        batch.select_for_eval()
+    engine.meta_forward(batch, meta, 0, batch.n_slides, use_bits, keep_hidden=False)
+    engine.pool_loss(batch, lab, 0, batch.n_slides)
+    return _host_rows(batch)
+
+
 def _eval_batches(loader, device, args, mode, extras=None):
     """(batch, device labels, label list) per chunk of an evaluation pass.  `extras`: see _collect."""
     discard = args.discard_classifiers if mode == "eval" else []
@@ -699,11 +787,11 @@ def _eval_pass_custom(loader, device, args, pooling_func):
     X, sizes, x_starts, labels = _collect(loader, device, args)
     bank = _ext_logits_bank(X, device)
     Ce = bank.C
-    outs = []
+    out = _Chunks()
+    out.labels = labels
     for ids in _chunks(sizes, X.size(1), X.element_size()):
         batch = _sub_batch(X, sizes, x_starts, ids, bank.C, bank.Ce, args.topj, args.topk, [])
         batch.scores(bank)
-        tensors, _ = batch.meta_ws()
         rows = []
         for b in range(len(ids)):
             o, n = batch.row_off_host[b], batch.sizes[b]
@@ -711,68 +799,41 @@ def _eval_pass_custom(loader, device, args, pooling_func):
             rows.append(pooling_func(logits_ext, [args.topk], coords_list=args.n_classes)[1][args.topk].reshape(1, -1))
         pooled = torch.cat(rows, 0).to(torch.float32).contiguous()
         lab = torch.tensor([labels[i] for i in ids], dtype=torch.int64).to(device)
-        loss = torch.empty(len(ids), dtype=torch.float32, device=device)
-        pred = torch.empty(len(ids), dtype=torch.int32, device=device)
-        engine.check(engine.lib().moc_ce_loss(engine.ptr(pooled), engine.ptr(lab), len(ids), pooled.size(1),
-                                              engine.ptr(loss), engine.ptr(pred), engine._stream()), "moc_ce_loss")
-        outs.append(torch.cat([pooled, loss.unsqueeze(1)], 1).cpu())
-    allv = torch.cat(outs, 0)
-    return allv[:, :-1].contiguous(), labels, allv[:, -1].tolist()
+        loss, _ = engine.ce_loss(pooled, lab)
+        out.parts[None].append(torch.cat([pooled, loss.unsqueeze(1)], 1).cpu())
+    return out.rows()
 
 
-def _eval_pass(loader, device, args, mode, model=None, pooling_func=None):
+def _eval_pass(loader, device, args, mode, model=None):
+    """One pass in `mode` ("eval", "ablation", "zs_" + a fused kind) -> (pooled [N, C] on the host, labels, losses)."""
     _loader_seed_draw(loader)
     bank, batches = _eval_batches(loader, device, args, mode)
-    C_ = bank.C
     meta = MetaState(model) if model is not None else None
-    outs, labels = [], []
+    use_bits = engine.eval_use_bits(args.discard_classifiers) if mode == "eval" else 0
+    out = _Chunks()
     for batch, lab, lab_list in batches:
-        n = batch.n_slides
-        tensors, _ = batch.meta_ws()
         if mode.startswith("zs"):
             batch.scores(bank)
-            st = batch.stats
-            kind = mode[3:]
-            if kind == "topj":
-                keys, vals, small, shared = st[:C_], st[:C_], False, False
-            elif kind == "delta_softmax":
-                keys, vals, small, shared = st[C_:2 * C_], st[:C_], False, False
-            elif kind == "delta_diff":
-                keys, vals, small, shared = st[2 * C_:2 * C_ + 1], st[:C_], False, True
-            else:   # bottomk: K rows of smallest background mass, mean of their foreground logits
-                keys, vals, small, shared = st[2 * C_ + 1:2 * C_ + 2], st[:C_], True, True
-            p = engine.topk_mean(keys, vals, args.topk, smallest=small, key_shared=shared, seg_off=batch.row_off)
-            tensors["pooled"].copy_(p)
-            engine.loss_only(batch, lab, 0, n)
+            rows = _zs_step(batch, mode[3:], lab, args.topk)
+        elif mode == "eval":
+            rows = _eval_step(batch, meta, lab, use_bits, bank)
         else:
-            batch.phase_a(bank, for_eval=(mode == "eval"))
-            if mode == "eval":
-                engine.meta_forward(batch, meta, 0, n, engine.eval_use_bits(args.discard_classifiers), keep_hidden=False)
-            else:
-                engine.mix_fixed(batch, 0, n, args.ablation_study)
-            engine.pool_loss(batch, lab, 0, n)
-        # one device->host transfer per chunk: [n, C] pooled logits | loss
-        outs.append(torch.cat([tensors["pooled"], tensors["loss"].unsqueeze(1)], 1).cpu())
-        labels.extend(lab_list)
-    allv = torch.cat(outs, 0)
-    return allv[:, :-1].contiguous(), labels, allv[:, -1].tolist()
+            batch.phase_a(bank)
+            engine.mix_fixed(batch, 0, batch.n_slides, args.ablation_study)
+            engine.pool_loss(batch, lab, 0, batch.n_slides)
+            rows = _host_rows(batch)
+        out.parts[None].append(rows)
+        out.labels.extend(lab_list)
+    return out.rows()
 
 
 def zs_evaluation(loader, device, args, pooling_func=topj_pooling):
     """main_moc.py:412-460."""
-    with torch.no_grad():
-        real_len = loader.dataset.real_len()
-        set_len = loader.dataset.repeat_num
-        loader.dataset.repeat_num = real_len
-        kinds = {topj_pooling: "topj", delta_softmax_classifier_pooling: "delta_softmax",
-                 delta_diff_classifier_pooling: "delta_diff", bottomk_irrel_classifier_pooling: "bottomk"}
-        try:
-            if pooling_func in kinds:
-                pooled, labels, losses = _eval_pass(loader, device, args, "zs_" + kinds[pooling_func])
-            else:           # any other callable, as the reference accepts (main_moc.py:429-432)
-                pooled, labels, losses = _eval_pass_custom(loader, device, args, pooling_func)
-        finally:
-            loader.dataset.repeat_num = set_len
+    with _every_slide_once(loader, restore="attr") as real_len:
+        if pooling_func in _ZS_KINDS:
+            pooled, labels, losses = _eval_pass(loader, device, args, "zs_" + _ZS_KINDS[pooling_func])
+        else:           # any other callable, as the reference accepts (main_moc.py:429-432)
+            pooled, labels, losses = _eval_pass_custom(loader, device, args, pooling_func)
     return _metrics(pooled, labels, losses, len(loader.dataset), real_len, args)
 
 
@@ -780,14 +841,8 @@ def evaluation(model, loader, device, args):
     """main_moc.py:462-520 (incl. the eval-side mix quirk, see engine.eval_use_bits)."""
     if model.training:                   # (nn.Module.eval() walks the module tree: 20 us of an 1 ms pass)
         model.eval()
-    with torch.no_grad():
-        real_len = loader.dataset.real_len()
-        set_len = len(loader.dataset)
-        loader.dataset.repeat_num = real_len
-        try:
-            pooled, labels, losses = _eval_pass(loader, device, args, "eval", model=model)
-        finally:
-            loader.dataset.repeat_num = set_len
+    with _every_slide_once(loader) as real_len:
+        pooled, labels, losses = _eval_pass(loader, device, args, "eval", model=model)
     return _metrics(pooled, labels, losses, len(loader.dataset), real_len, args)
 
 
@@ -807,21 +862,27 @@ def _sweep_checks(who, loader, topks):
     return topks
 
 
+def _sweep_axes(who, args, topjs, discard_sets):
+    """The (topj, discard) axes of a model sweep -> the distinct (topj, discard tuple) pairs, topj outermost;
+    discard_sets=None: the one of args."""
+    topjs = [int(j) for j in topjs]
+    assert topjs and min(topjs) >= 1, f"{who}: topj must be >= 1"
+    sets = [tuple(d) for d in ([args.discard_classifiers or ()] if discard_sets is None else discard_sets)]
+    assert sets, f"{who}: no discard set given"
+    return list(dict.fromkeys((j, d) for j in topjs for d in sets))
+
+
 def _pool_slabs(keys, vals, topks, lab, n, small=False, shared=False, seg_off=None, seg_len=None):
     """[n_K, n, C + 1] on the device: per K the pooled logits of moc_topk_mean at that K | their loss (moc_ce_loss) -- one
     ranking per group of at most eight K."""
     Cc = vals.size(0)
     out = torch.empty((len(topks), n, Cc + 1), dtype=torch.float32, device=vals.device)
-    loss = torch.empty(n, dtype=torch.float32, device=vals.device)
-    pred = torch.empty(n, dtype=torch.int32, device=vals.device)
     for g0 in range(0, len(topks), engine.MULTI_MAX_NK):
         ks = topks[g0:g0 + engine.MULTI_MAX_NK]
         slabs = engine.topk_mean_multi(keys, vals, ks, smallest=small, key_shared=shared, seg_off=seg_off, seg_len=seg_len)
         for i in range(len(ks)):
-            engine.check(engine.lib().moc_ce_loss(engine.ptr(slabs[i]), engine.ptr(lab), n, Cc, engine.ptr(loss), engine.ptr(pred),
-                                                  engine._stream()), "moc_ce_loss")
             out[g0 + i, :, :Cc] = slabs[i]
-            out[g0 + i, :, Cc] = loss
+            out[g0 + i, :, Cc] = engine.ce_loss(slabs[i], lab)[0]
     return out
 
 
@@ -850,27 +911,26 @@ def _pool_loss_slabs(batch, topks, lab, n):
     return out
 
 
-def _sweep_configs(batch, meta, lab, parts, topks):
+def _sweep_configs(batch, meta, lab, acc, configs, topks, g=()):
     """evaluation_sweep's loop over a batch whose statistics exist (flags cleared by the score pass): per (topj, discard)
-    of `parts` the selection, the candidates, the meta forward and the pooled logits | loss of every topk, appended to
-    parts[(topj, discard)].  Leaves the batch's topj / discard_bits changed: the caller restores them."""
+    of `configs` the selection, the candidates, the meta forward and the pooled logits | loss of every topk, appended to
+    acc.parts[g + (topj, discard)].  Leaves the batch's topj / discard_bits changed: see SlideBatch.borrowed."""
     n = batch.n_slides
     tensors, _ = batch.meta_ws()
-    for ci, (j, d) in enumerate(parts):
-        batch.c.topj, batch.c.discard_bits = j, engine._lib.discard_bits(d)
-        if ci > 0:
-            # the selectors only SET flags: the score pass cleared them for the first configuration, the
-            # sweep clears what the configuration before this one selected
-            batch.sel_flag.zero_()
-        batch.select()
-        batch.gather_candidates()
+    for ci, (j, d) in enumerate(configs):
+        batch.select_for_eval(j, d, clear=ci > 0)
         engine.meta_forward(batch, meta, 0, n, engine.eval_use_bits(d), keep_hidden=False)
         mixed = tensors["mixed"]
         if batch.C <= 2 or batch.C > 16:
             slabs = _pool_slabs(mixed, mixed, topks, lab, n, seg_off=batch.row_off, seg_len=batch.n_sel)
         else:
             slabs = _pool_loss_slabs(batch, topks, lab, n)
-        parts[(j, d)].append(slabs.cpu())
+        acc.parts[g + (j, d)].append(slabs.cpu())
+
+
+def _sweep_cells(acc, configs, topks, loader, real_len, args, g=()):
+    """{(topj, topk, discard): metrics} from the slabs kept under g + (topj, discard)."""
+    return {(j, k, d): m for j, d in configs for k, m in zip(topks, acc.metrics(g + (j, d), loader, real_len, args))}
 
 
 def evaluation_sweep(model, loader, device, args, topjs, topks, discard_sets=None):
@@ -881,44 +941,19 @@ def evaluation_sweep(model, loader, device, args, topjs, topks, discard_sets=Non
     _pool_loss_slabs); one device-to-host copy per (topj, discard).
     discard_sets=None: [args.discard_classifiers].  Resident splits without loader_seed_draw only."""
     topks = _sweep_checks("evaluation_sweep", loader, topks)
-    topjs = [int(j) for j in topjs]
-    assert topjs and min(topjs) >= 1, "evaluation_sweep: topj must be >= 1"
-    sets = [tuple(d) for d in ([args.discard_classifiers or ()] if discard_sets is None else discard_sets)]
-    assert sets, "evaluation_sweep: no discard set given"
+    configs = _sweep_axes("evaluation_sweep", args, topjs, discard_sets)
     if model.training:
         model.eval()
-    parts = {(j, d): [] for j in topjs for d in sets}
-    labels = []
-    with torch.no_grad():
-        real_len = loader.dataset.real_len()
-        set_len = len(loader.dataset)
-        loader.dataset.repeat_num = real_len
-        try:
-            bank, batches = _eval_batches(loader, device, args, "eval")
-            meta = MetaState(model)
-            for batch, lab, lab_list in batches:
-                n = batch.n_slides
-                tensors, _ = batch.meta_ws()
-                keep = (batch.c.topj, batch.c.discard_bits, batch.c.flags)      # (the batch may be a cached plan's)
-                try:
-                    # phase_a(for_eval=True)'s layout, then its first two launches -- once
-                    batch._layout(engine.COMPACT_STATS and batch.Ce > 16, cand_from_stats=engine.CAND_FROM_STATS and batch.C > 4)
-                    batch._n_sel_stale()
-                    engine.check(engine.lib().moc_mask_compact(engine.C.byref(batch.c), engine._stream()), "moc_mask_compact")
-                    engine.check(engine.lib().moc_scores(engine.C.byref(batch.c), engine.ptr(bank.image), engine._stream()), "moc_scores")
-                    _sweep_configs(batch, meta, lab, parts, topks)
-                finally:
-                    batch.c.topj, batch.c.discard_bits, batch.c.flags = keep
-                    batch._n_sel_stale()
-                labels.extend(lab_list)
-        finally:
-            loader.dataset.repeat_num = set_len
-    out = {}
-    for (j, d), chunks in parts.items():
-        allv = torch.cat(chunks, 1)
-        for i, k in enumerate(topks):
-            out[(j, k, d)] = _metrics(allv[i, :, :-1].contiguous(), labels, allv[i, :, -1].tolist(), len(loader.dataset), real_len, args)
-    return out
+    acc = _Chunks(configs, slabs=True)
+    with _every_slide_once(loader) as real_len:
+        bank, batches = _eval_batches(loader, device, args, "eval")
+        meta = MetaState(model)
+        for batch, lab, lab_list in batches:
+            with batch.borrowed():                   # (the batch may be a cached plan's)
+                batch.scores_for_eval(bank)          # once
+                _sweep_configs(batch, meta, lab, acc, configs, topks)
+            acc.labels.extend(lab_list)
+    return _sweep_cells(acc, configs, topks, loader, real_len, args)
 
 
 def zs_evaluation_sweep(loader, device, args, topks, pooling_funcs=ZS_POOLING_FUNCS):
@@ -928,71 +963,43 @@ def zs_evaluation_sweep(loader, device, args, topks, pooling_funcs=ZS_POOLING_FU
     shares the pass when those foreground columns ARE zeroshot_weights, and gets a pass of its own otherwise.)  Only the
     four fused pooling functions; any other callable stays with zs_evaluation."""
     topks = _sweep_checks("zs_evaluation_sweep", loader, topks)
-    kinds = {topj_pooling: "topj", delta_softmax_classifier_pooling: "delta_softmax",
-             delta_diff_classifier_pooling: "delta_diff", bottomk_irrel_classifier_pooling: "bottomk"}
-    funcs = list(pooling_funcs)
-    assert funcs and all(f in kinds for f in funcs), \
-        "zs_evaluation_sweep: only the four fused pooling functions (others: zs_evaluation, one call each)"
-    Cn = zeroshot_weights.size(1)
-    ext_is_fg = bool(torch.equal(zeroshot_weights_ext[:, :Cn].to(device=zeroshot_weights.device, dtype=torch.float32),
-                                 zeroshot_weights.to(torch.float32)))
+    funcs = _zs_funcs("zs_evaluation_sweep", pooling_funcs)
+    ext_is_fg = _ext_is_fg(zeroshot_weights, zeroshot_weights_ext)
     passes = {}                          # fg_from_ext -> the functions scored by that bank
     for f in funcs:
-        passes.setdefault(kinds[f] == "bottomk" and not ext_is_fg, []).append(f)
-    parts = {f: [] for f in funcs}
-    labels = []
-    with torch.no_grad():
-        real_len = loader.dataset.real_len()
-        set_len = loader.dataset.repeat_num
-        loader.dataset.repeat_num = real_len
-        try:
-            for pi, (from_ext, fs) in enumerate(passes.items()):
-                bank, batches = _eval_batches(loader, device, args, "zs_bottomk" if from_ext else "zs_topj")
-                C_ = bank.C
-                for batch, lab, lab_list in batches:
-                    batch.scores(bank)
-                    st = batch.stats
-                    for f in fs:
-                        kind = kinds[f]
-                        if kind == "topj":
-                            keys, vals, small, shared = st[:C_], st[:C_], False, False
-                        elif kind == "delta_softmax":
-                            keys, vals, small, shared = st[C_:2 * C_], st[:C_], False, False
-                        elif kind == "delta_diff":
-                            keys, vals, small, shared = st[2 * C_:2 * C_ + 1], st[:C_], False, True
-                        else:
-                            keys, vals, small, shared = st[2 * C_ + 1:2 * C_ + 2], st[:C_], True, True
-                        parts[f].append(_pool_slabs(keys, vals, topks, lab, batch.n_slides, small, shared,
-                                                    seg_off=batch.row_off).cpu())
-                    if pi == 0:
-                        labels.extend(lab_list)
-        finally:
-            loader.dataset.repeat_num = set_len
-    out = {}
-    for f in funcs:
-        allv = torch.cat(parts[f], 1)
-        for i, k in enumerate(topks):
-            out[(f.__name__, k)] = _metrics(allv[i, :, :-1].contiguous(), labels, allv[i, :, -1].tolist(), len(loader.dataset),
-                                            real_len, args)
-    return out
+        passes.setdefault(_ZS_KINDS[f] == "bottomk" and not ext_is_fg, []).append(f)
+    acc = _Chunks(funcs, slabs=True)
+    with _every_slide_once(loader, restore="attr") as real_len:
+        for pi, (from_ext, fs) in enumerate(passes.items()):
+            bank, batches = _eval_batches(loader, device, args, "zs_bottomk" if from_ext else "zs_topj")
+            for batch, lab, lab_list in batches:
+                batch.scores(bank)
+                for f in fs:
+                    acc.parts[f].append(_zs_slabs(batch, _ZS_KINDS[f], topks, lab))
+                if pi == 0:
+                    acc.labels.extend(lab_list)
+    return _zs_cells(acc, funcs, topks, loader, real_len, args)
+
+
+def _zs_funcs(who, pooling_funcs):
+    funcs = list(pooling_funcs)
+    assert funcs and all(f in _ZS_KINDS for f in funcs), \
+        f"{who}: only the four fused pooling functions (others: zs_evaluation, one call each)"
+    return funcs
+
+
+def _zs_slabs(batch, kind, topks, lab):
+    """A chunk of a fused zero-shot sweep, over a batch whose statistics exist: [n_K, n, C + 1] on the host."""
+    keys, vals, small, shared = _zs_columns(batch.stats, batch.C, kind)
+    return _pool_slabs(keys, vals, topks, lab, batch.n_slides, small, shared, seg_off=batch.row_off).cpu()
+
+
+def _zs_cells(acc, funcs, topks, loader, real_len, args, of=lambda f: f):
+    """{(pooling function's name, topk): metrics} from the slabs kept under of(f)."""
+    return {(f.__name__, k): m for f in funcs for k, m in zip(topks, acc.metrics(of(f), loader, real_len, args))}
 
 
 # ---- bank sweeps: several prompt banks of one class count from ONE read of the bags per group of banks ------------------
-_ZS_KINDS = {topj_pooling: "topj", delta_softmax_classifier_pooling: "delta_softmax",
-             delta_diff_classifier_pooling: "delta_diff", bottomk_irrel_classifier_pooling: "bottomk"}
-
-
-def _zs_columns(st, C_, kind):
-    """(keys, vals, smallest, key_shared) of a fused zero-shot pooling function over the full statistics layout."""
-    if kind == "topj":
-        return st[:C_], st[:C_], False, False
-    if kind == "delta_softmax":
-        return st[C_:2 * C_], st[:C_], False, False
-    if kind == "delta_diff":
-        return st[2 * C_:2 * C_ + 1], st[:C_], False, True
-    return st[2 * C_ + 1:2 * C_ + 2], st[:C_], True, True      # bottomk: K rows of smallest background mass
-
-
 def _bank_checks(who, loader, banks):
     """The refusals of the bank forms, before any launch -> the banks as (W, W_ext) tuples."""
     assert isinstance(loader, ResidentBags), f"{who}: resident splits only (main_moc.ResidentBags)"
@@ -1050,28 +1057,13 @@ def zs_evaluation_banks(loader, device, args, banks, pooling_func=topj_pooling):
     assert pooling_func in _ZS_KINDS, "zs_evaluation_banks: only the four fused pooling functions (others: zs_evaluation per bank)"
     kind = _ZS_KINDS[pooling_func]
     entries = [(W, We, kind == "bottomk") for W, We in banks]        # (zs_evaluation's own image for this function)
-    outs, labels = [[] for _ in banks], []
-    with torch.no_grad():
-        real_len = loader.dataset.real_len()
-        set_len = loader.dataset.repeat_num
-        loader.dataset.repeat_num = real_len
-        try:
-            for views, lab, lab_list in _bank_batches(loader, device, args, entries, []):
-                for g, v in enumerate(views):
-                    tensors, _ = v.meta_ws()
-                    keys, vals, small, shared = _zs_columns(v.stats, v.C, kind)
-                    p = engine.topk_mean(keys, vals, args.topk, smallest=small, key_shared=shared, seg_off=v.row_off)
-                    tensors["pooled"].copy_(p)
-                    engine.loss_only(v, lab, 0, v.n_slides)
-                    outs[g].append(torch.cat([tensors["pooled"], tensors["loss"].unsqueeze(1)], 1).cpu())
-                labels.extend(lab_list)
-        finally:
-            loader.dataset.repeat_num = set_len
-    res = []
-    for parts in outs:
-        allv = torch.cat(parts, 0)
-        res.append(_metrics(allv[:, :-1].contiguous(), labels, allv[:, -1].tolist(), len(loader.dataset), real_len, args))
-    return res
+    acc = _Chunks(range(len(banks)))
+    with _every_slide_once(loader, restore="attr") as real_len:
+        for views, lab, lab_list in _bank_batches(loader, device, args, entries, []):
+            for g, v in enumerate(views):
+                acc.parts[g].append(_zs_step(v, kind, lab, args.topk))
+            acc.labels.extend(lab_list)
+    return [acc.metrics(g, loader, real_len, args) for g in acc.parts]
 
 
 def zs_evaluation_sweep_banks(loader, device, args, banks, topks, pooling_funcs=ZS_POOLING_FUNCS):
@@ -1080,10 +1072,8 @@ def zs_evaluation_sweep_banks(loader, device, args, banks, topks, pooling_funcs=
     W_ext[:, :C] is not W, the fg_from_ext image is one more entry of the set, not a pass of its own."""
     topks = _sweep_checks("zs_evaluation_sweep_banks", loader, topks)
     banks = _bank_checks("zs_evaluation_sweep_banks", loader, banks)
-    funcs = list(pooling_funcs)
-    assert funcs and all(f in _ZS_KINDS for f in funcs), \
-        "zs_evaluation_sweep_banks: only the four fused pooling functions (others: zs_evaluation, one call each)"
-    entries, jobs = [], []                                          # jobs: (entry, bank, its functions)
+    funcs = _zs_funcs("zs_evaluation_sweep_banks", pooling_funcs)
+    entries, jobs = [], []                                       # jobs: (entry, bank, its functions)
     for g, (W, We) in enumerate(banks):
         own_ext = [f for f in funcs if _ZS_KINDS[f] == "bottomk" and not _ext_is_fg(W, We)]
         shared = [f for f in funcs if f not in own_ext]
@@ -1091,32 +1081,14 @@ def zs_evaluation_sweep_banks(loader, device, args, banks, topks, pooling_funcs=
             if fs:
                 jobs.append((len(entries), g, fs))
                 entries.append((W, We, from_ext))
-    parts = [{f: [] for f in funcs} for _ in banks]
-    labels = []
-    with torch.no_grad():
-        real_len = loader.dataset.real_len()
-        set_len = loader.dataset.repeat_num
-        loader.dataset.repeat_num = real_len
-        try:
-            for views, lab, lab_list in _bank_batches(loader, device, args, entries, []):
-                for e, g, fs in jobs:
-                    v = views[e]
-                    for f in fs:
-                        keys, vals, small, shared = _zs_columns(v.stats, v.C, _ZS_KINDS[f])
-                        parts[g][f].append(_pool_slabs(keys, vals, topks, lab, v.n_slides, small, shared, seg_off=v.row_off).cpu())
-                labels.extend(lab_list)
-        finally:
-            loader.dataset.repeat_num = set_len
-    res = []
-    for g in range(len(banks)):
-        out = {}
-        for f in funcs:
-            allv = torch.cat(parts[g][f], 1)
-            for i, k in enumerate(topks):
-                out[(f.__name__, k)] = _metrics(allv[i, :, :-1].contiguous(), labels, allv[i, :, -1].tolist(), len(loader.dataset),
-                                                real_len, args)
-        res.append(out)
-    return res
+    acc = _Chunks([(g, f) for g in range(len(banks)) for f in funcs], slabs=True)
+    with _every_slide_once(loader, restore="attr") as real_len:
+        for views, lab, lab_list in _bank_batches(loader, device, args, entries, []):
+            for e, g, fs in jobs:
+                for f in fs:
+                    acc.parts[(g, f)].append(_zs_slabs(views[e], _ZS_KINDS[f], topks, lab))
+            acc.labels.extend(lab_list)
+    return [_zs_cells(acc, funcs, topks, loader, real_len, args, of=lambda f, g=g: (g, f)) for g in range(len(banks))]
 
 
 def _bank_models(who, models, n_banks):
@@ -1137,34 +1109,16 @@ def evaluation_banks(models, loader, device, args, banks):
     bags per group of banks.  `models`: one model, or one per bank."""
     banks = _bank_checks("evaluation_banks", loader, banks)
     models = _bank_models("evaluation_banks", models, len(banks))
-    outs, labels = [[] for _ in banks], []
-    with torch.no_grad():
-        real_len = loader.dataset.real_len()
-        set_len = len(loader.dataset)
-        loader.dataset.repeat_num = real_len
-        try:
-            metas = [MetaState(m) for m in models]
-            use = engine.eval_use_bits(args.discard_classifiers)
-            for views, lab, lab_list in _bank_batches(loader, device, args, [(W, We, False) for W, We in banks],
-                                                      args.discard_classifiers):
-                for g, v in enumerate(views):
-                    n = v.n_slides
-                    tensors, _ = v.meta_ws()
-                    # the rest of phase_a(for_eval=True) behind the score pass, then evaluation()'s two launches
-                    v._layout(False, cand_from_stats=engine.CAND_FROM_STATS and v.C > 4)
-                    v.select()
-                    v.gather_candidates()
-                    engine.meta_forward(v, metas[g], 0, n, use, keep_hidden=False)
-                    engine.pool_loss(v, lab, 0, n)
-                    outs[g].append(torch.cat([tensors["pooled"], tensors["loss"].unsqueeze(1)], 1).cpu())
-                labels.extend(lab_list)
-        finally:
-            loader.dataset.repeat_num = set_len
-    res = []
-    for parts in outs:
-        allv = torch.cat(parts, 0)
-        res.append(_metrics(allv[:, :-1].contiguous(), labels, allv[:, -1].tolist(), len(loader.dataset), real_len, args))
-    return res
+    acc = _Chunks(range(len(banks)))
+    with _every_slide_once(loader) as real_len:
+        metas = [MetaState(m) for m in models]
+        use = engine.eval_use_bits(args.discard_classifiers)
+        for views, lab, lab_list in _bank_batches(loader, device, args, [(W, We, False) for W, We in banks],
+                                                  args.discard_classifiers):
+            for g, v in enumerate(views):
+                acc.parts[g].append(_eval_step(v, metas[g], lab, use))
+            acc.labels.extend(lab_list)
+    return [acc.metrics(g, loader, real_len, args) for g in acc.parts]
 
 
 def evaluation_sweep_banks(models, loader, device, args, banks, topjs, topks, discard_sets=None):
@@ -1173,35 +1127,15 @@ def evaluation_sweep_banks(models, loader, device, args, banks, topjs, topks, di
     topks = _sweep_checks("evaluation_sweep_banks", loader, topks)
     banks = _bank_checks("evaluation_sweep_banks", loader, banks)
     models = _bank_models("evaluation_sweep_banks", models, len(banks))
-    topjs = [int(j) for j in topjs]
-    assert topjs and min(topjs) >= 1, "evaluation_sweep_banks: topj must be >= 1"
-    sets = [tuple(d) for d in ([args.discard_classifiers or ()] if discard_sets is None else discard_sets)]
-    assert sets, "evaluation_sweep_banks: no discard set given"
-    parts = [{(j, d): [] for j in topjs for d in sets} for _ in banks]
-    labels = []
-    with torch.no_grad():
-        real_len = loader.dataset.real_len()
-        set_len = len(loader.dataset)
-        loader.dataset.repeat_num = real_len
-        try:
-            metas = [MetaState(m) for m in models]
-            for views, lab, lab_list in _bank_batches(loader, device, args, [(W, We, False) for W, We in banks], []):
-                for g, v in enumerate(views):
-                    v._layout(False, cand_from_stats=engine.CAND_FROM_STATS and v.C > 4)
-                    _sweep_configs(v, metas[g], lab, parts[g], topks)
-                labels.extend(lab_list)
-        finally:
-            loader.dataset.repeat_num = set_len
-    res = []
-    for g in range(len(banks)):
-        out = {}
-        for (j, d), chunks in parts[g].items():
-            allv = torch.cat(chunks, 1)
-            for i, k in enumerate(topks):
-                out[(j, k, d)] = _metrics(allv[i, :, :-1].contiguous(), labels, allv[i, :, -1].tolist(), len(loader.dataset),
-                                          real_len, args)
-        res.append(out)
-    return res
+    configs = _sweep_axes("evaluation_sweep_banks", args, topjs, discard_sets)
+    acc = _Chunks([(g,) + c for g in range(len(banks)) for c in configs], slabs=True)
+    with _every_slide_once(loader) as real_len:
+        metas = [MetaState(m) for m in models]
+        for views, lab, lab_list in _bank_batches(loader, device, args, [(W, We, False) for W, We in banks], []):
+            for g, v in enumerate(views):
+                _sweep_configs(v, metas[g], lab, acc, configs, topks, g=(g,))
+            acc.labels.extend(lab_list)
+    return [_sweep_cells(acc, configs, topks, loader, real_len, args, g=(g,)) for g in range(len(banks))]
 
 
 # plans of evaluation_runs, least recently used first.  A caller that evaluates one fixed set every epoch and a varying
@@ -1319,45 +1253,29 @@ def evaluation_runs(models, loaders, device, args):
         arena = engine.ModelArena.of_models([m for _, m in uniq.values()])
         model_of_run = [uniq[id(m)][0] for m in models]
         assert arena.D == D, "evaluation_runs: the models' width is not the bags'"
-        restore = []
-        for ld in loaders:
-            restore.append((ld.dataset, len(ld.dataset)))
-            ld.dataset.repeat_num = ld.dataset.real_len()
-        try:
-            plan = _eval_runs_plan(loaders, model_of_run, device, args)
-            use = engine.eval_use_bits(args.discard_classifiers)
-            outs = []
-            for batch, lab, rel, groups in plan["chunks"]:
-                tensors, _ = batch.meta_ws()
-                batch.phase_a(plan["bank"], for_eval=True)
-                for g0, gm, s0, sn in groups:
-                    engine.meta_forward_by_slide(batch, arena, g0, gm, rel, s0, sn, use)
-                engine.pool_loss(batch, lab, 0, batch.n_slides)
-                outs.append(torch.cat([tensors["pooled"], tensors["loss"].unsqueeze(1)], 1).cpu())
-        finally:
-            for ds, set_len in reversed(restore):
-                ds.repeat_num = set_len
-    allv = torch.cat(outs, 0)
+    acc = _Chunks()
+    with _every_slide_once(*loaders):                # (a split named twice ends where it began: restored last first)
+        plan = _eval_runs_plan(loaders, model_of_run, device, args)
+        use = engine.eval_use_bits(args.discard_classifiers)
+        for batch, lab, rel, groups in plan["chunks"]:
+            batch.phase_a(plan["bank"], for_eval=True)
+            for g0, gm, s0, sn in groups:
+                engine.meta_forward_by_slide(batch, arena, g0, gm, rel, s0, sn, use)
+            engine.pool_loss(batch, lab, 0, batch.n_slides)
+            acc.parts[None].append(_host_rows(batch))
+    acc.labels = plan["labels"]
     run_of = torch.tensor(plan["run_of"])
     evaluation_runs.last_pooled = []
     res = []
     for r, ld in enumerate(loaders):
-        rows = (run_of == r).nonzero().flatten()
-        pooled = allv[rows, :-1].contiguous()
+        pooled, labels, losses = acc.rows(of=(run_of == r).nonzero().flatten())
         evaluation_runs.last_pooled.append(pooled)
-        res.append(_metrics(pooled, [plan["labels"][i] for i in rows.tolist()], allv[rows, -1].tolist(), len(ld.dataset),
-                            ld.dataset.real_len(), args))
+        res.append(_metrics(pooled, labels, losses, len(ld.dataset), ld.dataset.real_len(), args))
     return res
 
 
 def ablation_evaluation(loader, device, args):
     """main_moc.py:523-582, args.ablation_study in {avg, sum, max}."""
-    real_len = loader.dataset.real_len()
-    set_len = len(loader.dataset)
-    loader.dataset.repeat_num = real_len
-    try:
-        with torch.no_grad():
-            pooled, labels, losses = _eval_pass(loader, device, args, "ablation")
-    finally:
-        loader.dataset.repeat_num = set_len
+    with _every_slide_once(loader) as real_len:
+        pooled, labels, losses = _eval_pass(loader, device, args, "ablation")
     return _metrics(pooled, labels, losses, len(loader.dataset), real_len, args)

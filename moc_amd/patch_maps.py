@@ -48,57 +48,51 @@ def patch_maps(model, loader, device, args) -> list[PatchMap]:
     zero-shot top-K mean of the logits and `pred` its argmax)."""
     if model is not None and model.training:
         model.eval()
-    ds = loader.dataset
-    set_len = len(ds)
     K = int(args.topk)
     out = []
-    with torch.no_grad():
-        ds.repeat_num = ds.real_len()
-        try:
-            M._loader_seed_draw(loader)
-            extras = []
-            bank, batches = M._eval_batches(loader, device, args, "eval", extras=extras)
-            C_ = bank.C
-            meta = engine.MetaState(model) if model is not None else None
-            use_bits = engine.eval_use_bits(args.discard_classifiers)
-            v = 0
-            for batch, lab, lab_list in batches:
-                n, T = batch.n_slides, batch.total
-                tensors, _ = batch.meta_ws()
-                batch.phase_a(bank, for_eval=True)
-                logits_d = batch.stats[:C_]
-                zs_pooled, zs_idx, zs_cnt = engine.topk_mean(logits_d, logits_d, K, want_idx=True, seg_off=batch.row_off)
-                host = {"logits": logits_d, "sel_flag": batch.sel_flag, "zs_idx": zs_idx, "zs_cnt": zs_cnt}
+    with M._every_slide_once(loader):
+        M._loader_seed_draw(loader)
+        extras = []
+        bank, batches = M._eval_batches(loader, device, args, "eval", extras=extras)
+        C_ = bank.C
+        meta = engine.MetaState(model) if model is not None else None
+        use_bits = engine.eval_use_bits(args.discard_classifiers)
+        v = 0
+        for batch, lab, lab_list in batches:
+            n, T = batch.n_slides, batch.total
+            tensors, _ = batch.meta_ws()
+            batch.phase_a(bank, for_eval=True)
+            logits_d = batch.stats[:C_]
+            zs_pooled, zs_idx, zs_cnt = engine.topk_mean(logits_d, logits_d, K, want_idx=True, seg_off=batch.row_off)
+            host = {"logits": logits_d, "sel_flag": batch.sel_flag, "zs_idx": zs_idx, "zs_cnt": zs_cnt}
+            if meta is not None:
+                engine.meta_forward(batch, meta, 0, n, use_bits, keep_hidden=False)
+                engine.pool_loss(batch, lab, 0, n)
+                gates = torch.empty((T, 4), dtype=torch.float32, device=batch.device)
+                mixed = torch.empty((C_, T), dtype=torch.float32, device=batch.device)
+                engine.meta_forward_dense(batch, meta, 0, n, use_bits, gates, mixed)
+                host.update(gates=gates, mixed=mixed, pooled=tensors["pooled"], pred=tensors["pred"],
+                            sel_idx=batch.sel_idx, topk_idx=tensors["topk_idx"], topk_cnt=tensors["topk_cnt"])
+            else:
+                host.update(pooled=zs_pooled, pred=zs_pooled.argmax(dim=1))
+            h = {k: t.cpu().numpy() for k, t in host.items()}     # one copy of each array per chunk
+            for b in range(n):
+                o, N = batch.row_off_host[b], batch.sizes[b]
+                coords, path = extras[v]
+                v += 1
+                kz = int(h["zs_cnt"][b, 0])
+                pm = PatchMap(
+                    path=path, label=int(lab_list[b]), pred=int(h["pred"][b]), pooled=h["pooled"][b].copy(),
+                    coords=np.asarray(coords, dtype=np.int64).reshape(N, 2).copy(),
+                    logits=np.ascontiguousarray(h["logits"][:, o:o + N].T),
+                    selected=h["sel_flag"][o:o + N].astype(bool),
+                    zs_evidence=h["zs_idx"][b, :, :kz].astype(np.int64))
                 if meta is not None:
-                    engine.meta_forward(batch, meta, 0, n, use_bits, keep_hidden=False)
-                    engine.pool_loss(batch, lab, 0, n)
-                    gates = torch.empty((T, 4), dtype=torch.float32, device=batch.device)
-                    mixed = torch.empty((C_, T), dtype=torch.float32, device=batch.device)
-                    engine.meta_forward_dense(batch, meta, 0, n, use_bits, gates, mixed)
-                    host.update(gates=gates, mixed=mixed, pooled=tensors["pooled"], pred=tensors["pred"],
-                                sel_idx=batch.sel_idx, topk_idx=tensors["topk_idx"], topk_cnt=tensors["topk_cnt"])
-                else:
-                    host.update(pooled=zs_pooled, pred=zs_pooled.argmax(dim=1))
-                h = {k: t.cpu().numpy() for k, t in host.items()}     # one copy of each array per chunk
-                for b in range(n):
-                    o, N = batch.row_off_host[b], batch.sizes[b]
-                    coords, path = extras[v]
-                    v += 1
-                    kz = int(h["zs_cnt"][b, 0])
-                    pm = PatchMap(
-                        path=path, label=int(lab_list[b]), pred=int(h["pred"][b]), pooled=h["pooled"][b].copy(),
-                        coords=np.asarray(coords, dtype=np.int64).reshape(N, 2).copy(),
-                        logits=np.ascontiguousarray(h["logits"][:, o:o + N].T),
-                        selected=h["sel_flag"][o:o + N].astype(bool),
-                        zs_evidence=h["zs_idx"][b, :, :kz].astype(np.int64))
-                    if meta is not None:
-                        kk = int(h["topk_cnt"][b, 0])
-                        pm.gates = h["gates"][o:o + N].copy()
-                        pm.mixed = np.ascontiguousarray(h["mixed"][:, o:o + N].T)
-                        pm.evidence = h["sel_idx"][o + h["topk_idx"][b, :, :kk]].astype(np.int64)
-                    out.append(pm)
-        finally:
-            ds.repeat_num = set_len
+                    kk = int(h["topk_cnt"][b, 0])
+                    pm.gates = h["gates"][o:o + N].copy()
+                    pm.mixed = np.ascontiguousarray(h["mixed"][:, o:o + N].T)
+                    pm.evidence = h["sel_idx"][o + h["topk_idx"][b, :, :kk]].astype(np.int64)
+                out.append(pm)
     return out
 
 

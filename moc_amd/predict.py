@@ -69,64 +69,58 @@ def predict(state_dicts, loader, device, args, labeled: bool = True, slide_ids=N
     from .patch_maps import EnsembleMap, slide_id_of
     R = len(state_dicts)
     assert 1 <= R <= MAX_MODELS, f"predict: 1 .. {MAX_MODELS} checkpoints"
-    ds = loader.dataset
-    set_len = len(ds)
     pooled, losses, labels = [], [], []
     parts = []                                             # maps: per slide, everything but the ensemble's probabilities
-    with torch.no_grad():
-        ds.repeat_num = ds.real_len()
-        try:
-            M._loader_seed_draw(loader)
-            extras = []
-            bank, batches = M._eval_batches(loader, device, args, "eval", extras=extras)
-            arena = engine.ModelArena(state_dicts, device)
-            use_bits = engine.eval_use_bits(args.discard_classifiers)
-            if maps and bank.C > 64:
-                raise SystemExit(f"--patch_maps: {bank.C} classes; the ensemble maps take at most 64")
-            K = int(args.topk)
-            v = 0
-            for batch, lab, lab_list in batches:
-                n = batch.n_slides
-                batch.phase_a(bank, for_eval=True)
-                mixed = torch.empty((R, batch.C, batch.total), dtype=torch.float32, device=batch.device)
-                engine.meta_forward_models(batch, arena, R, mixed, 0, n, use_bits)
-                lab_d = lab if labeled else torch.zeros_like(lab)
-                out = engine.pool_models(batch, mixed, lab_d, 0, n)
-                if maps:
-                    T = batch.total
-                    pm = torch.empty((batch.C, T), dtype=torch.float32, device=batch.device)
-                    ps = torch.empty((batch.C, T), dtype=torch.float32, device=batch.device)
-                    gm = torch.empty((T, 4), dtype=torch.float32, device=batch.device)
-                    engine.meta_forward_dense_models(batch, arena, R, M.CONCH_TEMPERATURE, pm, ps, gm, 0, n, use_bits)
-                    logits_d = batch.stats[:batch.C]
-                    _, zs_idx, zs_cnt = engine.topk_mean(logits_d, logits_d, K, want_idx=True, seg_off=batch.row_off)
-                    dev_arrays = {"logits": logits_d, "sel_flag": batch.sel_flag, "zs_idx": zs_idx, "zs_cnt": zs_cnt,
-                                  "prob_mean": pm, "prob_std": ps, "gates_mean": gm, "sel_idx": batch.sel_idx,
-                                  "topk_idx": out["topk_idx"], "topk_cnt": out["topk_cnt"], "pooled": out["pooled"]}
-                    h = {k: t.cpu().numpy() for k, t in dev_arrays.items()}     # one copy of each array per chunk
-                    for b in range(n):
-                        o, N = batch.row_off_host[b], batch.sizes[b]
-                        coords, path = extras[v]
-                        v += 1
-                        kz, kk = int(h["zs_cnt"][b, 0]), int(h["topk_cnt"][0, b, 0])
-                        parts.append(dict(
-                            path=path, label=int(lab_list[b]) if labeled else -1, pooled=h["pooled"][:, b].copy(),
-                            coords=np.asarray(coords, dtype=np.int64).reshape(N, 2).copy(),
-                            logits=np.ascontiguousarray(h["logits"][:, o:o + N].T),
-                            selected=h["sel_flag"][o:o + N].astype(bool),
-                            zs_evidence=h["zs_idx"][b, :, :kz].astype(np.int64),
-                            prob_mean=np.ascontiguousarray(h["prob_mean"][:, o:o + N].T),
-                            prob_std=np.ascontiguousarray(h["prob_std"][:, o:o + N].T),
-                            gates_mean=h["gates_mean"][o:o + N].copy(),
-                            evidence=h["sel_idx"][o + h["topk_idx"][:, b, :, :kk]].astype(np.int64)))
-                    pooled.append(h["pooled"])
-                    losses.append(out["loss"].cpu().numpy())
-                else:
-                    pooled.append(out["pooled"].cpu().numpy())
-                    losses.append(out["loss"].cpu().numpy())
-                labels.extend(lab_list)
-        finally:
-            ds.repeat_num = set_len
+    with M._every_slide_once(loader):
+        M._loader_seed_draw(loader)
+        extras = []
+        bank, batches = M._eval_batches(loader, device, args, "eval", extras=extras)
+        arena = engine.ModelArena(state_dicts, device)
+        use_bits = engine.eval_use_bits(args.discard_classifiers)
+        if maps and bank.C > 64:
+            raise SystemExit(f"--patch_maps: {bank.C} classes; the ensemble maps take at most 64")
+        K = int(args.topk)
+        v = 0
+        for batch, lab, lab_list in batches:
+            n = batch.n_slides
+            batch.phase_a(bank, for_eval=True)
+            mixed = torch.empty((R, batch.C, batch.total), dtype=torch.float32, device=batch.device)
+            engine.meta_forward_models(batch, arena, R, mixed, 0, n, use_bits)
+            lab_d = lab if labeled else torch.zeros_like(lab)
+            out = engine.pool_models(batch, mixed, lab_d, 0, n)
+            if maps:
+                T = batch.total
+                pm = torch.empty((batch.C, T), dtype=torch.float32, device=batch.device)
+                ps = torch.empty((batch.C, T), dtype=torch.float32, device=batch.device)
+                gm = torch.empty((T, 4), dtype=torch.float32, device=batch.device)
+                engine.meta_forward_dense_models(batch, arena, R, M.CONCH_TEMPERATURE, pm, ps, gm, 0, n, use_bits)
+                logits_d = batch.stats[:batch.C]
+                _, zs_idx, zs_cnt = engine.topk_mean(logits_d, logits_d, K, want_idx=True, seg_off=batch.row_off)
+                dev_arrays = {"logits": logits_d, "sel_flag": batch.sel_flag, "zs_idx": zs_idx, "zs_cnt": zs_cnt,
+                              "prob_mean": pm, "prob_std": ps, "gates_mean": gm, "sel_idx": batch.sel_idx,
+                              "topk_idx": out["topk_idx"], "topk_cnt": out["topk_cnt"], "pooled": out["pooled"]}
+                h = {k: t.cpu().numpy() for k, t in dev_arrays.items()}     # one copy of each array per chunk
+                for b in range(n):
+                    o, N = batch.row_off_host[b], batch.sizes[b]
+                    coords, path = extras[v]
+                    v += 1
+                    kz, kk = int(h["zs_cnt"][b, 0]), int(h["topk_cnt"][0, b, 0])
+                    parts.append(dict(
+                        path=path, label=int(lab_list[b]) if labeled else -1, pooled=h["pooled"][:, b].copy(),
+                        coords=np.asarray(coords, dtype=np.int64).reshape(N, 2).copy(),
+                        logits=np.ascontiguousarray(h["logits"][:, o:o + N].T),
+                        selected=h["sel_flag"][o:o + N].astype(bool),
+                        zs_evidence=h["zs_idx"][b, :, :kz].astype(np.int64),
+                        prob_mean=np.ascontiguousarray(h["prob_mean"][:, o:o + N].T),
+                        prob_std=np.ascontiguousarray(h["prob_std"][:, o:o + N].T),
+                        gates_mean=h["gates_mean"][o:o + N].copy(),
+                        evidence=h["sel_idx"][o + h["topk_idx"][:, b, :, :kk]].astype(np.int64)))
+                pooled.append(h["pooled"])
+                losses.append(out["loss"].cpu().numpy())
+            else:
+                pooled.append(out["pooled"].cpu().numpy())
+                losses.append(out["loss"].cpu().numpy())
+            labels.extend(lab_list)
     paths = [str(p) for _, p in extras]
     pooled = np.concatenate(pooled, axis=1)
     probs = _probs(pooled)
