@@ -235,7 +235,11 @@ int moc_scores_timed(const moc_batch_t* B, const void* bank, moc_stream_t stream
  * An evaluation pass: static walk over the whole chip, full statistics layout -- a batch with tile_ticket / cu_reserved
  * set or with MOC_STATS_COMPACT is refused (MOC_EINVAL), as are a null pointer, n_banks outside 1 .. 4, a Ce outside
  * C < Ce <= 16 and more banks than moc_scores_banks_max; MOC_EUNSUPPORTED where not even one bank's image fits in LDS
- * beside the epilogue tiles and one slide's metadata (moc_scores_banks_max == 0).  Nothing is launched on a refusal. */
+ * beside the epilogue tiles and one slide's metadata (moc_scores_banks_max == 0).  Nothing is launched on a refusal.
+ * stats[g] / sel_flag[g] are only ever addressed as stats[g] + r * B->total_rows + row_off[b] + i and sel_flag[g] +
+ * row_off[b] + i with 4- and 1-byte stores: they need only 4- / 1-byte alignment and may lie INSIDE a larger array of the
+ * same row stride -- a batch's own stats / sel_flag advanced by a number of slots, which lands bank g's statistics of
+ * slide b in the slots of another slide of the same size (moc_amd/runs.py: training under several banks). */
 int    moc_scores_banks_max(int D, int dtype);             /* banks one launch serves for this D / storage: the streaming
                                                               kernel's n-tile limits (four on fp32 bags, three on 16-bit
                                                               bags) and 160 KiB of LDS; 0 = none */
@@ -291,6 +295,17 @@ int moc_phase_a(const moc_batch_t* B, const void* bank, moc_stream_t stream);
  * Errors (not faults), before anything is launched: null B / leader_of_slide, a batch without stats / sel_flag, a bad slide
  * range.  Additive to ABI 20: the version number is unchanged. */
 int moc_stats_share(const moc_batch_t* B, const int32_t* leader_of_slide, int slide0, int n, moc_stream_t stream);
+
+/* The lists-only half of moc_stats_share (additive to ABI 20): for followers whose statistics their OWN score pass writes --
+ * runs that train under another prompt bank see their leader's masks and none of its scores.  Every follower slide b in
+ * [slide0, slide0 + n) with leader l = leader_of_slide[b] (as above: device int32 [B->n_slides], negative = left alone,
+ * clamped into the batch on the device) receives
+ *   n_kept[b] = n_kept[l];   kept[row_off[b] + i] = kept[row_off[l] + i]   for i < n_kept[l]
+ * with the count clamped to both slides' sizes.  stats and sel_flag are NOT touched (they may be null): the pass that scores
+ * the follower's slots writes the statistics and clears the flags.  An unmasked batch has no lists: MOC_OK, nothing launched.
+ * Errors (not faults), before anything is launched: null B / leader_of_slide, a masked batch without kept / n_kept, a bad
+ * slide range. */
+int moc_kept_share(const moc_batch_t* B, const int32_t* leader_of_slide, int slide0, int n, moc_stream_t stream);
 
 /* Phase A's result for slides [slide0, slide0+n) in a fixed-capacity, position-independent form -- what
  * slide_process hands to the meta-learner (main_moc.py:367-375: selected_feat + the four candidate matrices),

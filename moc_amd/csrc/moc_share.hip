@@ -118,6 +118,59 @@ __global__ __launch_bounds__(SH_THREADS) void stats_share_kernel(ShareArgs a) {
     }
 }
 
+// The lists-only half of the share (include/moc_hip.h moc_kept_share): a follower whose statistics its OWN score pass
+// writes -- a run under another prompt bank, which sees the leader's masks and none of its scores -- needs the leader's
+// kept-row list and count and nothing else; the 2C+3 statistics rows and the flags are left to that pass.
+struct KeptShareArgs {
+    const int32_t* leader_of_slide;
+    const int64_t* row_off;
+    int32_t* kept;
+    int32_t* n_kept;
+    int n_slides, slide0;
+    int vec_ok;              // kept is 16-byte aligned: a list's alignment follows from row_off alone
+};
+
+// grid (row blocks, follower slides), 256 threads
+__global__ __launch_bounds__(SH_THREADS) void kept_share_kernel(KeptShareArgs a) {
+    const int b = a.slide0 + (int)blockIdx.y;
+    int l = a.leader_of_slide[b];                              // (uniform: one scalar load)
+    if (l < 0) return;                                         // not a follower
+    l = l < a.n_slides ? l : a.n_slides - 1;                   // clamped into the batch, as in stats_share_kernel
+    if (l == b) return;
+    const int64_t src0 = a.row_off[l], dst0 = a.row_off[b];
+    const int cap_l = (int)(a.row_off[l + 1] - src0), cap_b = (int)(a.row_off[b + 1] - dst0);
+    int nk = a.n_kept[l];
+    nk = nk < cap_l ? nk : cap_l;                              // never outside either slide's slots
+    nk = nk < cap_b ? nk : cap_b;
+    nk = nk > 0 ? nk : 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) a.n_kept[b] = nk;
+    if (nk == 0) return;
+    const int t = (int)threadIdx.x;
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(a.kept) + src0;
+    uint32_t* dst = reinterpret_cast<uint32_t*>(a.kept) + dst0;
+    const bool vec = a.vec_ok && (((src0 - dst0) & 3) == 0);
+    if (vec) {
+        const int head = (int)((4 - (dst0 & 3)) & 3);          // scalar words in front of the first aligned one
+        const int h = head < nk ? head : nk;
+        const int nvec = (nk - h) >> 2;
+        const int tail0 = h + 4 * nvec;                        // scalar words behind the last full vector
+        for (int v = (int)blockIdx.x * SH_THREADS + t; v < nvec; v += (int)gridDim.x * SH_THREADS)
+            reinterpret_cast<uint4*>(dst + h)[v] = reinterpret_cast<const uint4*>(src + h)[v];
+        if (blockIdx.x == 0 && t < 8) {                        // head and tail: at most three words each
+            const int i = t < 4 ? t : tail0 + (t - 4);
+            const bool ok = t < 4 ? t < h : (t - 4) < nk - tail0;
+            if (ok) dst[i] = src[i];
+        }
+    } else {
+        for (int i0 = (int)blockIdx.x * SH_CHUNK; i0 < nk; i0 += (int)gridDim.x * SH_CHUNK) {
+            auto rd = [&](int u) { const int i = i0 + u * SH_THREADS + t; return src[i < nk ? i : nk - 1]; };
+            auto wr = [&](int u, uint32_t w) { const int i = i0 + u * SH_THREADS + t; if (i < nk) dst[i] = w; };
+            const uint32_t w0 = rd(0), w1 = rd(1), w2 = rd(2), w3 = rd(3);
+            wr(0, w0); wr(1, w1); wr(2, w2); wr(3, w3);
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int moc_stats_share(const moc_batch_t* B, const int32_t* leader_of_slide, int slide0, int n, moc_stream_t stream) {
@@ -141,5 +194,26 @@ extern "C" int moc_stats_share(const moc_batch_t* B, const int32_t* leader_of_sl
     const dim3 grid(moc_cdiv(B->max_rows, SH_CHUNK), n);
     stats_share_kernel<<<grid, SH_THREADS, 0, (hipStream_t)stream>>>(a);
     MOC_CHECK_LAUNCH("moc_stats_share");
+    return MOC_OK;
+}
+
+extern "C" int moc_kept_share(const moc_batch_t* B, const int32_t* leader_of_slide, int slide0, int n, moc_stream_t stream) {
+    MOC_REQUIRE(B && leader_of_slide, "moc_kept_share: null pointer");
+    if (int rc = moc_check_batch(B, "moc_kept_share")) return rc;
+    MOC_REQUIRE(slide0 >= 0 && n >= 1 && (int64_t)slide0 + n <= B->n_slides, "moc_kept_share: bad slide range [%d, %d + %d) of %d",
+                slide0, slide0, n, B->n_slides);
+    MOC_REQUIRE(n <= 65535, "moc_kept_share: at most 65535 slides per call, got %d", n);
+    if (!B->mask) return MOC_OK;                               // no lists: every slide keeps all of its rows
+    MOC_REQUIRE(B->kept && B->n_kept, "moc_kept_share: a masked batch without kept / n_kept");
+    KeptShareArgs a;
+    a.leader_of_slide = leader_of_slide;
+    a.row_off = B->row_off;
+    a.kept = B->kept;
+    a.n_kept = B->n_kept;
+    a.n_slides = B->n_slides; a.slide0 = slide0;
+    a.vec_ok = ((uintptr_t)B->kept & 15) == 0 ? 1 : 0;
+    const dim3 grid(moc_cdiv(B->max_rows, SH_CHUNK), n);
+    kept_share_kernel<<<grid, SH_THREADS, 0, (hipStream_t)stream>>>(a);
+    MOC_CHECK_LAUNCH("moc_kept_share");
     return MOC_OK;
 }

@@ -547,7 +547,7 @@ def train(model, train_loader, optimizer, device, args):
 _run_sets = {}
 
 
-def train_runs(models, train_loaders, optimizers, device, args, generators=None, per_run_adam=False):
+def train_runs(models, train_loaders, optimizers, device, args, generators=None, per_run_adam=False, banks=None, bank_of_run=None):
     """main_moc.py:378-410 for several independent runs at once -- what scripts/moc_train.sh:11-31 starts as one process per
     (fold, shot): `train(models[r], train_loaders[r], optimizers[r], device, args)` for every r, stepped in lockstep by one
     launch pair per meta-step (moc_amd.runs.TrainRuns; include/moc_hip.h moc_train_steps_runs).  Per run bit-identical to
@@ -558,17 +558,20 @@ def train_runs(models, train_loaders, optimizers, device, args, generators=None,
     split object and hold equal generator states share one draw and one score pass per pass -- DESIGN.md section 9h).
     `per_run_adam`: every run steps with its own optimizer's lr / betas / eps / weight_decay (re-read every pass) instead
     of the runs having to share them -- the cells of an lr x weight-decay grid in one lockstep chain.
+    `banks` = [(W, W_ext), ...] with `bank_of_run`: run r trains under banks[bank_of_run[r]] instead of the module's bank (a
+    bank grid: the runs of one split and generator state share one draw and one multi-bank score pass -- DESIGN.md section 9l).
     -> the TrainRuns object (kept for the next pass: call again with the same lists)."""
     from .runs import TrainRuns
     hp = lambda a: (a.topj, a.topk, tuple(sorted(a.discard_classifiers or ())))
     key = (tuple(id(m) for m in models), tuple(id(o) for o in optimizers), tuple(id(l) for l in train_loaders),
            tuple(hp(a) for a in args) if isinstance(args, (list, tuple)) else hp(args), tuple(len(l) for l in train_loaders),
-           bool(per_run_adam))
+           bool(per_run_adam), None if banks is None else (tuple((id(b[0]), id(b[1])) for b in banks), tuple(bank_of_run or ())))
     ent = _run_sets.get(key)
     if ent is None:
         if len(_run_sets) > 2:
             _run_sets.clear()
-        ent = _run_sets[key] = (TrainRuns(models, optimizers, train_loaders, device, args, generators=generators, per_run_adam=per_run_adam),
+        ent = _run_sets[key] = (TrainRuns(models, optimizers, train_loaders, device, args, generators=generators, per_run_adam=per_run_adam,
+                                          banks=banks, bank_of_run=bank_of_run),
                                 list(models), list(optimizers), list(train_loaders))
     rs = ent[0]
     rs.train_pass()

@@ -112,6 +112,13 @@ def get_args(argv=None):
                         "share a score pass per epoch and step in one lockstep chain, each with its own Adam (moc_amd.runs)")
     p.add_argument("--lrs", type=str, default=None, help="comma-separated learning rates (see --seeds)")
     p.add_argument("--wds", type=str, default=None, help="comma-separated weight decays (see --seeds)")
+    p.add_argument("--banks", default=None, nargs="+", type=_parse_bank, metavar="NAME=W.pt,W_ext.pt",
+                   help="prompt banks to compare in the few-shot setting: saved [D, C] and [D, Ce] tensors, one class count, "
+                        "Ce <= 16 (moc_amd.sweep --banks takes the same).  Trains a meta-learner under EVERY bank for every fold of "
+                        "--folds (or the one --fold) in this process; needs --seed: the banks' runs of a fold then draw the same "
+                        "masks and share one multi-bank score pass per epoch (moc_amd.runs).  Run (NAME, F) writes into "
+                        "{result_dir}/bank_{NAME}/ what `--fold F` alone writes with that bank installed, and "
+                        "{result_dir}/bank_grid_summary.csv holds one line per bank")
     p.add_argument("--patch_maps", type=str, default=None, choices=list(PATCH_MAP_CHOICES),
                    help="after main(), write per-patch maps (moc_amd.patch_maps) of these splits with the best checkpoint to "
                         "{result_dir}/patch_maps_shot_S_fold_F/{split}/ (default: none; test with --patch_maps_from)")
@@ -122,6 +129,11 @@ def get_args(argv=None):
 
 
 PATCH_MAP_CHOICES = ("none", "train", "val", "test", "all")
+
+
+def _parse_bank(text):
+    from .sweep import parse_bank
+    return parse_bank(text)
 
 
 def patch_map_splits(args):
@@ -900,16 +912,217 @@ def cli_optgrid(args):
     return out
 
 
+# ------------------------------------------------------------------ bank grids (--banks)
+def bankgrid_requested(args):
+    return getattr(args, "banks", None) is not None
+
+
+def bankgrid_dir(result_dir, name):
+    """Where the runs under bank NAME write: {result_dir}/bank_{NAME}."""
+    return os.path.join(result_dir, f"bank_{name}")
+
+
+def check_bankgrid_args(args):
+    """Refusals of a bank grid, from the command line and the banks' files alone (before any bag is loaded) -> [(name, W,
+    W_ext)] host tensors, or None without --banks."""
+    if not bankgrid_requested(args):
+        return None
+    if args.seed is None:
+        raise SystemExit("--banks needs --seed: the banks' runs of a fold start from one meta-learner and one mask stream")
+    if getattr(args, "shots", ""):
+        raise SystemExit("--banks does not combine with --shots: one --shot per grid")
+    if hgrid_requested(args):
+        raise SystemExit("--banks does not combine with --topjs / --topks / --discard_sets: one grid per command")
+    if optgrid_requested(args):
+        raise SystemExit(f"--banks does not combine with {OPT_GRID_FLAGS}: one grid per command")
+    if patch_map_splits(args) or args.patch_maps_from:
+        raise SystemExit("--banks does not combine with --patch_maps / --patch_maps_from: run one bank at a time")
+    if args.loader_seed_draw:
+        raise SystemExit("--banks does not combine with --loader_seed_draw: the runs draw their masks from private generators "
+                         "(no DataLoader base-seed draw)")
+    if args.cache_scores:
+        raise SystemExit("--banks does not combine with --cache_scores: a score cache belongs to one bank")
+    if args.ablation_study != "none":
+        raise SystemExit("--banks trains the meta-learner: the ablation study trains none")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("--banks is a one-GPU option (WORLD_SIZE > 1): run the grid without a launcher")
+    from .sweep import check_bank_names, load_bank_files
+    check_bank_names(args.banks)
+    return load_bank_files(args.banks, wide="a bank grid takes banks of at most {ce} (wide banks: one run_moc per bank)",
+                           mixed="run one grid per class count")
+
+
+def bankgrid_blocks(n_banks, n_folds, max_runs):
+    """The folds cut into blocks trained one after the other: whole folds -- a fold's banks stay together, they share the
+    score pass -- as many as fit `max_runs` runs (a fold is n_banks runs).  -> list of lists of fold positions.  Pure."""
+    if n_banks > max_runs:
+        raise SystemExit(f"--banks: {n_banks} banks in one process, at most {max_runs}")
+    per = max(1, max_runs // n_banks)
+    return [list(range(i, min(i + per, n_folds))) for i in range(0, n_folds, per)]
+
+
+def bankgrid_runs(args, names, folds):
+    """The runs' namespaces, bank-major (the leaders of the folds are consecutive runs: one score launch serves them all),
+    the folds inside a bank in the given order."""
+    import copy
+    out = []
+    for name in names:
+        for fold in folds:
+            a = copy.copy(args)
+            a.fold, a.bank, a.result_dir = fold, name, bankgrid_dir(args.result_dir, name)
+            out.append(a)
+    return out
+
+
+def bankgrid_bytes(fold_footprints, D, itemsize, C, n_banks):
+    """grid_bytes of n_banks runs per fold: the splits of a fold once, the work arrays -- per bank -- n_banks times."""
+    from . import engine
+    assert engine.bank_work_row_bytes(C) == 4 * (2 * C + 3) + 4 * (2 * C + 2) + 13 + 4 * C     # (grid_bytes' evaluation row)
+    return grid_bytes([fp for _ in range(n_banks) for fp in fold_footprints], D, itemsize, C)
+
+
+def write_bankgrid_summary(result_dir, names, folds, shot):
+    """{result_dir}/bank_grid_summary.csv: one line per bank in the given order -- the number of runs (folds) and the mean and
+    population standard deviation over them of the best validation AUC and of the test AUC at it, read from the banks'
+    best_results_* files (`best_val`, `test_at_best_val`).  -> path."""
+    rows = []
+    for name in names:
+        vals = []
+        for fold in folds:
+            with open(os.path.join(bankgrid_dir(result_dir, name), f"best_results_shot_{shot}_fold_{fold}.json")) as f:
+                r = json.load(f)
+            vals.append((r["best_val"], r["test_at_best_val"]))
+        v = np.asarray(vals, dtype=np.float64)
+        rows.append({"bank": name, "runs": len(vals), "best_val_mean": v[:, 0].mean(), "best_val_std": v[:, 0].std(),
+                     "test_auc_mean": v[:, 1].mean(), "test_auc_std": v[:, 1].std()})
+    path = os.path.join(result_dir, "bank_grid_summary.csv")
+    pd.DataFrame(rows).to_csv(path, index=False, float_format="%.17g")
+    return path
+
+
+def main_banks(args_list, names, folds, models, optimizers, loaders_of_fold, device, generators, banks):
+    """main() for the runs of a bank grid, bank-major (run g * len(folds) + i: bank g, fold folds[i]): the zero-shot numbers of
+    all banks from one read of every split (zs_evaluation_banks), the training passes in one TrainRuns with one multi-bank score
+    pass per mask group, and per epoch, fold and split one evaluation_banks over the models of that fold -- train and validation
+    always, test for the banks whose validation AUC improved.  Every run prints (behind a [bank NAME] tag), saves and returns
+    what main() does for it alone with its bank installed.  -> list of result dicts, in run order."""
+    G, F = len(names), len(folds)
+    run = lambda g, i: g * F + i
+    tag = lambda a: f"[bank {a.bank}] [fold {a.fold}]"
+    a0 = args_list[0]
+    st = [None] * (G * F)
+    for i in range(F):
+        zs = [(-1,) * G] * 3
+        if a0.check_zeroshot:
+            zs = [M.zs_evaluation_banks(ld, device, a0, banks) for ld in loaders_of_fold[i]]
+        for g in range(G):
+            a = args_list[run(g, i)]
+            os.makedirs(a.result_dir, exist_ok=True)
+            z = (zs[0][g], zs[1][g], zs[2][g])
+            if a0.check_zeroshot:
+                print(f"{tag(a)} Zero-shot Train: {z[0]}, Val: {z[1]}, Test: {z[2]}")
+                with open(os.path.join(a.result_dir, f"zs_results_shot_{a.shot}_fold_{a.fold}.json"), "w") as f:
+                    json.dump({"zs_train": z[0], "zs_val": z[1], "zs_test": z[2]}, f, indent=4)
+            st[run(g, i)] = dict(zs=z, best_val=0, test_at_best_val=0, test_acc_at_best_val=0, best_epoch=0,
+                                 model_path=os.path.join(a.result_dir, f"best_model_shot_{a.shot}_fold_{a.fold}.pt"))
+    trains = [loaders_of_fold[i][0] for _ in range(G) for i in range(F)]
+    of_run = [g for g in range(G) for _ in range(F)]
+    for epoch in range(getattr(a0, "epochs", 25)):
+        print("Epoch: ", epoch)
+        M.train_runs(models, trains, optimizers, device, a0, generators=generators, banks=banks, bank_of_run=of_run)
+        for i in range(F):
+            tr, va, te = loaders_of_fold[i]
+            ms = [models[run(g, i)] for g in range(G)]
+            ev_tr = M.evaluation_banks(ms, tr, device, a0, banks)
+            ev_va = M.evaluation_banks(ms, va, device, a0, banks)
+            better = [g for g in range(G) if ev_va[g]["auc"] > st[run(g, i)]["best_val"]]
+            ev_te = dict(zip(better, M.evaluation_banks([ms[g] for g in better], te, device, a0, [banks[g] for g in better]))) if better else {}
+            for g in range(G):
+                a, s_ = args_list[run(g, i)], st[run(g, i)]
+                if g in ev_te:
+                    print(f"{tag(a)} Epoch: {epoch}, Train: {ev_tr[g]}, Val: {ev_va[g]}, Test: {ev_te[g]}")
+                    s_.update(best_val=ev_va[g]["auc"], test_at_best_val=ev_te[g]["auc"], test_acc_at_best_val=ev_te[g]["acc"], best_epoch=epoch)
+                    torch.save(models[run(g, i)].state_dict(), s_["model_path"])
+                else:
+                    print(f"{tag(a)} Epoch: {epoch}, Train: {ev_tr[g]}, Val: {ev_va[g]}")
+    out = []
+    for r, (a, s_) in enumerate(zip(args_list, st)):
+        print(f"{tag(a)} Best Val: {s_['best_val']}, Test at Best Val: {s_['test_at_best_val']}, Test acc: {s_['test_acc_at_best_val']}, "
+              f"Best Epoch: {s_['best_epoch']}")
+        res = {"zero_shot_train": s_["zs"][0], "zero_shot_val": s_["zs"][1], "zero_shot_test": s_["zs"][2],
+               "best_val": s_["best_val"], "test_at_best_val": s_["test_at_best_val"], "test_acc_at_best_val": s_["test_acc_at_best_val"],
+               "best_epoch": s_["best_epoch"], "best_model_path": s_["model_path"]}
+        with open(os.path.join(a.result_dir, f"best_results_shot_{a.shot}_fold_{a.fold}.json"), "w") as f:
+            json.dump(res, f, indent=4)
+        out.append(res)
+    print("\nEnd training.")
+    return out
+
+
+def cli_bankgrid(args, bank_files):
+    """`--banks` (with --folds or the one --fold): every (bank, fold) run in this process."""
+    names = [n for n, _, _ in bank_files]
+    folds = folds_of_rank(args.folds, 0, 1) if args.folds else [int(args.fold)]
+    C_ = _synthetic_classes(args) if args.synthetic else len(_label_map(args))
+    for name, W, _ in bank_files:
+        if W.size(1) != C_ or W.size(0) != FEATURE_DIM:
+            raise SystemExit(f"--banks: {name}: W is [{W.size(0)}, {W.size(1)}]; this task needs [{FEATURE_DIM}, {C_}]")
+    device = torch.device("cuda", torch.cuda.current_device())
+    torch.cuda.set_device(device)
+    from . import runs as RUNS
+    blocks = bankgrid_blocks(len(names), len(folds), RUNS.MAX_RUNS)
+    # the footprint of the largest block before a bag is loaded
+    itemsize = 2 if args.bag_dtype in ("bf16", "fp16") else 4
+    fps = {a.fold: split_footprints(a) for a in bankgrid_runs(args, names[:1], folds)}
+    need = bankgrid_bytes([fps[folds[i]] for i in blocks[0]], FEATURE_DIM, itemsize, C_, len(names))
+    free = torch.cuda.mem_get_info(device)[0]
+    if need > free:
+        raise SystemExit(f"--banks: a block of {len(names)} bank(s) x {len(blocks[0])} fold(s) needs about {need / 2**30:.1f} GiB of "
+                         f"device memory, {free / 2**30:.1f} GiB are free: name fewer folds")
+    banks = [(W.to(device), We.to(device)) for _, W, We in bank_files]
+    adam = {"lr": args.lr, "weight_decay": args.weight_decay}
+    out = {}
+    for block in blocks:
+        fs = [folds[i] for i in block]
+        args_list = bankgrid_runs(args, names, fs)
+        loaders_of_fold, share = [], {}
+        for a in args_list[:len(fs)]:
+            loaders = prepare(a, device, share=share, share_train=True)
+            assert all(isinstance(ld, M.ResidentBags) for ld in loaders), "a bank grid needs resident splits (--resident 1)"
+            loaders_of_fold.append(loaders)
+        models, optimizers, gens = [], [], []
+        for a in args_list:
+            a.n_classes = args_list[0].n_classes
+            # exactly what the bank's own `--fold F --seed S` command does with the default generator: seed, build the
+            # meta-learner, and the masks follow from wherever that leaves the stream -- the banks' runs of a fold start from
+            # equal parameters and equal generator states and share their masks
+            torch.manual_seed(args.seed)
+            model = M.senet(FEATURE_DIM, 4).to(device)
+            g = torch.Generator()
+            g.set_state(torch.get_rng_state())
+            models.append(model)
+            optimizers.append(torch.optim.Adam(model.parameters(), **adam))
+            gens.append(g)
+        res = main_banks(args_list, names, fs, models, optimizers, loaders_of_fold, device, gens, banks)
+        for a, r in zip(args_list, res):
+            out[(a.bank, a.fold)] = r
+    print("bank grid summary:", write_bankgrid_summary(args.result_dir, names, folds, args.shot))
+    return [out[(n, f)] for n in names for f in folds]
+
+
 def cli(argv=None):
     args = get_args(argv)
     if args.summary:
         summary(args)
         return None
+    bank_files = check_bankgrid_args(args)
     check_optgrid_args(args)
     check_hgrid_args(args)
     check_patch_map_args(args)
     if not torch.cuda.is_available():
         raise RuntimeError("moc_amd needs a GPU: there is no CPU fallback")
+    if bank_files is not None:
+        return cli_bankgrid(args, bank_files)
     if optgrid_requested(args):
         return cli_optgrid(args)
     if hgrid_requested(args):

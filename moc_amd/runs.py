@@ -30,6 +30,13 @@ depend on none of topj / topk / discard_classifiers.  Runs whose split is the sa
 state form a MASK GROUP per pass (`mask_groups`): its first run, the leader, draws and is scored; the others' slots are
 filled by moc_stats_share, and the selection runs once per distinct (topj, discard) over that configuration's slides.
 MOC_RUNS_SHARE=0 makes every run its own leader.
+
+A BANK GRID (`banks` / `bank_of_run`: DESIGN.md section 9l) trains the runs of one (fold, seed) under several narrow prompt
+banks.  They draw the same masks too, but a bank's statistics are its own: the followers receive the kept-row lists alone
+(moc_kept_share) and ONE moc_scores_banks launch per leader block and pass of the bank set reads the leader's rows and writes
+bank g's statistics straight into the slots of the run that trains under bank g -- the per-bank pointers of the launch are
+the batch's own arrays advanced by the distance between the two runs' slots (`bank_score_plan`).
+MOC_RUNS_BANKS_FUSED=0 scores every (mask group, bank) with a moc_scores launch of its own instead: the same bits.
 """
 from __future__ import annotations
 
@@ -40,7 +47,7 @@ from concurrent.futures import ThreadPoolExecutor
 import torch
 
 from . import engine
-from ._lib import MocAdamHp, MocRuns, check, lib, ptr
+from ._lib import MocAdamHp, MocBankSet, MocRuns, check, lib, ptr
 from .engine import HIDDEN, MetaState, SlideBatch
 
 MAX_RUNS = 32           # runs of one TrainRuns (five shots x five folds and some); one moc_train_steps_runs call: 16
@@ -111,11 +118,62 @@ def consecutive_blocks(items):
     return out
 
 
+def bank_heads(leader, bank_of_run):
+    """{(mask-group leader, bank): the first run of that group that trains under that bank} -- the run whose slots the score
+    pass writes; the group's later runs under the same bank are filled from it (moc_stats_share).  Pure."""
+    head = {}
+    for r, (l, g) in enumerate(zip(leader, bank_of_run)):
+        head.setdefault((l, g), r)
+    return head
+
+
+def bank_score_plan(leader, bank_of_run, run_slide0, run_n, row_off_host, passes):
+    """The moc_scores_banks launches of one draw.  leader[r]: the mask-group leader of run r (mask_groups); bank_of_run[r]:
+    its bank; run_slide0 / run_n: first slide and slides of every run in the batch; row_off_host: first slot of every slide
+    (n_slides + 1 entries); passes: [(first bank, banks)] of the bank set (engine.plan_bank_passes).
+    -> [(leader slide0, n, first bank of the launch, [(bank, delta slots | None), ...])]: the launch reads slides
+    [slide0, slide0 + n) -- a block of consecutive leader runs -- under the consecutive banks listed, and bank g's statistics
+    of the slot row_off[b] + i land at slot row_off[b] + i + delta: the slots of the group's first run under bank g
+    (`bank_heads`).  None: no run of the block trains under that bank (its statistics go to scratch); a pass is trimmed to
+    the banks between its first and last bank with a run, and dropped when it has none.  Consecutive leaders share a launch
+    when their deltas agree bank for bank (runs ordered bank-major: always).
+    delta is ONE number per (leader, bank) because both runs visit the same slides in the same order: asserted here slide
+    by slide.  Pure: host integers only."""
+    R = len(leader)
+    assert len(bank_of_run) == R and len(run_slide0) == R and len(run_n) == R
+    per_leader = {}
+    for (l, g), h in bank_heads(leader, bank_of_run).items():
+        assert leader[l] == l and h >= l, "bank_score_plan: a leader is the first run of its group"
+        assert run_n[h] == run_n[l], f"bank_score_plan: runs {l} and {h} share masks but not the number of visits"
+        sl, sh = run_slide0[l], run_slide0[h]
+        d = row_off_host[sh] - row_off_host[sl]
+        for k in range(run_n[l] + 1):
+            assert row_off_host[sh + k] - row_off_host[sl + k] == d, \
+                f"bank_score_plan: runs {l} and {h} do not visit slides of the same sizes in the same order (visit {k})"
+        per_leader.setdefault(l, {})[g] = int(d)
+    blocks = []                                              # [[leader runs], {bank: delta}]
+    for l in sorted(per_leader):
+        if blocks and blocks[-1][0][-1] == l - 1 and blocks[-1][1] == per_leader[l]:
+            blocks[-1][0].append(l)
+        else:
+            blocks.append([[l], per_leader[l]])
+    plan = []
+    for runs_, deltas in blocks:
+        s0, n = run_slide0[runs_[0]], sum(run_n[r] for r in runs_)
+        for g0, ng in passes:
+            present = [g for g in range(g0, g0 + ng) if g in deltas]
+            if present:
+                plan.append((s0, n, present[0], [(g, deltas.get(g)) for g in range(present[0], present[-1] + 1)]))
+    return plan
+
+
 class TrainRuns:
     """R (model, optimizer, resident train split) triples trained in lockstep.  `generators`: one CPU torch.Generator
-    per run -- the run's mask stream (default: fresh generators seeded from the default generator, in run order)."""
+    per run -- the run's mask stream (default: fresh generators seeded from the default generator, in run order).
+    `banks`: [(W [D, C], W_ext [D, Ce]), ...] of one C, every Ce <= 16, and `bank_of_run[r]`: the bank run r trains under (a
+    bank grid; the module's classifier bank is neither read nor changed).  Default: every run under the module's bank."""
 
-    def __init__(self, models, optimizers, splits, device, args, generators=None, per_run_adam=False):
+    def __init__(self, models, optimizers, splits, device, args, generators=None, per_run_adam=False, banks=None, bank_of_run=None):
         from . import main_moc as M
         # per_run_adam: every run steps with its OWN optimizer's lr / betas / eps / weight_decay (moc_train_steps_runs_hp) --
         # the cells of an lr x weight-decay grid stay in one lockstep chain; default: the runs must share them
@@ -139,6 +197,22 @@ class TrainRuns:
         dt, D = splits[0].X.dtype, splits[0].X.size(1)
         assert all(sp.X.dtype == dt and sp.X.size(1) == D for sp in splits), "train_runs: one storage type and width"
         assert not any(sp.loader_seed_draw for sp in splits), "train_runs: loader_seed_draw splits are not batched"
+        if banks is not None:                                # refused before anything is allocated
+            banks = [tuple(b) for b in banks]
+            assert banks and all(len(b) == 2 and b[0].dim() == 2 and b[1].dim() == 2 for b in banks), "train_runs: banks = [(W, W_ext), ...]"
+            assert bank_of_run is not None and len(bank_of_run) == R and all(0 <= int(g) < len(banks) for g in bank_of_run), \
+                "train_runs: bank_of_run names one of the banks for every run"
+            assert all(b[0].size(1) == args.n_classes for b in banks), \
+                f"train_runs: banks of different C do not share a pass (n_classes = {args.n_classes}; got {[int(b[0].size(1)) for b in banks]})"
+            assert all(b[1].size(1) <= engine.BANK_SET_MAX_CE for b in banks), \
+                f"train_runs: a bank wider than {engine.BANK_SET_MAX_CE} columns ({[int(b[1].size(1)) for b in banks]}) trains in a run of its own"
+            assert all(b[0].size(0) == D and b[1].size(0) == D for b in banks), "train_runs: the banks are for another width"
+            assert os.environ.get("MOC_CACHE_SCORES", "0") != "1" and not any(sp.cache_scores for sp in splits), \
+                "train_runs: a score cache belongs to one bank (cache_scores splits and banks do not combine)"
+        else:
+            assert bank_of_run is None, "train_runs: bank_of_run without banks"
+        self.bank_of_run = None if banks is None else [int(g) for g in bank_of_run]
+        self.banks_fused = os.environ.get("MOC_RUNS_BANKS_FUSED", "1") != "0"
         if generators is None:
             generators = []
             for _ in range(R):
@@ -167,20 +241,29 @@ class TrainRuns:
                 labels.append(sp.labels[k])
                 rows += sp.sizes[k]
             self.run_rows.append((sum(s_ for s_ in sizes) - rows, rows))
-        bank = M._bank_for(self.X, device)
+        self.bank_set = self.banks_alone = self._bank_scratch = None
+        if banks is None:
+            bank = M._bank_for(self.X, device)
+        else:
+            # one image for all banks; the batch struct's Ce is read by the score pass alone (every launch of one carries its
+            # own bank's), so the batch keeps the largest
+            bank = self.bank_set = engine.BankSet(banks, self.X.dtype, device)
+            if not self.banks_fused:
+                self.banks_alone = [engine.Bank(W_, We_, self.X.dtype, device) for W_, We_ in banks]
         assert bank.C == args.n_classes
+        batch_Ce = bank.Ce if banks is None else max(bank.Ce)
         self.bank, self.args, self.args_list = bank, args, args_list
         T = sum(sizes)
         # (the batch's own topj / discard: run 0's; its topk: the largest, which sizes the work arrays -- every launch of a
         # grid takes a copy of the struct carrying its configuration's values)
-        self.batches = [SlideBatch(self.X, sizes, bank.C, bank.Ce, args.topj, max(k for _, k, _ in self.cfg), args.discard_classifiers,
+        self.batches = [SlideBatch(self.X, sizes, bank.C, batch_Ce, args.topj, max(k for _, k, _ in self.cfg), args.discard_classifiers,
                                    mask=torch.ones(T, dtype=torch.uint8), x_starts=starts) for _ in range(2)]
         # (round 4 measurements, profiles/NOTES.md: the meta-steps crawl while a score pass streams beside them whether or not
         # it leaves them compute units, so phase A here runs at full width; MOC_RUNS_RESERVE_CUS brings the reservation back)
         self.reserve = int(os.environ.get("MOC_RUNS_RESERVE_CUS", "0"))
         self.lookahead = os.environ.get("MOC_RUNS_LOOKAHEAD", "0") != "0"
         self.upload_flags = os.environ.get("MOC_RUNS_UPLOAD_FLAGS", "0") != "0"    # (measured: no gain from the copy)
-        if bank.Ce <= 16 and self.reserve > 0:
+        if banks is None and bank.Ce <= 16 and self.reserve > 0:
             for b in self.batches:
                 b.reserve_cus(self.reserve)
         if os.environ.get("MOC_CACHE_SCORES", "0") == "1" or all(sp.cache_scores for sp in splits):
@@ -397,9 +480,13 @@ class TrainRuns:
             batch.use_host_mask(self.flags[i], kept, max_kept)
         scored = sum(self.run_n[r] for r in range(self.R) if leader[r] == r)
         # one configuration and nobody to share with: the batch's own four launches, as ever
-        plain = scored == batch.n_slides and len(set((j, d) for j, _, d in self.cfg)) == 1
+        plain = scored == batch.n_slides and len(set((j, d) for j, _, d in self.cfg)) == 1 and self.bank_set is None
         self.pass_info[turn] = {"leader": leader, "plain": plain,
                                 "report": {"slides": batch.n_slides, "scored_slides": scored, "shared_slides": batch.n_slides - scored}}
+        if self.bank_set is not None:
+            plan = bank_score_plan(leader, self.bank_of_run, self.run_slide0, self.run_n, batch.row_off_host, self.bank_set.passes)
+            self.pass_info[turn]["plan"] = plan
+            self.pass_info[turn]["report"]["bank_passes"] = len(plan) if self.banks_fused else 0
         self.last_phase_a = self.pass_info[turn]["report"]
         if plain:
             if head_only:
@@ -409,7 +496,8 @@ class TrainRuns:
         else:
             # head: the leaders' kept-row lists (a launch per block of consecutive leader runs)
             bank = self.bank
-            assert bank.D == batch.D and bank.C == batch.C and bank.Ce == batch.Ce and bank.dtype == batch.X.dtype
+            assert bank.D == batch.D and bank.C == batch.C and bank.dtype == batch.X.dtype
+            assert batch.Ce == (bank.Ce if self.bank_set is None else max(bank.Ce))
             batch._layout(engine.COMPACT_STATS and batch.Ce > 16)
             batch._n_sel_stale()
             for s0, n_ in self._slide_blocks([r for r in range(self.R) if leader[r] == r]):
@@ -433,28 +521,20 @@ class TrainRuns:
             batch.phase_a_tail(self.bank)
             return
         leader, st = info["leader"], engine._stream()
-        for s0, n_ in self._slide_blocks([r for r in range(self.R) if leader[r] == r]):
-            v = self._view(batch.c, s0, n_)
-            if batch.stats_cache is not None:
-                cache, compact = batch.stats_cache
-                assert compact == bool(batch.c.flags & engine._lib.MOC_STATS_COMPACT) and cache.size(1) == self.X.size(0)
-                check(lib().moc_scores_from_cache(C.byref(v), ptr(cache), cache.size(1), st), "moc_scores_from_cache")
-            else:
-                check(lib().moc_scores(C.byref(v), ptr(self.bank.image), st), "moc_scores")
-        if any(leader[r] != r for r in range(self.R)):
-            # the followers' slots: kept rows, statistics and cleared union flags from their leaders' (moc_stats_share)
-            key = tuple(leader)
-            lead = self._lead_dev.get(key)
-            if lead is None:
-                if len(self._lead_dev) > 8:
-                    self._lead_dev.clear()
-                of_slide = []
-                for r in range(self.R):
-                    d = self.run_slide0[leader[r]] - self.run_slide0[r]
-                    of_slide += [-1 if d == 0 else s_ + d for s_ in range(self.run_slide0[r], self.run_slide0[r] + self.run_n[r])]
-                lead = self._lead_dev[key] = torch.tensor(of_slide, dtype=torch.int32).to(self.device)
-                lead.record_stream(self.side)
-            check(lib().moc_stats_share(C.byref(batch.c), ptr(lead), 0, batch.n_slides, st), "moc_stats_share")
+        if self.bank_set is not None:
+            self._score_banks(batch, info, st)
+        else:
+            for s0, n_ in self._slide_blocks([r for r in range(self.R) if leader[r] == r]):
+                v = self._view(batch.c, s0, n_)
+                if batch.stats_cache is not None:
+                    cache, compact = batch.stats_cache
+                    assert compact == bool(batch.c.flags & engine._lib.MOC_STATS_COMPACT) and cache.size(1) == self.X.size(0)
+                    check(lib().moc_scores_from_cache(C.byref(v), ptr(cache), cache.size(1), st), "moc_scores_from_cache")
+                else:
+                    check(lib().moc_scores(C.byref(v), ptr(self.bank.image), st), "moc_scores")
+            if any(leader[r] != r for r in range(self.R)):
+                # the followers' slots: kept rows, statistics and cleared union flags from their leaders' (moc_stats_share)
+                check(lib().moc_stats_share(C.byref(batch.c), ptr(self._leader_of_slide(leader)), 0, batch.n_slides, st), "moc_stats_share")
         batch._n_sel_stale()
         by_sel = {}
         for r, (j, _, d) in enumerate(self.cfg):               # moc_select / moc_gather_candidates read topj and discard_bits only
@@ -466,6 +546,61 @@ class TrainRuns:
                 check(lib().moc_select(C.byref(v), st), "moc_select")
                 check(lib().moc_gather_candidates(C.byref(v), None, st), "moc_gather_candidates")
         batch._n_sel_request()
+
+    def _leader_of_slide(self, source, tag=None):
+        """Device int32 [n_slides] for the share kernels: the slide that slide b copies from -- slide k of run source[r] for slide
+        k of run r -- or -1 where source[r] == r.  Kept per (tag, source)."""
+        key = (tag, tuple(source))
+        lead = self._lead_dev.get(key)
+        if lead is None:
+            if len(self._lead_dev) > 8:
+                self._lead_dev.clear()
+            of_slide = []
+            for r in range(self.R):
+                d = self.run_slide0[source[r]] - self.run_slide0[r]
+                of_slide += [-1 if d == 0 else s_ + d for s_ in range(self.run_slide0[r], self.run_slide0[r] + self.run_n[r])]
+            lead = self._lead_dev[key] = torch.tensor(of_slide, dtype=torch.int32).to(self.device)
+            lead.record_stream(self.side)
+        return lead
+
+    def _score_banks(self, batch, info, st):
+        """The score pass of a bank grid (behind the leaders' moc_mask_compact): the lists to every follower, then bank g's
+        statistics of a mask group into the slots of the group's first run under bank g, then to the group's other runs
+        under that bank."""
+        leader, bs, R = info["leader"], self.bank_set, self.R
+        if any(leader[r] != r for r in range(R)):
+            check(lib().moc_kept_share(C.byref(batch.c), ptr(self._leader_of_slide(leader)), 0, batch.n_slides, st), "moc_kept_share")
+        heads = bank_heads(leader, self.bank_of_run)
+        cb = type(batch.c).from_buffer_copy(batch.c)          # full layout, static walk over the whole chip
+        cb.tile_ticket = cb.cu_reserved = None
+        cb.flags = 0
+        if self.banks_fused:
+            T = batch.total
+            for s0, n_, g0, entries in info["plan"]:
+                S = MocBankSet(n_banks=len(entries), C=bs.C, image=bs.image.data_ptr() + g0 * bs.tile_bytes)
+                for i, (g, d) in enumerate(entries):
+                    S.Ce[i] = bs.Ce[g]
+                    if d is None:                             # nobody in this block trains under bank g
+                        if self._bank_scratch is None:
+                            self._bank_scratch = (torch.empty((2 * bs.C + 3, T), dtype=torch.float32, device=self.device),
+                                                  torch.empty(T, dtype=torch.uint8, device=self.device))
+                            for t_ in self._bank_scratch:
+                                t_.record_stream(self.side)
+                        S.stats[i], S.sel_flag[i] = ptr(self._bank_scratch[0]), ptr(self._bank_scratch[1])
+                    else:
+                        # the last slot written is the last slot of the run under bank g (bank_score_plan asserts the layout)
+                        assert 0 <= d and batch.row_off_host[s0 + n_] + d <= T
+                        S.stats[i], S.sel_flag[i] = ptr(batch.stats) + 4 * d, ptr(batch.sel_flag) + d
+                check(lib().moc_scores_banks(C.byref(self._view(cb, s0, n_)), C.byref(S), st), "moc_scores_banks")
+        else:
+            for (_, g), h in heads.items():
+                cb.Ce = bs.Ce[g]
+                v = self._view(cb, self.run_slide0[h], self.run_n[h])
+                check(lib().moc_scores(C.byref(v), ptr(self.banks_alone[g].image), st), "moc_scores")
+        source = [heads[(leader[r], self.bank_of_run[r])] for r in range(R)]
+        if any(source[r] != r for r in range(R)):             # same masks, same bank: topj / topk / discard / Adam values differ
+            check(lib().moc_stats_share(C.byref(batch.c), ptr(self._leader_of_slide(source, "bank")), 0, batch.n_slides, st),
+                  "moc_stats_share")
 
     def train_pass(self):
         """One pass (epoch) of every run: main_moc.train for each of them, in lockstep."""

@@ -138,33 +138,45 @@ def check_args(a):
 MAX_BANK_CE = 16       # engine.BANK_SET_MAX_CE (kept literal here, as MAX_TOPK is)
 
 
-def check_bank_args(a):
-    """--banks: refusals from the command line and the files alone, before any GPU work -> ([(name, W, W_ext)] host
-    tensors, the checkpoints' state_dicts: none, one, or one per bank)."""
-    names = [n for n, _, _ in a.banks]
+def check_bank_names(specs, flag="--banks"):
+    """[(name, W file, W_ext file)]: duplicate names and missing files are refused (SystemExit).  Shared with run_moc --banks."""
+    names = [n for n, _, _ in specs]
     dup = sorted({n for n in names if names.count(n) > 1})
     if dup:
-        raise SystemExit(f"--banks: duplicate bank name {dup[0]!r} (a name is its bank's output directory)")
-    for _, fw, fe in a.banks:
+        raise SystemExit(f"{flag}: duplicate bank name {dup[0]!r} (a name is its bank's output directory)")
+    for _, fw, fe in specs:
         for f in (fw, fe):
             if not os.path.isfile(f):
-                raise SystemExit(f"--banks: {f}: no such file")
-    n_ckpt = len(a.ckpt or ())
-    if n_ckpt not in (0, 1, len(a.banks)):
-        raise SystemExit(f"--ckpt: one checkpoint for all banks or one per bank ({len(a.banks)}); got {n_ckpt}")
+                raise SystemExit(f"{flag}: {f}: no such file")
+
+
+def load_bank_files(specs, flag="--banks", wide="the bank axis takes banks of at most {ce} (wide banks: one plain sweep per bank)",
+                    mixed="run one sweep per class count"):
+    """The banks' tensors from their files -> [(name, W, W_ext)] host fp32; a file that does not hold W [D, C] / W_ext [D, Ce]
+    with Ce > C, a bank wider than MAX_BANK_CE columns and banks of different C are refused (SystemExit)."""
     banks = []
-    for name, fw, fe in a.banks:
+    for name, fw, fe in specs:
         W, We = (torch.load(f, map_location="cpu") for f in (fw, fe))
         if not (torch.is_tensor(W) and torch.is_tensor(We) and W.dim() == 2 and We.dim() == 2 and W.size(0) == We.size(0)
                 and We.size(1) > W.size(1)):
-            raise SystemExit(f"--banks: {name}: need saved tensors W [D, C] and W_ext [D, Ce] with Ce > C")
+            raise SystemExit(f"{flag}: {name}: need saved tensors W [D, C] and W_ext [D, Ce] with Ce > C")
         if We.size(1) > MAX_BANK_CE:
-            raise SystemExit(f"--banks: {name}: Ce={We.size(1)} columns; the bank axis takes banks of at most {MAX_BANK_CE} "
-                             "(wide banks: one plain sweep per bank)")
+            raise SystemExit(f"{flag}: {name}: Ce={We.size(1)} columns; " + wide.format(ce=MAX_BANK_CE))
         banks.append((name, W.float(), We.float()))
     Cs = sorted({int(W.size(1)) for _, W, _ in banks})
     if len(Cs) != 1:
-        raise SystemExit(f"--banks: banks of different C ({Cs}) do not share a score pass; run one sweep per class count")
+        raise SystemExit(f"{flag}: banks of different C ({Cs}) do not share a score pass; {mixed}")
+    return banks
+
+
+def check_bank_args(a):
+    """--banks: refusals from the command line and the files alone, before any GPU work -> ([(name, W, W_ext)] host
+    tensors, the checkpoints' state_dicts: none, one, or one per bank)."""
+    check_bank_names(a.banks)
+    n_ckpt = len(a.ckpt or ())
+    if n_ckpt not in (0, 1, len(a.banks)):
+        raise SystemExit(f"--ckpt: one checkpoint for all banks or one per bank ({len(a.banks)}); got {n_ckpt}")
+    banks = load_bank_files(a.banks)
     sds = []
     if n_ckpt:
         from .predict import load_checkpoints
