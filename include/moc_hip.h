@@ -555,6 +555,28 @@ int moc_adapter_logits(const float* X, int64_t N, int c, const float* const* W1,
                        const float* G /*nullable*/, const float* Wc, int C, float ratio, float* logits,
                        void* workspace, size_t workspace_bytes, moc_stream_t stream);
 
+/* f3: the Nystrom attention layer of TransMIL (models/model_mil.py:105-122; moc_amd/nystrom.py),
+ * forward only, for the no-grad passes.  Built for ONE shape -- heads = 8, dim_head = 64, landmarks = 256, a residual
+ * convolution of at most 33 (odd) taps, batch 1 -- anything else is refused before a launch (moc_nystrom_workspace: 0).
+ * qkv [n_pad, 1536] device fp32 as to_qkv leaves it, token-major: q of head h at columns 64 h .. 64 h + 63, k at 512 + 64 h,
+ * v at 1024 + 64 h; n_pad a multiple of 256 (front-padding rows are ordinary rows: nothing is masked).
+ *   moc_nystrom_landmark_values:  W[h] = softmax_over_tokens(q_l[h] k[h]^T) v[h]            W, q_l: [8, 256, 64]
+ *       (q_l: the scaled segment means of q).  The token range is split in ranges of 512 whose (max, sum, accumulator)
+ *       partials go through `ws` (moc_nystrom_workspace bytes) and are merged in index order: no atomics, same bits on
+ *       every call.
+ *   moc_nystrom_token_values:     out[i, 64 h ..] = softmax_256(scale q[i, h] k_l[h]^T) Y[h] + sum_t w[h, t] v[i + t - taps / 2, h]
+ *       k_l, Y: [8, 256, 64]; conv_w [8, taps] (rows outside [0, n_pad) count as zero) or null for no residual (taps is
+ *       then ignored); out [n_pad, 512] fp32, token-major, written.
+ * All pointers 16-byte aligned.  Products are fp32 (v_mfma_f32_16x16x4_f32).  Additive to ABI 20: the version number is
+ * unchanged. */
+size_t moc_nystrom_workspace(int64_t n_pad, int heads, int dim_head, int landmarks);   /* 0: unsupported shape */
+int moc_nystrom_landmark_values(const float* qkv, int64_t n_pad, int heads, int dim_head, int landmarks,
+                                const float* q_l /* [h, m, d], already scaled */, float* W /* [h, m, d] */,
+                                void* ws, size_t ws_bytes, moc_stream_t stream);
+int moc_nystrom_token_values(const float* qkv, int64_t n_pad, int heads, int dim_head, int landmarks,
+                             const float* k_l, const float* Y, const float* conv_w /* [h, taps] or NULL */, int taps,
+                             float scale, float* out /* [n_pad, h*d] */, moc_stream_t stream);
+
 /* a10-a15 fused: `n` consecutive meta-steps (one slide each, slides slide0..slide0+n-1 in
  * order, one Adam step per slide: main_moc.py:380-410), parameters and Adam moments
  * updated in place.  Per-slide loss/pooled land in ws->loss / ws->pooled. */

@@ -1310,3 +1310,57 @@ def adapter_logits(feat: torch.Tensor, W1s, W2s, router, classifier: torch.Tenso
                                    ptr(classifier), Cc, C.c_float(float(ratio)), ptr(logits), ptr(ws), nbytes, _stream()),
           "moc_adapter_logits")
     return logits
+
+
+NYSTROM_HEADS, NYSTROM_DIM_HEAD, NYSTROM_LANDMARKS, NYSTROM_MAX_TAPS = 8, 64, 256, 33   # what moc_nystrom_* is built for
+
+
+def _nystrom_qkv(qkv: torch.Tensor, what: str) -> int:
+    assert qkv.is_cuda and qkv.dtype == torch.float32, f"{what}: fp32 tensors on the GPU (no CPU fallback)"
+    assert qkv.dim() == 2 and qkv.shape[1] == 3 * NYSTROM_HEADS * NYSTROM_DIM_HEAD and qkv.is_contiguous(), \
+        f"{what}: qkv must be a contiguous [n_pad, 1536]"
+    n_pad = qkv.shape[0]
+    assert n_pad >= NYSTROM_LANDMARKS and n_pad % NYSTROM_LANDMARKS == 0, f"{what}: n_pad={n_pad} is no multiple of 256"
+    return n_pad
+
+
+def _nystrom_hmd(t: torch.Tensor, name: str, what: str) -> torch.Tensor:
+    assert t.is_cuda and t.dtype == torch.float32, f"{what}: fp32 tensors on the GPU (no CPU fallback)"
+    assert t.shape == (NYSTROM_HEADS, NYSTROM_LANDMARKS, NYSTROM_DIM_HEAD), f"{what}: {name} must be [8, 256, 64]"
+    return t.detach().contiguous()
+
+
+def nystrom_landmark_values(qkv: torch.Tensor, q_l: torch.Tensor) -> torch.Tensor:
+    """Kernel A of the fused Nystrom forward (include/moc_hip.h moc_nystrom_landmark_values): W [8, 256, 64], for each
+    head softmax_over_tokens(q_l k^T) v, from qkv [n_pad, 1536] as to_qkv leaves it and the scaled landmark queries q_l
+    [8, 256, 64].  No score matrix is formed; no gradient."""
+    what = "nystrom_landmark_values"
+    n_pad = _nystrom_qkv(qkv, what)
+    q_l = _nystrom_hmd(q_l, "q_l", what)
+    W = torch.empty_like(q_l)
+    nbytes = lib().moc_nystrom_workspace(n_pad, NYSTROM_HEADS, NYSTROM_DIM_HEAD, NYSTROM_LANDMARKS)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=qkv.device)
+    check(lib().moc_nystrom_landmark_values(ptr(qkv.detach()), n_pad, NYSTROM_HEADS, NYSTROM_DIM_HEAD, NYSTROM_LANDMARKS,
+                                            ptr(q_l), ptr(W), ptr(ws), nbytes, _stream()), "moc_nystrom_landmark_values")
+    return W
+
+
+def nystrom_token_values(qkv: torch.Tensor, k_l: torch.Tensor, Y: torch.Tensor, conv_w, scale: float) -> torch.Tensor:
+    """Kernel B of the fused Nystrom forward (moc_nystrom_token_values): out [n_pad, 512], token-major, for each token
+    and head softmax_256(scale q k_l^T) Y + the depth-wise residual convolution of v with conv_w [8, taps] (None: no
+    residual).  k_l, Y: [8, 256, 64].  No gradient."""
+    what = "nystrom_token_values"
+    n_pad = _nystrom_qkv(qkv, what)
+    k_l, Y = _nystrom_hmd(k_l, "k_l", what), _nystrom_hmd(Y, "Y", what)
+    taps = 0
+    if conv_w is not None:
+        assert conv_w.is_cuda and conv_w.dtype == torch.float32, f"{what}: fp32 tensors on the GPU (no CPU fallback)"
+        assert conv_w.dim() == 2 and conv_w.shape[0] == NYSTROM_HEADS, f"{what}: conv_w must be [8, taps]"
+        taps = conv_w.shape[1]
+        assert taps % 2 == 1 and taps <= NYSTROM_MAX_TAPS, f"{what}: taps={taps} must be odd and at most 33"
+        conv_w = conv_w.detach().contiguous()
+    out = torch.empty((n_pad, NYSTROM_HEADS * NYSTROM_DIM_HEAD), dtype=torch.float32, device=qkv.device)
+    check(lib().moc_nystrom_token_values(ptr(qkv.detach()), n_pad, NYSTROM_HEADS, NYSTROM_DIM_HEAD, NYSTROM_LANDMARKS, ptr(k_l),
+                                         ptr(Y), ptr(conv_w), taps, C.c_float(float(scale)), ptr(out), _stream()),
+          "moc_nystrom_token_values")
+    return out

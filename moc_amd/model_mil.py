@@ -149,6 +149,15 @@ class TransMIL(nn.Module):
         self.norm = nn.LayerNorm(512)
         self._fc2 = nn.Linear(512, self.n_classes)
 
+    @property
+    def fused(self) -> bool:
+        """Both layers' attention on the fused Nystrom forward (nystrom.NystromAttention.forward_fused) in no-grad passes."""
+        return bool(self.layer1.attn.fused and self.layer2.attn.fused)
+
+    @fused.setter
+    def fused(self, on: bool):
+        self.layer1.attn.fused = self.layer2.attn.fused = bool(on)
+
     def _tokens(self, data):
         """fc1, wrap-around padding to a square, class token, layer 1, PPEG, layer 2 (:236-266)."""
         if len(data.shape) == 2:

@@ -10,7 +10,8 @@ convolution residual on the values.  Module / parameter names follow the package
 so that a TransMIL checkpoint trained with it loads.  Checked here against what CAN be checked: exact softmax
 attention in the limit where every token is its own landmark, the pseudo-inverse against `torch.linalg.pinv`, shapes
 and padding (tests/test_baselines_cpu.py).  Plain torch operations: this is a signature shim (SURVEY.md section 8,
-f3), not part of the HIP hot path."""
+f3); with `fused = True` the no-grad forward runs on the kernels of csrc/moc_nystrom.hip instead, which are checked
+against THIS restatement (tests/test_gpu_nystrom.py) and pin nothing more than it does."""
 from __future__ import annotations
 
 from math import ceil
@@ -47,7 +48,54 @@ class NystromAttention(nn.Module):
             k = residual_conv_kernel
             self.res_conv = nn.Conv2d(heads, heads, (k, 1), padding=(k // 2, 0), groups=heads, bias=False)
 
+    # True: forward takes forward_fused (the HIP kernels of moc_nystrom.hip wherever they apply, this torch code elsewhere)
+    fused = False
+
     def forward(self, x, mask=None, return_attn=False):
+        if self.fused:
+            return self.forward_fused(x, mask=mask, return_attn=return_attn)
+        return self._forward_torch(x, mask=mask, return_attn=return_attn)
+
+    def _fused_applies(self, x, mask, return_attn) -> bool:
+        if mask is not None or return_attn:
+            return False
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            return False                                  # the kernels form no gradient
+        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.shape[0] == 1 and x.shape[1] >= 1
+                and x.is_contiguous()):
+            return False
+        if not (self.heads == 8 and self.to_qkv.out_features == 3 * 8 * 64 and self.num_landmarks == 256
+                and all(p.dtype == torch.float32 and p.is_cuda for p in self.parameters())):
+            return False
+        return not self.residual or tuple(self.res_conv.kernel_size) == (33, 1)
+
+    def forward_fused(self, x, mask=None, return_attn=False):
+        """The no-grad forward on the HIP kernels: to_qkv, the landmark means, attn2 and its
+        pseudo-inverse in torch; W = softmax(q_l k^T) v (kernel A); Y = pinv W; softmax(q k_l^T) Y + res_conv(v) (kernel
+        B); to_out.  Neither [8, n, 256] score matrix is formed.  Wherever the kernels do not apply -- a gradient is
+        wanted, x is not a contiguous fp32 [1, n, dim] CUDA tensor, another layer shape, mask / return_attn -- this is
+        the torch code above, bit for bit."""
+        if not self._fused_applies(x, mask, return_attn):
+            return self._forward_torch(x, mask=mask, return_attn=return_attn)
+        from . import engine
+        n, h, m = x.shape[1], self.heads, self.num_landmarks
+        if n % m > 0:
+            x = F.pad(x, (0, 0, m - (n % m), 0), value=0)
+        qkv = self.to_qkv(x)[0]                           # [n_pad, 1536]: q | k | v, each head-major in its 512 columns
+        l, inner = qkv.shape[0] // m, qkv.shape[1] // 3
+        # the landmark means of q and k in one pass over their 1,024 columns; the scale (64 ** -0.5, a power of two) commutes
+        # with the sum and the division exactly, so it is applied to the [256, 512] means and not to the [n, 512] queries
+        means = qkv[:, :2 * inner].reshape(m, l, 2 * inner).sum(dim=1) / l
+        q_l = (means[:, :inner] * self.scale).reshape(m, h, -1).transpose(0, 1).contiguous()                        # h m d
+        k_l = means[:, inner:].reshape(m, h, -1).transpose(0, 1).contiguous()
+        attn2 = (q_l @ k_l.transpose(-1, -2)).softmax(dim=-1)
+        pinv = moore_penrose_iter_pinv(attn2.unsqueeze(0), self.pinv_iterations)[0]
+        W = engine.nystrom_landmark_values(qkv, q_l)      # softmax over the tokens of q_l k^T, times v
+        conv_w = self.res_conv.weight.reshape(h, -1) if self.residual else None
+        out = engine.nystrom_token_values(qkv, k_l, pinv @ W, conv_w, self.scale)
+        return self.to_out(out.unsqueeze(0))[:, -n:]
+
+    def _forward_torch(self, x, mask=None, return_attn=False):
         assert mask is None and not return_attn, "the reference calls attn(x) only (models/model_mil.py:119)"
         b, n, _ = x.shape
         h, m = self.heads, self.num_landmarks

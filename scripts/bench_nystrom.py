@@ -1,0 +1,116 @@
+"""Row f3: time TransMIL's fused Nystrom forward (NystromAttention.forward_fused: moc_nystrom_landmark_values +
+moc_nystrom_token_values around the torch pieces) against the torch path (`fused = False`, unchanged from before the
+kernels existed), all under no_grad: the whole model on one bag, one attention layer alone, and each kernel alone against
+its two bounds -- the bytes of qkv it must read (plus the output it writes) and its products at the fp32 matrix peak
+(v_mfma_f32_16x16x4_f32).
+
+Each figure is the median and the minimum of `--iters` single runs, each between two events, after `--warmup` untimed
+runs.  "faster" is claimed only where the fused median is below the torch path's minimum.
+
+    python scripts/bench_nystrom.py [--n 15000] [--iters 30] [--json out.json]
+"""
+import argparse
+import json
+import math
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from moc_amd import engine  # noqa: E402
+from moc_amd.model_mil import TransMIL  # noqa: E402
+
+F32_MFMA_PEAK = 157.3e12      # v_mfma_f32_16x16x4_f32: 64 flop / clock / SIMD
+HBM_PEAK = 8.0e12
+H, D, M, TAPS = 8, 64, 256, 33
+
+
+def times_us(fn, iters, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(iters):
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        fn()
+        e.record()
+        e.synchronize()
+        out.append(s.elapsed_time(e) * 1e3)
+    return {"median_us": statistics.median(out), "min_us": min(out)}
+
+
+def pair(label, fn, switch, iters, warmup):
+    """fn timed with the flag off, then on."""
+    r = {}
+    for fused in (False, True):
+        switch(fused)
+        r["fused" if fused else "torch"] = times_us(fn, iters, warmup)
+    t, f = r["torch"], r["fused"]
+    r["fused_is_faster"] = f["median_us"] < t["min_us"]
+    print(f"{label:24s}: torch median {t['median_us']:9.1f} us (min {t['min_us']:9.1f})   fused median {f['median_us']:9.1f} us "
+          f"(min {f['min_us']:9.1f})   {'fused faster' if r['fused_is_faster'] else 'NOT faster'} "
+          f"(x{t['median_us'] / f['median_us']:.2f} on the medians)")
+    return r
+
+
+def kernel(label, fn, nbytes, flops, iters, warmup):
+    r = times_us(fn, iters, warmup)
+    sec = r["median_us"] * 1e-6
+    r.update(bytes=nbytes, flops=flops, bytes_per_s=nbytes / sec, flops_per_s=flops / sec,
+             hbm_bound_us=nbytes / HBM_PEAK * 1e6, mfma_bound_us=flops / F32_MFMA_PEAK * 1e6)
+    nearer = max(r["hbm_bound_us"], r["mfma_bound_us"])
+    r["fraction_of_nearer_bound"] = nearer / r["median_us"]
+    print(f"{label:24s}: median {r['median_us']:8.1f} us (min {r['min_us']:8.1f})   {nbytes / 1e6:6.1f} MB at "
+          f"{r['bytes_per_s'] / 1e12:.3f} TB/s (bound {r['hbm_bound_us']:.1f} us)   {flops / 1e9:5.2f} GFLOP at "
+          f"{r['flops_per_s'] / 1e12:.1f} TFLOP/s (bound {r['mfma_bound_us']:.1f} us)   {r['fraction_of_nearer_bound']:.2f} of the nearer bound")
+    return r
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=15000)
+    ap.add_argument("--iters", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+    assert a.iters >= 20
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(0)
+    bag = torch.randn(a.n, 512, generator=g).to(dev)
+    torch.manual_seed(1)
+    model = TransMIL(n_classes=2, size_arg="conch").to(dev).eval()
+    attn = model.layer1.attn
+    out = {"n": a.n}
+    with torch.no_grad():
+        side = math.ceil(math.sqrt(a.n))                                  # TransMIL pads the bag to a square, + class token
+        n_tok = side * side + 1
+        out["tokens"] = n_tok
+        x = torch.nn.functional.layer_norm(torch.randn(1, n_tok, 512, generator=g), (512,)).to(dev)
+        out["model"] = pair(f"TransMIL {a.n} x 512", lambda: model(bag), lambda on: setattr(model, "fused", on), a.iters, a.warmup)
+        out["layer"] = pair(f"one layer, {n_tok} tokens", lambda: attn(x), lambda on: setattr(attn, "fused", on), a.iters, a.warmup)
+        model.fused = False
+
+        n_pad = -(-n_tok // M) * M
+        out["n_pad"] = n_pad
+        qkv = attn.to_qkv(torch.nn.functional.pad(x, (0, 0, n_pad - n_tok, 0)))[0].contiguous()
+        l = n_pad // M
+        q_l = ((qkv[:, :512] * attn.scale).reshape(M, l, H, D).sum(1) / l).transpose(0, 1).contiguous()
+        k_l = (qkv[:, 512:1024].reshape(M, l, H, D).sum(1) / l).transpose(0, 1).contiguous()
+        Y = engine.nystrom_landmark_values(qkv, q_l)
+        w = attn.res_conv.weight.reshape(H, TAPS).contiguous()
+        scores = 2.0 * H * M * n_pad * D                                  # one [256, n] x 64 product per head
+        out["landmark_values"] = kernel("moc_nystrom_landmark_values", lambda: engine.nystrom_landmark_values(qkv, q_l),
+                                        2 * n_pad * 512 * 4, 2 * scores, a.iters, a.warmup)
+        out["token_values"] = kernel("moc_nystrom_token_values", lambda: engine.nystrom_token_values(qkv, k_l, Y, w, attn.scale),
+                                     3 * n_pad * 512 * 4, 2 * scores + 2.0 * n_pad * 512 * 48, a.iters, a.warmup)
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            json.dump(out, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
