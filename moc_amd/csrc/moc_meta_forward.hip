@@ -382,22 +382,70 @@ __global__ __launch_bounds__(256, BF16 ? 1 : 3) void meta_forward_kernel(FwdArgs
 // run on the bf16 matrix cores (fwd_split4 / fwd_mfma6): per wave D / 128 k-steps x six v_mfma_f32_16x16x32_bf16 (24 x 16
 // cycles at D = 512 instead of 32 x 32), the row split once by the wave that fetches it, the tile in LDS as three bf16 planes.
 // grid (ceil(S_bound/16), n), 1024 threads; D <= 1024.
+constexpr int GATE_STR = H + 4;                             // row stride of the gate chain's operands in LDS (floats; below)
 constexpr int FKS_PSTR = H + 4;                             // row stride of a partial tile in LDS (floats)
 __host__ __device__ constexpr int fks_lds_bytes(int D) {
-    return 3 * 16 * D * 2 + 4 * 16 * FKS_PSTR * 4 + 16 * (H + 1) * 4 + 16 * 4 * 4 + 4 * H * 4;
+    return 3 * 16 * D * 2 + 4 * 16 * FKS_PSTR * 4 + 16 * GATE_STR * 4 + 16 * 4 * 4 + 4 * GATE_STR * 4;
+}
+// The gate chain's operands in LDS: the hidden tile Hs [16] and W2 [4], rows of H floats at a stride of GATE_STR = H + 4
+// floats -- 17 sixteen-byte slots, so chunk c of row r lies in slot (r + c) mod 16 of the 256-byte bank row.  The one wave
+// that forms the 16 x 4 gates (lane = row * 4 + gate) reads a row as sixteen ds_read_b128 at immediate offsets from one
+// address: the rows one 16-lane group of such a read touches (four hidden rows, four W2 rows; lanes of one row share an
+// address) lie in distinct slots.  The writers keep storing one float per thread.
+// z = sum over h, ascending, of fmaf(Hs[r][h], W2[i][h], z) from 0: the chain every forward kernel runs for gate i of row r
+// (same order, same bits).  The operands come in groups of 3 + 3 reads through two buffers, a group requested before the
+// group ahead of it is consumed: 48 registers (all 32 reads at once would be 128, and 64 already cost the kernel scratch).
+template <int N>
+__device__ __forceinline__ void gate_load(const float4* hr, const float4* wr, float4 (&hv)[3], float4 (&wv)[3]) {
+#pragma unroll
+    for (int c = 0; c < N; ++c) { hv[c] = hr[c]; wv[c] = wr[c]; }
+}
+template <int N>
+__device__ __forceinline__ float gate_fma(const float4 (&hv)[3], const float4 (&wv)[3], float z) {
+#pragma unroll
+    for (int c = 0; c < N; ++c) {
+        z = fmaf(hv[c].x, wv[c].x, z);
+        z = fmaf(hv[c].y, wv[c].y, z);
+        z = fmaf(hv[c].z, wv[c].z, z);
+        z = fmaf(hv[c].w, wv[c].w, z);
+    }
+    return z;
+}
+__device__ __forceinline__ float gate_chain(const float* Hs, const float* W2s, int r, int i) {
+    static_assert(H == 64, "sixteen chunks: five groups of three and one");
+    const float4* hr = reinterpret_cast<const float4*>(Hs + r * GATE_STR);
+    const float4* wr = reinterpret_cast<const float4*>(W2s + i * GATE_STR);
+    float4 ha[3], wa[3], hb[3], wb[3];
+    gate_load<3>(hr, wr, ha, wa);
+    gate_load<3>(hr + 3, wr + 3, hb, wb);
+    float z = gate_fma<3>(ha, wa, 0.f);
+    gate_load<3>(hr + 6, wr + 6, ha, wa);
+    z = gate_fma<3>(hb, wb, z);
+    gate_load<3>(hr + 9, wr + 9, hb, wb);
+    z = gate_fma<3>(ha, wa, z);
+    gate_load<3>(hr + 12, wr + 12, ha, wa);
+    z = gate_fma<3>(hb, wb, z);
+    gate_load<1>(hr + 15, wr + 15, hb, wb);
+    z = gate_fma<3>(ha, wa, z);
+    z = gate_fma<1>(hb, wb, z);
+    return z;
 }
 // DQ = D / 256: every loop over a row's pieces or a quarter's fragments has a compile-time trip count.  STATS: the candidate
 // scores come from the score pass's statistics through sel_idx (cand_mode != 0: evaluation of a few slides); the training
 // step reads the materialised columns -- no dependent load, no branch between the barrier and the chain.
+// Waves per SIMD the kernel is held to (its own sixteen are four): 8 / 6 / 4 / 4 at D = 256 / 512 / 768 / 1024, what hipcc
+// gave it unasked before the gate chain read wide -- with only "four" to aim at it spends registers freely there (84-101
+// at D = 512, scratch at D >= 768: profiles/NOTES.md) and leaves fewer to whatever shares the compute unit with the forward.
+constexpr int fks_waves(int dq) { return dq == 1 ? 8 : dq == 2 ? 6 : 4; }
 template <int DQ, bool STATS>
-__global__ __launch_bounds__(1024) void meta_forward_ksplit_kernel(FwdArgs a) {
+__global__ __launch_bounds__(1024, fks_waves(DQ)) void meta_forward_ksplit_kernel(FwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int D = DQ * 256;
     uint4* xt = reinterpret_cast<uint4*>(smem);                                     // [3 terms][16][D/8] chunks, swizzled
     float* part = reinterpret_cast<float*>(smem + (size_t)3 * 16 * D * 2);          // [4][16][FKS_PSTR]
-    float (*Hs)[H + 1] = reinterpret_cast<float (*)[H + 1]>(part + 4 * 16 * FKS_PSTR);
-    float (*Gs)[4] = reinterpret_cast<float (*)[4]>(reinterpret_cast<float*>(Hs) + 16 * (H + 1));
-    float* W2s = reinterpret_cast<float*>(Gs) + 16 * 4;
+    float* Hs = part + 4 * 16 * FKS_PSTR;                                           // [16][GATE_STR]
+    float4* Gs = reinterpret_cast<float4*>(Hs + 16 * GATE_STR);                     // [16] rows of four gates
+    float* W2s = reinterpret_cast<float*>(Gs + 16);                                 // [4][GATE_STR]
     const FwdRun fr = fwd_run_setup(a);
     const int b = fr.b;
     const int64_t base = fr.base;
@@ -494,7 +542,7 @@ __global__ __launch_bounds__(1024) void meta_forward_ksplit_kernel(FwdArgs a) {
         float* pp = part + (size_t)(kq * 16 + (lane >> 4) * 4) * FKS_PSTR + ht * 16 + (lane & 15);
 #pragma unroll
         for (int i = 0; i < 4; ++i) pp[i * FKS_PSTR] = acc[i];
-        if (t < 4 * H) W2s[t] = w2_pre;
+        if (t < 4 * H) W2s[(t >> 6) * GATE_STR + (t & 63)] = w2_pre;
     }
     __syncthreads();
     MOC_STAMP(7);
@@ -503,34 +551,35 @@ __global__ __launch_bounds__(1024) void meta_forward_ksplit_kernel(FwdArgs a) {
         const float* pp = part + (size_t)r * FKS_PSTR + h;
         const float pre = moc_fadd(moc_fadd(moc_fadd(pp[0], pp[16 * FKS_PSTR]), pp[32 * FKS_PSTR]), pp[48 * FKS_PSTR]);
         const float hv = fmaxf(moc_fadd(pre, bias), 0.f);
-        Hs[r][h] = hv;
+        Hs[r * GATE_STR + h] = hv;
         if (a.H1 && row0 + r < S) a.H1[(base + row0 + r) * H + h] = hv;      // needed by the backward pass only
     }
     __syncthreads();
     MOC_STAMP(8);
     if (t < 64) {
         const int r = t >> 2, i = t & 3;
-        float z = 0.f;
-        for (int h = 0; h < H; ++h) z = fmaf(Hs[r][h], W2s[i * H + h], z);
+        float z = gate_chain(Hs, W2s, r, i);
         z += b2_pre;
         const float g = 1.f / (1.f + expf(-z));
-        Gs[r][i] = g;
+        reinterpret_cast<float*>(Gs)[t] = g;
         if (a.gates && row0 + r < S) a.gates[(base + row0 + r) * 4 + i] = g;
     }
     __syncthreads();
     MOC_STAMP(9);
     if (ec < C) {                                            // (uniform over a class's sixteen lanes)
+        const float4 lam4 = Gs[er];                          // the row's four gates: one 16-byte read
         float v = 0.f;   // 0 + x == x exactly, so this is the reference's running sum in both modes
-        if (a.use_bits & 1u) v = moc_fadd(v, moc_fmul(Gs[er][0], pre_c[0]));
-        if (a.use_bits & 2u) v = moc_fadd(v, moc_fmul(Gs[er][1], pre_c[1]));
-        if (a.use_bits & 4u) v = moc_fadd(v, moc_fmul(Gs[er][2], pre_c[2]));
-        if (a.use_bits & 8u) v = moc_fadd(v, moc_fmul(Gs[er][3], pre_c[3]));
-        if (e_ok) a.mixed[(int64_t)ec * a.stride + base + row0 + er] = v;
+        if (a.use_bits & 1u) v = moc_fadd(v, moc_fmul(lam4.x, pre_c[0]));
+        if (a.use_bits & 2u) v = moc_fadd(v, moc_fmul(lam4.y, pre_c[1]));
+        if (a.use_bits & 4u) v = moc_fadd(v, moc_fmul(lam4.z, pre_c[2]));
+        if (a.use_bits & 8u) v = moc_fadd(v, moc_fmul(lam4.w, pre_c[3]));
         if (a.tile_on) {
-            const float4 lam4 = {Gs[er][0], Gs[er][1], Gs[er][2], Gs[er][3]};
+            // the rank first, then the mixed score and the record: the lane's stores leave back to back
+            const int rank = tile_rank16(e_ok, v, row0 + er);
+            if (e_ok) a.mixed[(int64_t)ec * a.stride + base + row0 + er] = v;
             const float4 sc4 = {pre_c[0], pre_c[1], pre_c[2], pre_c[3]};
-            tile_emit(a.tile, fr.tile_slot0 / TILE_R + (int64_t)ec * fr.tile_cap + blockIdx.x, e_ok, v, row0 + er, rid_e, lam4, sc4);
-        }
+            tile_store(a.tile, fr.tile_slot0 / TILE_R + (int64_t)ec * fr.tile_cap + blockIdx.x, rank, e_ok, v, row0 + er, rid_e, lam4, sc4);
+        } else if (e_ok) a.mixed[(int64_t)ec * a.stride + base + row0 + er] = v;
     }
     MOC_STAMP(2);
     MOC_STAMP_MAX(30);                                      // (diagnostic: the last workgroup of the launch to get here)

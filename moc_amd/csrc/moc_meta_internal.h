@@ -48,20 +48,47 @@ __host__ __device__ inline TileWs tile_carve(void* p, int64_t ns) {
 __host__ __device__ inline size_t tile_bytes(int64_t ns) { return (size_t)ns * 48 + (size_t)(ns / TILE_R) * 4 + 16; }
 
 // Epilogue of a forward workgroup: thread t = class * 16 + row holds the mixed score v of (row0 + row, class); the 16 rows
-// of a class are 16 consecutive lanes (one DPP row).  Every lane ranks its key among the row's sixteen by fifteen row
-// rotations (keys are unique: absent rows carry (0 | ~row)), ranks 0 .. TILE_R-1 write their record, rank TILE_R writes rho.
-__device__ __forceinline__ void tile_emit(const TileWs& T, int64_t tc, bool ok, float v, int row, int64_t rid, float4 lam, float4 sc) {
-    const unsigned hi = ok ? moc_key_desc(v) : 0u, lo = ~(unsigned)row;
+// of a class are 16 consecutive lanes (one DPP row).  Every lane ranks its key (score word | ~row; keys are unique: absent
+// rows carry (0 | ~row)) among the row's sixteen, ranks 0 .. TILE_R-1 write their record, rank TILE_R writes rho.
+// tile_rank16, the rank: each lane counts the row's score words above its own -- fifteen row rotations of one DPP move and
+// one compare.  That count is the rank wherever no two present rows of the tile share a score word; an absent row (score
+// word 0, rows at and past S: the tail of the tile) has rank = its place in the tile whatever the others hold, since every
+// earlier row beats it by its score or, score words equal, by its row.  A count is never above the true rank, and the true
+// ranks of a tile sum to 0 + ... + 15 = 120: the counts are the ranks exactly when the row's sum is 120 (four DPP adds).
+// Otherwise -- equal scores, rare -- the wave ranks again on the whole key, two moves and a two-word compare per rotation
+// (the only form until the tail was shortened: 105 instructions against 50); the branch is on a ballot, uniform over the
+// wave.  `row`: the row in the slide, a multiple of 16 plus the lane's place.
+__device__ __forceinline__ int tile_rank16(bool ok, float v, int row) {
+    const unsigned hi = ok ? moc_key_desc(v) : 0u;
     int rank = 0;
+#define MOC_ROR(n) rank += ((unsigned)__builtin_amdgcn_update_dpp(0, (int)hi, 0x120 + n, 0xf, 0xf, false) > hi) ? 1 : 0;
+    MOC_ROR(1) MOC_ROR(2) MOC_ROR(3) MOC_ROR(4) MOC_ROR(5) MOC_ROR(6) MOC_ROR(7) MOC_ROR(8)
+    MOC_ROR(9) MOC_ROR(10) MOC_ROR(11) MOC_ROR(12) MOC_ROR(13) MOC_ROR(14) MOC_ROR(15)
+#undef MOC_ROR
+    if (!ok) rank = row & 15;
+    int sum = rank;
+    sum += __builtin_amdgcn_update_dpp(0, sum, 0x128, 0xf, 0xf, false);
+    sum += __builtin_amdgcn_update_dpp(0, sum, 0x124, 0xf, 0xf, false);
+    sum += __builtin_amdgcn_update_dpp(0, sum, 0x122, 0xf, 0xf, false);
+    sum += __builtin_amdgcn_update_dpp(0, sum, 0x121, 0xf, 0xf, false);
+    if (__builtin_amdgcn_ballot_w64(sum != 120) != 0) {
+        const unsigned lo = ~(unsigned)row;
+        rank = 0;
 #define MOC_ROR(n)                                                                                              \
     {                                                                                                           \
         const unsigned ohi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)hi, 0x120 + n, 0xf, 0xf, false);     \
         const unsigned olo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)lo, 0x120 + n, 0xf, 0xf, false);     \
         rank += (ohi > hi || (ohi == hi && olo > lo)) ? 1 : 0;                                                  \
     }
-    MOC_ROR(1) MOC_ROR(2) MOC_ROR(3) MOC_ROR(4) MOC_ROR(5) MOC_ROR(6) MOC_ROR(7) MOC_ROR(8)
-    MOC_ROR(9) MOC_ROR(10) MOC_ROR(11) MOC_ROR(12) MOC_ROR(13) MOC_ROR(14) MOC_ROR(15)
+        MOC_ROR(1) MOC_ROR(2) MOC_ROR(3) MOC_ROR(4) MOC_ROR(5) MOC_ROR(6) MOC_ROR(7) MOC_ROR(8)
+        MOC_ROR(9) MOC_ROR(10) MOC_ROR(11) MOC_ROR(12) MOC_ROR(13) MOC_ROR(14) MOC_ROR(15)
 #undef MOC_ROR
+    }
+    return rank;
+}
+// the stores of a lane whose rank is known (a caller with a store of its own puts it in front: they leave back to back)
+__device__ __forceinline__ void tile_store(const TileWs& T, int64_t tc, int rank, bool ok, float v, int row, int64_t rid, float4 lam, float4 sc) {
+    const unsigned hi = ok ? moc_key_desc(v) : 0u, lo = ~(unsigned)row;
     if (rank < TILE_R) {
         const int64_t slot = tc * TILE_R + rank;
         T.key[slot] = ((unsigned long long)hi << 32) | lo;
@@ -71,6 +98,9 @@ __device__ __forceinline__ void tile_emit(const TileWs& T, int64_t tc, bool ok, 
     } else if (rank == TILE_R) {
         T.rho[tc] = hi;
     }
+}
+__device__ __forceinline__ void tile_emit(const TileWs& T, int64_t tc, bool ok, float v, int row, int64_t rid, float4 lam, float4 sc) {
+    tile_store(T, tc, tile_rank16(ok, v, row), ok, v, row, rid, lam, sc);
 }
 
 // An entry of an array inside the kernel's (single, by-value) argument struct, read straight from the kernel-argument
