@@ -863,11 +863,13 @@ __global__ __launch_bounds__(1024) void pool_w1_step_kernel(FusedArgs g, float* 
 //    in front of the first load.
 //  * The pooling of class c is ONE wave's business from the first load to the pooled rows, with no workgroup barrier in
 //    between: it reads the class's tile records (above; VQ keys per lane), forms the sixteen group maxima in registers
-//    (32-bit score keys: quad maxima, one ds_bpermute, fifteen row rotations for the ranks), lists the records >= T0,
-//    requests the candidates' row ids / gates / candidate scores -- one round trip that the ranking loop hides -- and
-//    leaves the pooled rows' operands in LDS.  No second gather round for them.
-//  * Then ONE more round trip: the pairs' 256-column row pieces (three waves), their hidden activation of unit h,
-//    while the fourth wave does the cross entropy; the parameters this workgroup steps were requested at the top.
+//    (32-bit score keys: quad maxima, one ds_bpermute, fifteen row rotations for the ranks), lists the records >= T0
+//    (places by ballot, no LDS counter), requests the candidates' row ids / gates / candidate scores -- one round trip
+//    that the ranking loop hides -- and leaves the pooled rows' operands in LDS.  No second gather round for them.
+//  * Then ONE more round trip: the pairs' 256-column row pieces (three waves); the fourth wave requests their hidden
+//    activation of unit h, does the cross entropy under that request (butterflies by DPP) and forms dz / dh of the
+//    pairs itself, so that ONE barrier stands between the round trip and the gradient sums; the parameters this
+//    workgroup steps were requested at the top.
 // Falls back to the full scores inside the kernel when the records cannot prove exactness.
 struct TileStepArgs {
     // ---- first cache line (64 bytes): what the first loads need -- they are issued before the other lines are touched
@@ -952,6 +954,21 @@ static_assert(offsetof(TileStepArgsRunsHp, adam_r) % sizeof(AdamCoef) == 0, "a r
 __host__ __device__ __forceinline__ const TileStepArgs& tile_common(const TileStepArgs& x) { return x; }
 __host__ __device__ __forceinline__ const TileStepArgs& tile_common(const TileStepArgsRuns& x) { return x.s; }
 __host__ __device__ __forceinline__ const TileStepArgs& tile_common(const TileStepArgsRunsHp& x) { return x.s; }
+
+// Lane l's value of x on lane l ^ OFF of its row of sixteen lanes (OFF = 8, 4, 2, 1), by DPP: what __shfl_xor gives for
+// these partners, without its ds_bpermute round trip.  Every lane of the row must be active.
+//   8: row_ror:8     4: row_half_mirror (l -> 7 - l of eight), then quad_perm [3,2,1,0]     2: quad_perm [2,3,0,1]     1: [1,0,3,2]
+template <int OFF>
+__device__ __forceinline__ int row16_xor(int x) {
+    static_assert(OFF == 8 || OFF == 4 || OFF == 2 || OFF == 1, "partners within a row of sixteen");
+    if constexpr (OFF == 8) return __builtin_amdgcn_update_dpp(0, x, 0x128, 0xf, 0xf, false);
+    else if constexpr (OFF == 4)
+        return __builtin_amdgcn_update_dpp(0, __builtin_amdgcn_update_dpp(0, x, 0x141, 0xf, 0xf, false), 0x1B, 0xf, 0xf, false);
+    else if constexpr (OFF == 2) return __builtin_amdgcn_update_dpp(0, x, 0x4E, 0xf, 0xf, false);
+    else return __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xf, 0xf, false);
+}
+template <int OFF>
+__device__ __forceinline__ float row16_xor(float x) { return __uint_as_float((unsigned)row16_xor<OFF>((int)__float_as_uint(x))); }
 
 template <int VQ, typename ArgsT>
 __global__ __launch_bounds__(256, 4) void pool_w1_step_tiles_kernel(ArgsT args) {
@@ -1090,7 +1107,7 @@ __global__ __launch_bounds__(256, 4) void pool_w1_step_tiles_kernel(ArgsT args) 
     float* topv = reinterpret_cast<float*>(lsrc + (size_t)C * CL);                   // [C][16]
     float* pooled_s = topv + (size_t)C * 16;                                         // [C]
     float* dpool = pooled_s + C;                                                     // [C]
-    int* ncand = reinterpret_cast<int*>(dpool + C);                                  // [C]
+    int* ncand = reinterpret_cast<int*>(dpool + C);                                  // [C] the fall-back's counters (the records' lists are placed by ballot)
     int* flagc = ncand + C;                                                          // [C] 1: the records cannot prove exactness
     int* topk_s = flagc + C;                                                         // [C][K]
     float* h1s = reinterpret_cast<float*>(topk_s + C * K);                           // [P]
@@ -1100,7 +1117,6 @@ __global__ __launch_bounds__(256, 4) void pool_w1_step_tiles_kernel(ArgsT args) 
     for (int c = wave; c < C; c += 4) {                                              // ---- class c: this wave's, start to end
         const int64_t s_c = slot0 + (int64_t)c * cap * TILE_R;                       // the class's first record
         if (c != wave) MOC_TILE_KEYS(c)
-        if (lane == 0) ncand[c] = 0;
         // the score halves of the keys decide bound and candidates (32-bit maxima and compares); absent records: 0
         uint32_t hi[VQ];
         uint32_t m = 0u;
@@ -1130,25 +1146,26 @@ __global__ __launch_bounds__(256, 4) void pool_w1_step_tiles_kernel(ArgsT args) 
         const unsigned long long hit = __ballot(lane < 16 && grank == k - 1 && gm != 0u);
         uint32_t T0 = 0u;
         if (hit != 0ull) T0 = (uint32_t)__builtin_amdgcn_readlane((int)gm, __ffsll((long long)hit) - 1);
-        // the records >= T0: a lane with any takes its places in the list by ONE LDS add (few lanes have any)
+        // the records >= T0 take their places in the list by ballot: sixty-four records at a time, a record's place is the
+        // count so far (wave-uniform) plus the candidates on the lanes below it.  No LDS counter: an LDS add of per-lane
+        // counts is compiled into a serial loop over the lanes that hold any, in front of the add's own round trip.  The
+        // order of the list (q-major) is nobody's business: ranks compare unique keys, lsrc carries the record.
         // (an absent record's key half is 0: with the bound raised to 1 one compare tells both; the sixty-fours of records
         // past the slide's last tile are skipped by uniform branches)
         const uint32_t T1 = T0 > 1u ? T0 : 1u;
-        int cnt = 0;
+        int n = 0;
 #pragma unroll
-        for (int q = 0; q < VQ; ++q)
-            if (q * 64 < nrec) cnt += hi[q] >= T1 ? 1 : 0;
-        if (cnt > 0) {
-            int pos = atomicAdd(&ncand[c], cnt);
-#pragma unroll
-            for (int q = 0; q < VQ; ++q) {
-                if (q * 64 < nrec && hi[q] >= T1) {
-                    if (pos < CL) {
-                        list[(size_t)c * PS_CAP + pos] = key[q];
-                        lsrc[c * CL + pos] = q * 64 + lane;
-                    }
-                    ++pos;
+        for (int q = 0; q < VQ; ++q) {
+            if (q * 64 < nrec) {
+                // (the score half again from the key: hi[] need not live across the ranks above -- fewer VGPRs, less scratch at VQ = 16)
+                const bool in = (q * 64 + lane < nrec ? (uint32_t)(key[q] >> 32) : 0u) >= T1;
+                const unsigned long long bq = __ballot(in);
+                const int pos = n + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bq >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bq, 0u));
+                if (in && pos < CL) {
+                    list[(size_t)c * PS_CAP + pos] = key[q];
+                    lsrc[c * CL + pos] = q * 64 + lane;
                 }
+                n += __popcll(bq);
             }
         }
         // ... and the proof that no score >= T0 is missing from the records: no tile's (TILE_R + 1)-th largest reaches T0
@@ -1156,9 +1173,7 @@ __global__ __launch_bounds__(256, 4) void pool_w1_step_tiles_kernel(ArgsT args) 
 #pragma unroll
         for (int rq = 0; rq < VQ / 4; ++rq)
             bad = bad || (rq * 64 + lane < ntile && rho[rq] != 0u && rho[rq] >= T0);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_wave_barrier();
-        const int n = ncand[c];
+        __builtin_amdgcn_wave_barrier();                 // (a wave's LDS accesses are served in order: the list is there for its readers)
         const bool fall = __ballot(bad) != 0ull || n > CL || n < k || k <= 0;
         if (lane == 0) { flagc[c] = fall ? 1 : 0; t0s[c] = (unsigned long long)T0 << 32; }
         MOC_STAMP(11);
@@ -1178,11 +1193,14 @@ __global__ __launch_bounds__(256, 4) void pool_w1_step_tiles_kernel(ArgsT args) 
                 const int p = c * k + rank;
                 prid[p] = rid; plam[p] = lam; psc[p] = scv;
             }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_wave_barrier();
-            if (lane == 0) {                                                         // summed largest first
-                float sum = 0.f;
-                for (int r = 0; r < k; ++r) sum += topv[c * 16 + r];
+            // summed largest first: ONE LDS read puts value r on lane r, the chain of additions takes them from there
+            // (k dependent LDS reads on one lane were k round trips in front of the barrier every wave waits at)
+            const float tv = lane < k ? topv[c * 16 + lane] : 0.f;
+            float sum = 0.f;
+#pragma nounroll                                         // (unrolled, its sixteen conditions r < k live in SGPRs across the class loop)
+            for (int r = 0; r < k; ++r) sum += __uint_as_float((unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(tv), r));
+            if (lane == 0) {
                 pooled_s[c] = sum / (float)k;
                 if (wg0) {
                     a.pooled_out[(int64_t)b * C + c] = pooled_s[c];
@@ -1272,16 +1290,62 @@ __global__ __launch_bounds__(256, 4) void pool_w1_step_tiles_kernel(ArgsT args) 
     }
     MOC_STAMP(14);
     MOC_STAMP(15);
-    // ---- round trip 2: the pairs' row pieces and their hidden activation of unit h
+    // ---- round trip 2: the pairs' row pieces (three waves) and their hidden activation of unit h (the fourth)
     const int P = C * k;
-    if (P > 0) {                                                                     // (uniform)
-        const unsigned kinv = (65536u + (unsigned)k - 1u) / (unsigned)k;
-        if (wave == 3) {                                                             // the pairs' hidden activation of unit h
-            for (int p = lane; p < P; p += 64) {
-                const int c = (int)(((unsigned)p * kinv) >> 16);
-                h1s[p] = a.H1[(base + topk_s[c * K + (p - c * k)]) * H + h];
+    if (wave == 3) {
+        // Lane p is pair p: P <= 64, for step_plan gives this kernel only shapes with C * K <= 64 (pool_one with train;
+        // launch_tile_step_as refuses others).  The wave REQUESTS the pairs' hidden activation, does the cross entropy of
+        // the pooled logits under that round trip, and then forms the pairs' dz and dh itself: their operands are dpool
+        // (its own), the gates / candidate scores / W2 column (in LDS since the barrier above) and the activation it asked
+        // for -- nothing of the row pieces, so no phase of its own between two workgroup barriers.
+        float hv = 0.f;
+        int pc = 0;                                                                  // the pair's class
+        if (lane < P) {                                                              // (then k > 0)
+            const unsigned kinv = (65536u + (unsigned)k - 1u) / (unsigned)k;
+            pc = (int)(((unsigned)lane * kinv) >> 16);
+            hv = a.H1[(base + topk_s[pc * K + (lane - pc * k)]) * H + h];
+        }
+        // cross entropy, argmax and d loss / d pooled.  The logits sit on lanes 0 .. 15 (C <= 16): the two butterflies over
+        // them (partners xor 8, 4, 2, 1; ties to the smaller class) move their operands by DPP, not through the LDS pipe
+        const float xv = lane < C ? pooled_s[lane] : -INFINITY;
+        float mx = xv;
+        int arg = lane < C ? lane : 0x7fffffff;
+#define MOC_CE_MAX(OFF)                                                                                               \
+        {                                                                                                             \
+            const float om = row16_xor<OFF>(mx);                                                                      \
+            const int oa = row16_xor<OFF>(arg);                                                                       \
+            if (om > mx || (om == mx && oa < arg)) { mx = om; arg = oa; }                                             \
+        }
+        MOC_CE_MAX(8) MOC_CE_MAX(4) MOC_CE_MAX(2) MOC_CE_MAX(1)
+#undef MOC_CE_MAX
+        const float ex = lane < C ? expf(xv - mx) : 0.f;
+        float se = ex;
+        se += row16_xor<8>(se); se += row16_xor<4>(se); se += row16_xor<2>(se); se += row16_xor<1>(se);
+        const float lse = mx + logf(se);
+        if (lane < C) dpool[lane] = expf(xv - lse) - (lane == y ? 1.f : 0.f);
+        if (lane == 0 && wg0) {
+            a.loss[b] = lse - pooled_s[y];
+            a.pred[b] = arg;
+        }
+        __builtin_amdgcn_wave_barrier();
+        if (lane < P) {                                   // lane = pair: its dz, and dh of hidden unit h
+            const int p = lane;
+            h1s[p] = hv;
+            const float gk = dpool[pc] / (float)k;
+            const float4 l4 = plam[p], s4 = psc[p];
+            const float lamv[4] = {l4.x, l4.y, l4.z, l4.w}, scs[4] = {s4.x, s4.y, s4.z, s4.w};
+            float v = 0.f;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float dlam = (a.use_bits >> i & 1u) ? gk * scs[i] : 0.f;
+                const float dzi = dlam * lamv[i] * (1.f - lamv[i]);
+                dz[p * 4 + i] = dzi;
+                v = fmaf(dzi, w2s[i], v);
             }
-        } else if (!tail_wg) {                                                       // row pieces -> fp32 in LDS: eight in flight per wave
+            dhs[p] = hv > 0.f ? v : 0.f;
+        }
+    } else if (P > 0) {                                                              // (uniform)
+        if (!tail_wg) {                                                              // row pieces -> fp32 in LDS: eight in flight per wave
             // (twenty-four rows per round over the three waves: K = 10, C = 2 is ONE round trip; with four per wave it was two)
             const int esz = a.xdt == MOC_F32 ? 4 : 2;
             const int64_t col0 = (int64_t)cb * 256 * esz;
@@ -1324,45 +1388,8 @@ __global__ __launch_bounds__(256, 4) void pool_w1_step_tiles_kernel(ArgsT args) 
             }
         }
     }
-    // cross entropy of the pooled logits, argmax and d loss / d pooled: the fourth wave, beside the others' row requests
-    if (wave == 3) {
-        const float xv = lane < C ? pooled_s[lane] : -INFINITY;
-        float mx = xv;
-        int arg = lane < C ? lane : 0x7fffffff;
-        for (int off = 8; off > 0; off >>= 1) {
-            const float om = __shfl_xor(mx, off, 64);
-            const int oa = __shfl_xor(arg, off, 64);
-            if (om > mx || (om == mx && oa < arg)) { mx = om; arg = oa; }
-        }
-        const float ex = lane < C ? expf(xv - mx) : 0.f;
-        float se = ex;
-        for (int off = 8; off > 0; off >>= 1) se += __shfl_xor(se, off, 64);
-        const float lse = mx + logf(se);
-        if (lane < C) dpool[lane] = expf(xv - lse) - (lane == y ? 1.f : 0.f);
-        if (lane == 0 && wg0) {
-            a.loss[b] = lse - pooled_s[y];
-            a.pred[b] = arg;
-        }
-    }
-    __syncthreads();
+    __syncthreads();                                     // the ONE barrier in front of the gradient loops: row pieces, dz, dh, h1s
     MOC_STAMP(16);
-    for (int p = t; p < P; p += 256) {                   // thread = pair: its dz, and dh of hidden unit h
-        const unsigned kinv = (65536u + (unsigned)k - 1u) / (unsigned)k;
-        const int c = (int)(((unsigned)p * kinv) >> 16);
-        const float gk = dpool[c] / (float)k;
-        const float4 l4 = plam[p], s4 = psc[p];
-        const float lamv[4] = {l4.x, l4.y, l4.z, l4.w}, scs[4] = {s4.x, s4.y, s4.z, s4.w};
-        float v = 0.f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float dlam = (a.use_bits >> i & 1u) ? gk * scs[i] : 0.f;
-            const float dzi = dlam * lamv[i] * (1.f - lamv[i]);
-            dz[p * 4 + i] = dzi;
-            v = fmaf(dzi, w2s[i], v);
-        }
-        dhs[p] = h1s[p] > 0.f ? v : 0.f;
-    }
-    __syncthreads();
     MOC_STAMP(17);
     // ---- gradients of the owned elements, every sum over the pairs in ascending order (operands four pairs at a time:
     // the additions stay in order, the LDS reads do not wait for each other)
@@ -2223,6 +2250,7 @@ TileStepArgs tile_step_args(const StepPlan& p, const moc_batch_t* B, const moc_m
 template <typename ArgsT>
 int launch_tile_step_as(const StepPlan& p, const moc_batch_t* B, const ArgsT& args, int runs, int tb, hipStream_t s) {
     const TileStepArgs& ta = tile_common(args);
+    MOC_REQUIRE(B->C * B->topk <= 64, "moc_fused_step(tiles): C * topk = %d pairs, one wave forms at most 64", B->C * B->topk);
     const dim3 grid(B->D / 256 + (ta.tail_inside ? 0 : 1), H, runs);   // D / 256 column blocks of W1 (+ the tail workgroup), per hidden unit
 #define MOC_TILES_LAUNCH(VQ) pool_w1_step_tiles_kernel<VQ, ArgsT><<<grid, 256, p.smem, s>>>(args)
     const int vq = moc_cdiv((int64_t)tb * TILE_R, 64);                 // keys per lane of a class wave
