@@ -29,6 +29,7 @@ writes the result files.
 from __future__ import annotations
 
 import argparse
+import copy
 import json
 import os
 from glob import glob
@@ -399,14 +400,69 @@ def _is_main():
     return not dist.is_initialized() or dist.get_rank() == 0
 
 
+class ResultBook:
+    """What main() (main_moc.py:586-644) keeps, prints and writes for ONE run: its zero-shot numbers, the best validation AUC so
+    far with the test numbers at it, the checkpoint and the two result files.  `a` carries the run's shot / fold / result_dir;
+    every line goes through `say` behind `prefix`, and the files are written only with `write`."""
+
+    def __init__(self, a, prefix="", say=print, write=True):
+        self.a, self.prefix, self.say, self.write = a, prefix, say, write
+        self.zs = (-1, -1, -1)
+        self.best_val = self.test_at_best_val = self.test_acc_at_best_val = self.best_epoch = 0
+        self.model_path = os.path.join(a.result_dir, f"best_model_shot_{a.shot}_fold_{a.fold}.pt")
+        if write:
+            os.makedirs(a.result_dir, exist_ok=True)
+
+    def _dump(self, stem, obj):
+        if self.write:
+            with open(os.path.join(self.a.result_dir, f"{stem}_shot_{self.a.shot}_fold_{self.a.fold}.json"), "w") as f:
+                json.dump(obj, f, indent=4)
+
+    def say_zero_shot(self):
+        self.say(f"{self.prefix}Zero-shot Train: {self.zs[0]}, Val: {self.zs[1]}, Test: {self.zs[2]}")
+
+    def zero_shot(self, zs_train, zs_val, zs_test):
+        self.zs = (zs_train, zs_val, zs_test)
+        self.say_zero_shot()
+        self._dump("zs_results", {"zs_train": zs_train, "zs_val": zs_val, "zs_test": zs_test})
+
+    def improves(self, val_eval):
+        """Whether this epoch visits the test split: only on a strictly better validation AUC (:618-628)."""
+        return val_eval["auc"] > self.best_val
+
+    def epoch(self, epoch, model, train_eval, val_eval, test_eval=None):
+        """The epoch's line; with `test_eval` (the caller evaluated the test split because `improves(val_eval)`) the new best
+        and the checkpoint."""
+        if test_eval is None:
+            self.say(f"{self.prefix}Epoch: {epoch}, Train: {train_eval}, Val: {val_eval}")
+            return
+        self.say(f"{self.prefix}Epoch: {epoch}, Train: {train_eval}, Val: {val_eval}, Test: {test_eval}")
+        self.best_val, self.test_at_best_val, self.test_acc_at_best_val = val_eval["auc"], test_eval["auc"], test_eval["acc"]
+        self.best_epoch = epoch
+        if self.write:
+            torch.save(model.state_dict(), self.model_path)
+
+    def close(self):
+        """The `Best Val` line and best_results_shot_S_fold_F.json -> the result dict."""
+        self.say(f"{self.prefix}Best Val: {self.best_val}, Test at Best Val: {self.test_at_best_val}, "
+                 f"Test acc: {self.test_acc_at_best_val}, Best Epoch: {self.best_epoch}")
+        results = {
+            "zero_shot_train": self.zs[0], "zero_shot_val": self.zs[1], "zero_shot_test": self.zs[2],
+            "best_val": self.best_val, "test_at_best_val": self.test_at_best_val, "test_acc_at_best_val": self.test_acc_at_best_val,
+            "best_epoch": self.best_epoch, "best_model_path": self.model_path,
+        }
+        self._dump("best_results", results)
+        return results
+
+
 def main(args, model, optimizer, train_loader, val_loader, test_loader, device):
     """main_moc.py:586-644.  The loaders are anything main_moc's loops take, or moc_amd.dist.ShardedSplit objects
     (multi-GPU: every rank calls this; rank 0 prints and writes)."""
     chief = _is_main()
     say = print if chief else (lambda *a, **k: None)
-    if chief:
-        os.makedirs(args.result_dir, exist_ok=True)
     if args.ablation_study != "none":
+        if chief:
+            os.makedirs(args.result_dir, exist_ok=True)
         ablation_eval_dict = (mdist.ablation_evaluation(test_loader, device, args) if isinstance(test_loader, mdist.ShardedSplit)
                               else M.ablation_evaluation(test_loader, device, args))
         say(f"Ablation Study: {args.ablation_study}, Test: {ablation_eval_dict}")
@@ -415,47 +471,19 @@ def main(args, model, optimizer, train_loader, val_loader, test_loader, device):
                 json.dump(ablation_eval_dict, f, indent=4)
         return ablation_eval_dict
 
-    zs_train, zs_val, zs_test = -1, -1, -1
+    book = ResultBook(args, say=say, write=chief)         # every rank keeps the book (the test split is a collective); the chief speaks
     if args.check_zeroshot:
-        zs_train = _zs_evaluation(train_loader, device, args)
-        zs_val = _zs_evaluation(val_loader, device, args)
-        zs_test = _zs_evaluation(test_loader, device, args)
-        say(f"Zero-shot Train: {zs_train}, Val: {zs_val}, Test: {zs_test}")
-        if chief:
-            with open(os.path.join(args.result_dir, f"zs_results_shot_{args.shot}_fold_{args.fold}.json"), "w") as f:
-                json.dump({"zs_train": zs_train, "zs_val": zs_val, "zs_test": zs_test}, f, indent=4)
-
-    best_val = 0
-    test_at_best_val = 0
-    test_acc_at_best_val = 0
-    best_epoch = 0
-    model_path = os.path.join(args.result_dir, f"best_model_shot_{args.shot}_fold_{args.fold}.pt")
+        book.zero_shot(_zs_evaluation(train_loader, device, args), _zs_evaluation(val_loader, device, args),
+                       _zs_evaluation(test_loader, device, args))
     for epoch in range(getattr(args, "epochs", 25)):
         say("Epoch: ", epoch)
         _train(model, train_loader, optimizer, device, args)
         train_eval = _evaluation(model, train_loader, device, args)
         val_eval = _evaluation(model, val_loader, device, args)
-        if val_eval["auc"] > best_val:          # the test split is only visited on improvement (:618-628)
-            test_eval = _evaluation(model, test_loader, device, args)
-            say(f"Epoch: {epoch}, Train: {train_eval}, Val: {val_eval}, Test: {test_eval}")
-            best_val = val_eval["auc"]
-            test_at_best_val = test_eval["auc"]
-            test_acc_at_best_val = test_eval["acc"]
-            best_epoch = epoch
-            if chief:
-                torch.save(model.state_dict(), model_path)
-        else:
-            say(f"Epoch: {epoch}, Train: {train_eval}, Val: {val_eval}")
-    say(f"Zero-shot Train: {zs_train}, Val: {zs_val}, Test: {zs_test}")
-    say(f"Best Val: {best_val}, Test at Best Val: {test_at_best_val}, Test acc: {test_acc_at_best_val}, Best Epoch: {best_epoch}")
-    results = {
-        "zero_shot_train": zs_train, "zero_shot_val": zs_val, "zero_shot_test": zs_test,
-        "best_val": best_val, "test_at_best_val": test_at_best_val, "test_acc_at_best_val": test_acc_at_best_val,
-        "best_epoch": best_epoch, "best_model_path": model_path,
-    }
-    if chief:
-        with open(os.path.join(args.result_dir, f"best_results_shot_{args.shot}_fold_{args.fold}.json"), "w") as f:
-            json.dump(results, f, indent=4)
+        test_eval = _evaluation(model, test_loader, device, args) if book.improves(val_eval) else None
+        book.epoch(epoch, model, train_eval, val_eval, test_eval)
+    book.say_zero_shot()        # main alone, as the reference (:629): once more before the last line, -1s without --check_zeroshot
+    results = book.close()
     say("\nEnd training.")
     return results
 
@@ -496,18 +524,17 @@ def main_runs(args_list, models, optimizers, loaders_list, device, generators=No
     -> list of result dicts."""
     R = len(models)
     a0 = args_list[0]
-    tag = (lambda a: f"[shot {a.shot} fold {a.fold}]") if len({a.shot for a in args_list}) > 1 else (lambda a: f"[fold {a.fold}]")
     # a hyper-parameter grid: the runs of every configuration (topj, topk, discard set), in order of first appearance
     by_cfg = {}
     for r, a in enumerate(args_list):
         by_cfg.setdefault((a.topj, a.topk, tuple(a.discard_classifiers or ())), []).append(r)
-    if len(by_cfg) > 1:
-        fold_tag = tag
-        tag = lambda a: f"[topj {a.topj} topk {a.topk} {hgrid_discard_name(a.discard_classifiers)}] " + fold_tag(a)
+    shots = len({a.shot for a in args_list}) > 1
 
-    if per_run_adam:
-        cell_tag = tag
-        tag = lambda a: f"[seed {a.seed} lr {a.lr:g} wd {a.weight_decay:g}] " + cell_tag(a)
+    def tag(a):
+        """What tells the run's lines from its neighbours': only what differs between the runs of this call."""
+        return ((f"[seed {a.seed} lr {a.lr:g} wd {a.weight_decay:g}] " if per_run_adam else "")
+                + (f"[topj {a.topj} topk {a.topk} {hgrid_discard_name(a.discard_classifiers)}] " if len(by_cfg) > 1 else "")
+                + (f"[shot {a.shot} fold {a.fold}]" if shots else f"[fold {a.fold}]"))
 
     def evaluate(ms, lds):
         """evaluation_runs over (model, loader) pairs named by run index: its plan belongs to one `args`, so a grid evaluates
@@ -522,19 +549,10 @@ def main_runs(args_list, models, optimizers, loaders_list, device, generators=No
                     out[i] = e
         return out
     assert a0.ablation_study == "none", "main_runs: the ablation study trains nothing -- run it per fold"
-    st = []
-    for r in range(R):
-        a = args_list[r]
-        os.makedirs(a.result_dir, exist_ok=True)
-        tr, va, te = loaders_list[r]
-        zs = (-1, -1, -1)
+    books = [ResultBook(a, prefix=tag(a) + " ") for a in args_list]
+    for a, book, (tr, va, te) in zip(args_list, books, loaders_list):
         if a.check_zeroshot:
-            zs = (M.zs_evaluation(tr, device, a), M.zs_evaluation(va, device, a), M.zs_evaluation(te, device, a))
-            print(f"{tag(a)} Zero-shot Train: {zs[0]}, Val: {zs[1]}, Test: {zs[2]}")
-            with open(os.path.join(a.result_dir, f"zs_results_shot_{a.shot}_fold_{a.fold}.json"), "w") as f:
-                json.dump({"zs_train": zs[0], "zs_val": zs[1], "zs_test": zs[2]}, f, indent=4)
-        st.append(dict(zs=zs, best_val=0, test_at_best_val=0, test_acc_at_best_val=0, best_epoch=0,
-                       model_path=os.path.join(a.result_dir, f"best_model_shot_{a.shot}_fold_{a.fold}.pt")))
+            book.zero_shot(M.zs_evaluation(tr, device, a), M.zs_evaluation(va, device, a), M.zs_evaluation(te, device, a))
     trains = [ls[0] for ls in loaders_list]
     M.pack_splits(trains + [ls[1] for ls in loaders_list])       # (one array per pass of evaluation_runs, packed once)
     M.pack_splits([ls[2] for ls in loaders_list])
@@ -544,29 +562,11 @@ def main_runs(args_list, models, optimizers, loaders_list, device, generators=No
                      per_run_adam=per_run_adam)
         # all runs' train and validation splits in one pass, then the test splits of the runs that improved in another
         ev = evaluate(list(range(R)) + list(range(R)), trains + [ls[1] for ls in loaders_list])
-        better = [r for r in range(R) if ev[R + r]["auc"] > st[r]["best_val"]]
+        better = [r for r in range(R) if books[r].improves(ev[R + r])]
         ev_test = dict(zip(better, evaluate(better, [loaders_list[r][2] for r in better]))) if better else {}
         for r in range(R):
-            a, s_ = args_list[r], st[r]
-            train_eval, val_eval = ev[r], ev[R + r]
-            if r in ev_test:
-                test_eval = ev_test[r]
-                print(f"{tag(a)} Epoch: {epoch}, Train: {train_eval}, Val: {val_eval}, Test: {test_eval}")
-                s_.update(best_val=val_eval["auc"], test_at_best_val=test_eval["auc"], test_acc_at_best_val=test_eval["acc"], best_epoch=epoch)
-                torch.save(models[r].state_dict(), s_["model_path"])
-            else:
-                print(f"{tag(a)} Epoch: {epoch}, Train: {train_eval}, Val: {val_eval}")
-    out = []
-    for r in range(R):
-        a, s_ = args_list[r], st[r]
-        print(f"{tag(a)} Best Val: {s_['best_val']}, Test at Best Val: {s_['test_at_best_val']}, Test acc: {s_['test_acc_at_best_val']}, "
-              f"Best Epoch: {s_['best_epoch']}")
-        res = {"zero_shot_train": s_["zs"][0], "zero_shot_val": s_["zs"][1], "zero_shot_test": s_["zs"][2],
-               "best_val": s_["best_val"], "test_at_best_val": s_["test_at_best_val"], "test_acc_at_best_val": s_["test_acc_at_best_val"],
-               "best_epoch": s_["best_epoch"], "best_model_path": s_["model_path"]}
-        with open(os.path.join(a.result_dir, f"best_results_shot_{a.shot}_fold_{a.fold}.json"), "w") as f:
-            json.dump(res, f, indent=4)
-        out.append(res)
+            books[r].epoch(epoch, models[r], ev[r], ev[R + r], ev_test.get(r))
+    out = [book.close() for book in books]
     print("\nEnd training.")
     return out
 
@@ -597,57 +597,130 @@ def run_result_dir(args, shot: int):
     return os.path.join(args.result_dir, f"{shot}_shot") if getattr(args, "shots", "") else args.result_dir
 
 
+# ------------------------------------------------------------------ what the grid drivers share (cli_folds, cli_hgrid, cli_optgrid, cli_bankgrid)
+def grid_device():
+    """The GPU of this process, made current: under a launcher the rank's own, else the current one."""
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")) if world > 1 else torch.cuda.current_device())
+    torch.cuda.set_device(device)
+    return device
+
+
+def task_shape(args):
+    """(classes, bytes per stored bag element) of the command's task, from the command line and the label table alone."""
+    return _synthetic_classes(args) if args.synthetic else len(_label_map(args)), 2 if args.bag_dtype in ("bf16", "fp16") else 4
+
+
+def fold_footprints(args, folds):
+    """{fold: split_footprints of (--shot, fold)}: what a grid whose cells share the splits of a fold holds once per fold."""
+    out = {}
+    for fold in folds:
+        a = copy.copy(args)
+        a.fold = fold
+        out[fold] = split_footprints(a)
+    return out
+
+
+def refuse_unless_fits(what, need, device, advice=lambda free: ": name fewer folds"):
+    """The refusal before a bag is loaded: `need` (grid_bytes of the largest block) against the device's free memory."""
+    free = torch.cuda.mem_get_info(device)[0]
+    if need > free:
+        raise SystemExit(f"{what} needs about {need / 2**30:.1f} GiB of device memory, {free / 2**30:.1f} GiB are free{advice(free)}")
+
+
+def grid_blocks(n_items, runs_per_item, max_runs, too_many):
+    """`n_items` things of `runs_per_item` runs each cut into blocks trained one after the other: whole items, as many as fit
+    `max_runs` runs.  One item that does not fit is refused with `too_many`.  -> list of lists of item indices.  Pure."""
+    if runs_per_item > max_runs:
+        raise SystemExit(too_many)
+    per = max(1, max_runs // runs_per_item)
+    return [list(range(i, min(i + per, n_items))) for i in range(0, n_items, per)]
+
+
+def grid_runs(args, cells, folds, of_cell):
+    """The runs' namespaces: a copy of `args` per (cell, fold) with `of_cell(cell)`'s attributes (its result_dir among them),
+    cells in the given order, fold-major inside one (the runs of a lockstep chain are consecutive)."""
+    out = []
+    for cell in cells:
+        for fold in folds:
+            a = copy.copy(args)
+            a.fold = fold
+            vars(a).update(of_cell(cell))
+            out.append(a)
+    return out
+
+
+def build_run(seed, device, lr, weight_decay):
+    """-> (meta-learner, its Adam, the run's mask generator): exactly what the run's own single command does with the default
+    generator -- seed (with None the stream goes on from wherever it is, as it does without --seed), build the meta-learner,
+    and the masks follow from wherever that leaves the stream -- here in a generator of the run's own.  The ORDER is the
+    point: the generator takes the state the constructor left behind, so runs built from one seed start from equal
+    parameters AND equal generator states; they draw the same masks, which is what lets the cells of a fold share a score
+    pass per epoch (moc_amd.runs)."""
+    if seed is not None:
+        torch.manual_seed(seed)
+    model = M.senet(FEATURE_DIM, 4).to(device)
+    g = torch.Generator()
+    g.set_state(torch.get_rng_state())
+    return model, torch.optim.Adam(model.parameters(), lr=lr, weight_decay=weight_decay), g
+
+
+def resident_splits(a, device, share, share_train, what):
+    """prepare() for a run of a grid: lockstep training and the batched evaluations take resident splits only."""
+    loaders = prepare(a, device, share=share, share_train=share_train)
+    assert all(isinstance(ld, M.ResidentBags) for ld in loaders), f"{what} needs resident splits (--resident 1)"
+    return loaders
+
+
+def train_blocks(blocks, device, what, build, share_train=True, per_run_adam=False):
+    """main_runs over every block (a list of run namespaces), one block after the other: per run its splits, THEN the run
+    itself (`build(a)` -> build_run's triple; the single command prepares before it seeds, too).  One `share` dict serves
+    all blocks: a split that any earlier run named is held once.  -> the result dicts in run order."""
+    out, share = [], {}
+    for args_list in blocks:
+        models, optimizers, loaders_list, gens = [], [], [], []
+        for a in args_list:
+            loaders_list.append(resident_splits(a, device, share, share_train, what))
+            model, optimizer, g = build(a)
+            models.append(model)
+            optimizers.append(optimizer)
+            gens.append(g)
+        out += main_runs(args_list, models, optimizers, loaders_list, device, generators=gens, per_run_adam=per_run_adam)
+    return out
+
+
 def cli_folds(args):
     """`--folds a,b,...` and / or `--shots a,b,...`: those runs in this process (under a launcher: this rank's share of
     them, nothing exchanged)."""
-    import copy
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
-    pairs = pairs_of_rank(getattr(args, "shots", ""), args.folds, args.shot, args.fold, rank, world)
-    device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")) if world > 1 else torch.cuda.current_device())
-    torch.cuda.set_device(device)
+    pairs = pairs_of_rank(getattr(args, "shots", ""), args.folds, args.shot, args.fold, rank, world)     # (shot, fold) pairs are what is dealt
+    device = grid_device()
     if not pairs:
         print(f"rank {rank}: no fold to train")
         return []
     assert not args.loader_seed_draw, "--folds: the runs draw their masks from private generators (no DataLoader base-seed draw)"
     from . import runs as RUNS
-    if len(pairs) > RUNS.MAX_RUNS:
+    if len(pairs) > RUNS.MAX_RUNS:      # one block: runs of different shot counts share nothing that a cut could keep together
         raise SystemExit(f"--shots x --folds: {len(pairs)} runs in one process, at most {RUNS.MAX_RUNS}")
-    if getattr(args, "shots", ""):
-        # the footprint of the grid before a bag is loaded: splits that two runs share count once
-        fps = []
-        for shot, fold in pairs:
-            a = copy.copy(args)
-            a.fold, a.shot = fold, shot
-            fps.append(split_footprints(a))
-        itemsize = 2 if args.bag_dtype in ("bf16", "fp16") else 4
-        C_ = _synthetic_classes(args) if args.synthetic else len(_label_map(args))
-        free = torch.cuda.mem_get_info(device)[0]
-        need = grid_bytes(fps, FEATURE_DIM, itemsize, C_)
-        if need > free:
-            k = largest_grid(fps, FEATURE_DIM, itemsize, C_, free)
-            raise SystemExit(f"--shots x --folds: this grid needs about {need / 2**30:.1f} GiB of device memory, {free / 2**30:.1f} GiB "
-                             f"are free.  The largest leading part of it that fits is {k} run(s): {pairs[:k]}")
-    args_list, models, optimizers, loaders_list, gens = [], [], [], [], []
-    share = {}
+    args_list = []
     for shot, fold in pairs:
         a = copy.copy(args)
         a.fold, a.shot = fold, shot
         a.result_dir = run_result_dir(args, shot)
-        loaders = prepare(a, device, share=share)
-        assert all(isinstance(ld, M.ResidentBags) for ld in loaders), "--folds needs resident splits (--resident 1)"
-        # exactly what `--fold F` alone does with the default generator: seed, build the meta-learner, and the masks follow
-        # from wherever that leaves the stream -- here in a generator of the run's own
-        if args.seed is not None:
-            torch.manual_seed(args.seed)
-        model = M.senet(FEATURE_DIM, 4).to(device)
-        g = torch.Generator()
-        g.set_state(torch.get_rng_state())
         args_list.append(a)
-        models.append(model)
-        optimizers.append(torch.optim.Adam(model.parameters(), lr=args.lr, weight_decay=args.weight_decay))
-        loaders_list.append(loaders)
-        gens.append(g)
-    return main_runs(args_list, models, optimizers, loaders_list, device, generators=gens)
+    if getattr(args, "shots", ""):
+        # only with --shots: plain --folds is the reference launcher's handful of folds of one shot and has never been sized; a
+        # grid grows with its shot counts, and since its runs stand alone the refusal can name the leading part that fits
+        C_, itemsize = task_shape(args)
+        fps = [split_footprints(a) for a in args_list]          # (splits that two runs share count once)
+
+        def leading_part(free):
+            k = largest_grid(fps, FEATURE_DIM, itemsize, C_, free)
+            return f".  The largest leading part of it that fits is {k} run(s): {pairs[:k]}"
+        refuse_unless_fits("--shots x --folds: this grid", grid_bytes(fps, FEATURE_DIM, itemsize, C_), device, leading_part)
+    # share_train stays off: no two (shot, fold) pairs have the same train split, only validation and test splits recur
+    return train_blocks([args_list], device, "--folds", share_train=False,
+                        build=lambda a: build_run(args.seed, device, lr=args.lr, weight_decay=args.weight_decay))
 
 
 # ------------------------------------------------------------------ hyper-parameter grids (--topjs / --topks / --discard_sets)
@@ -710,72 +783,43 @@ def check_hgrid_args(args):
 def hgrid_blocks(n_configs, n_folds, max_runs):
     """The configurations cut into blocks trained one after the other: whole configurations, as many as fit `max_runs` runs
     (a configuration is n_folds runs).  -> list of lists of configuration indices.  Pure."""
-    if n_folds > max_runs:
-        raise SystemExit(f"--folds: {n_folds} folds in one process, at most {max_runs}")
-    per = max(1, max_runs // n_folds)
-    return [list(range(i, min(i + per, n_configs))) for i in range(0, n_configs, per)]
+    return grid_blocks(n_configs, n_folds, max_runs, f"--folds: {n_folds} folds in one process, at most {max_runs}")
 
 
 def hgrid_runs(args, configs, folds):
-    """The runs' namespaces: configurations in the given order, fold-major inside one (the runs of a lockstep chain are
-    consecutive)."""
-    import copy
-    out = []
-    for cfg in configs:
-        for fold in folds:
-            a = copy.copy(args)
-            a.fold, a.topj, a.topk, a.discard_classifiers = fold, cfg[0], cfg[1], list(cfg[2])
-            a.result_dir = hgrid_dir(args.result_dir, cfg)
-            out.append(a)
-    return out
+    """The runs' namespaces: configurations in the given order, fold-major inside one (grid_runs)."""
+    return grid_runs(args, configs, folds, lambda cfg: dict(topj=cfg[0], topk=cfg[1], discard_classifiers=list(cfg[2]),
+                                                            result_dir=hgrid_dir(args.result_dir, cfg)))
+
+
+def cells_block_bytes(args, n_cells, folds):
+    """grid_bytes of a block of `n_cells` cells x `folds` whose cells share the splits of a fold: those count once."""
+    C_, itemsize = task_shape(args)
+    fps = fold_footprints(args, folds)
+    return grid_bytes([fps[f] for _ in range(n_cells) for f in folds], FEATURE_DIM, itemsize, C_)
 
 
 def cli_hgrid(args):
     """`--topjs / --topks / --discard_sets` (with --folds or the one --fold): every (configuration, fold) run in this process.
     Under a launcher the configurations are dealt to the ranks, nothing exchanged."""
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
-    configs = hgrid_configs(args)[rank::world]
+    configs = hgrid_configs(args)[rank::world]      # whole configurations are what is dealt: a rank keeps every fold's shared score pass
     folds = folds_of_rank(args.folds, 0, 1) if args.folds else [int(args.fold)]
-    device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")) if world > 1 else torch.cuda.current_device())
-    torch.cuda.set_device(device)
+    device = grid_device()
     if not configs:
         print(f"rank {rank}: no configuration to train")
         return []
     from . import runs as RUNS
     blocks = hgrid_blocks(len(configs), len(folds), RUNS.MAX_RUNS)
-    # the footprint of the largest block before a bag is loaded: the splits of a fold count once for all its configurations
-    itemsize = 2 if args.bag_dtype in ("bf16", "fp16") else 4
-    C_ = _synthetic_classes(args) if args.synthetic else len(_label_map(args))
-    fps = {}
-    for a in hgrid_runs(args, configs[:1], folds):
-        fps[a.fold] = split_footprints(a)
-    need = grid_bytes([fps[f] for _ in blocks[0] for f in folds], FEATURE_DIM, itemsize, C_)
-    free = torch.cuda.mem_get_info(device)[0]
-    if need > free:
-        raise SystemExit(f"--topjs x --topks x --discard_sets: a block of {len(blocks[0])} configuration(s) x {len(folds)} fold(s) needs "
-                         f"about {need / 2**30:.1f} GiB of device memory, {free / 2**30:.1f} GiB are free: name fewer folds")
-    M.EVAL_RUN_PLANS = max(M.EVAL_RUN_PLANS, 3 * len(blocks[0]))      # (a plan per configuration and kind of pass)
-    out, share = [], {}
-    for block in blocks:
-        args_list, models, optimizers, loaders_list, gens = [], [], [], [], []
-        for a in hgrid_runs(args, [configs[i] for i in block], folds):
-            loaders = prepare(a, device, share=share, share_train=True)
-            assert all(isinstance(ld, M.ResidentBags) for ld in loaders), "a hyper-parameter grid needs resident splits (--resident 1)"
-            # exactly what the configuration's own `--fold F` command does with the default generator: seed, build the
-            # meta-learner, and the masks follow from wherever that leaves the stream -- with --seed the configurations of a
-            # fold start from equal generator states and share their masks
-            if args.seed is not None:
-                torch.manual_seed(args.seed)
-            model = M.senet(FEATURE_DIM, 4).to(device)
-            g = torch.Generator()
-            g.set_state(torch.get_rng_state())
-            args_list.append(a)
-            models.append(model)
-            optimizers.append(torch.optim.Adam(model.parameters(), lr=args.lr, weight_decay=args.weight_decay))
-            loaders_list.append(loaders)
-            gens.append(g)
-        out += main_runs(args_list, models, optimizers, loaders_list, device, generators=gens)
-    return out
+    refuse_unless_fits(f"--topjs x --topks x --discard_sets: a block of {len(blocks[0])} configuration(s) x {len(folds)} fold(s)",
+                       cells_block_bytes(args, len(blocks[0]), folds), device)
+    # evaluation_runs' plan belongs to one (topj, topk, discard set), so main_runs evaluates configuration by configuration: a
+    # plan per configuration of a block and kind of pass (train + val, and two sets of improved runs' test splits)
+    M.EVAL_RUN_PLANS = max(M.EVAL_RUN_PLANS, 3 * len(blocks[0]))
+    # (train_blocks' one `share` across the blocks: every block names the same folds, whose splits are loaded once)
+    return train_blocks([hgrid_runs(args, [configs[i] for i in block], folds) for block in blocks], device, "a hyper-parameter grid",
+                        build=lambda a: build_run(args.seed, device, lr=args.lr, weight_decay=args.weight_decay))
+
 
 # ------------------------------------------------------------------ optimizer grids (--seeds / --lrs / --wds)
 OPT_GRID_FLAGS = "--seeds / --lrs / --wds"
@@ -839,36 +883,34 @@ def check_optgrid_args(args):
 
 
 def optgrid_runs(args, cells, folds):
-    """The runs' namespaces: cells in the given order, fold-major inside one (hgrid_runs' order)."""
-    import copy
-    out = []
-    for cell in cells:
-        for fold in folds:
-            a = copy.copy(args)
-            a.fold, a.seed, a.lr, a.weight_decay = fold, cell[0], cell[1], cell[2]
-            a.result_dir = optgrid_dir(args.result_dir, cell)
-            out.append(a)
-    return out
+    """The runs' namespaces: cells in the given order, fold-major inside one (grid_runs)."""
+    return grid_runs(args, cells, folds, lambda cell: dict(seed=cell[0], lr=cell[1], weight_decay=cell[2],
+                                                           result_dir=optgrid_dir(args.result_dir, cell)))
+
+
+def summary_row(result_dirs_and_folds, shot):
+    """The columns the grids' summaries share: the number of runs and the mean and population standard deviation over them of
+    the best validation AUC and of the test AUC at it, read from the runs' best_results_* files (`best_val`,
+    `test_at_best_val`: the keys --summary reads them by)."""
+    vals = []
+    for result_dir, fold in result_dirs_and_folds:
+        with open(os.path.join(result_dir, f"best_results_shot_{shot}_fold_{fold}.json")) as f:
+            r = json.load(f)
+        vals.append((r["best_val"], r["test_at_best_val"]))
+    v = np.asarray(vals, dtype=np.float64)
+    return {"runs": len(vals), "best_val_mean": v[:, 0].mean(), "best_val_std": v[:, 0].std(),
+            "test_auc_mean": v[:, 1].mean(), "test_auc_std": v[:, 1].std()}
 
 
 def write_optgrid_summary(result_dir, cells, folds, shot):
-    """{result_dir}/opt_grid_summary.csv: one line per (lr, weight_decay) in order of first appearance -- the number of runs
-    (seeds x folds) and the mean and population standard deviation of their best validation AUC and of the test AUC at it,
-    read from the cells' best_results_* files (`best_val`, `test_at_best_val`: the keys --summary reads them by).  -> path."""
+    """{result_dir}/opt_grid_summary.csv: one line per (lr, weight_decay) in order of first appearance over its runs (seeds x
+    folds, seed-major): summary_row's columns.  -> path."""
     by_hp = {}
     for cell in cells:
-        for fold in folds:
-            with open(os.path.join(optgrid_dir(result_dir, cell), f"best_results_shot_{shot}_fold_{fold}.json")) as f:
-                r = json.load(f)
-            by_hp.setdefault((cell[1], cell[2]), []).append((r["best_val"], r["test_at_best_val"]))
-    rows = []
-    for (lr, wd), vals in by_hp.items():
-        v = np.asarray(vals, dtype=np.float64)
-        rows.append({"lr": format(lr, "g"), "weight_decay": format(wd, "g"), "runs": len(vals),
-                     "best_val_mean": v[:, 0].mean(), "best_val_std": v[:, 0].std(),
-                     "test_auc_mean": v[:, 1].mean(), "test_auc_std": v[:, 1].std()})
+        by_hp.setdefault((cell[1], cell[2]), []).extend((optgrid_dir(result_dir, cell), fold) for fold in folds)
+    rows = [{"lr": format(lr, "g"), "weight_decay": format(wd, "g"), **summary_row(runs, shot)} for (lr, wd), runs in by_hp.items()]
     path = os.path.join(result_dir, "opt_grid_summary.csv")
-    pd.DataFrame(rows).to_csv(path, index=False)
+    pd.DataFrame(rows).to_csv(path, index=False)        # (no float_format: pandas' shortest round-trip text, as this file has always had)
     return path
 
 
@@ -876,38 +918,15 @@ def cli_optgrid(args):
     """`--seeds / --lrs / --wds` (with --folds or the one --fold): every (cell, fold) run in this process."""
     cells = optgrid_cells(args)
     folds = folds_of_rank(args.folds, 0, 1) if args.folds else [int(args.fold)]
-    device = torch.device("cuda", torch.cuda.current_device())
-    torch.cuda.set_device(device)
+    device = grid_device()      # one GPU: check_optgrid_args refuses a launcher (the cells of a fold step in ONE chain)
     from . import runs as RUNS
     blocks = hgrid_blocks(len(cells), len(folds), RUNS.MAX_RUNS)
-    # the footprint of the largest block before a bag is loaded: the splits of a fold count once for all its cells
-    itemsize = 2 if args.bag_dtype in ("bf16", "fp16") else 4
-    C_ = _synthetic_classes(args) if args.synthetic else len(_label_map(args))
-    fps = {a.fold: split_footprints(a) for a in optgrid_runs(args, cells[:1], folds)}
-    need = grid_bytes([fps[f] for _ in blocks[0] for f in folds], FEATURE_DIM, itemsize, C_)
-    free = torch.cuda.mem_get_info(device)[0]
-    if need > free:
-        raise SystemExit(f"--seeds x --lrs x --wds: a block of {len(blocks[0])} cell(s) x {len(folds)} fold(s) needs about "
-                         f"{need / 2**30:.1f} GiB of device memory, {free / 2**30:.1f} GiB are free: name fewer folds")
-    out, share = [], {}
-    for block in blocks:
-        args_list, models, optimizers, loaders_list, gens = [], [], [], [], []
-        for a in optgrid_runs(args, [cells[i] for i in block], folds):
-            loaders = prepare(a, device, share=share, share_train=True)
-            assert all(isinstance(ld, M.ResidentBags) for ld in loaders), "an optimizer grid needs resident splits (--resident 1)"
-            # exactly what the cell's own `--fold F --seed S --lr LR --weight_decay WD` command does with the default generator:
-            # seed, build the meta-learner, and the masks follow from wherever that leaves the stream -- the (lr, wd) cells of a
-            # (seed, fold) start from equal parameters and equal generator states and share their masks
-            torch.manual_seed(a.seed)
-            model = M.senet(FEATURE_DIM, 4).to(device)
-            g = torch.Generator()
-            g.set_state(torch.get_rng_state())
-            args_list.append(a)
-            models.append(model)
-            optimizers.append(torch.optim.Adam(model.parameters(), lr=a.lr, weight_decay=a.weight_decay))
-            loaders_list.append(loaders)
-            gens.append(g)
-        out += main_runs(args_list, models, optimizers, loaders_list, device, generators=gens, per_run_adam=True)
+    refuse_unless_fits(f"--seeds x --lrs x --wds: a block of {len(blocks[0])} cell(s) x {len(folds)} fold(s)",
+                       cells_block_bytes(args, len(blocks[0]), folds), device)
+    # every run is seeded with ITS cell's seed and steps with ITS cell's rates (per_run_adam): the (lr, wd) cells of a (seed, fold)
+    # start from equal parameters and equal generator states and share their masks
+    out = train_blocks([optgrid_runs(args, [cells[i] for i in block], folds) for block in blocks], device, "an optimizer grid",
+                       build=lambda a: build_run(a.seed, device, lr=a.lr, weight_decay=a.weight_decay), per_run_adam=True)
     print("optimizer grid summary:", write_optgrid_summary(args.result_dir, cells, folds, args.shot))
     return out
 
@@ -955,23 +974,13 @@ def check_bankgrid_args(args):
 def bankgrid_blocks(n_banks, n_folds, max_runs):
     """The folds cut into blocks trained one after the other: whole folds -- a fold's banks stay together, they share the
     score pass -- as many as fit `max_runs` runs (a fold is n_banks runs).  -> list of lists of fold positions.  Pure."""
-    if n_banks > max_runs:
-        raise SystemExit(f"--banks: {n_banks} banks in one process, at most {max_runs}")
-    per = max(1, max_runs // n_banks)
-    return [list(range(i, min(i + per, n_folds))) for i in range(0, n_folds, per)]
+    return grid_blocks(n_folds, n_banks, max_runs, f"--banks: {n_banks} banks in one process, at most {max_runs}")
 
 
 def bankgrid_runs(args, names, folds):
     """The runs' namespaces, bank-major (the leaders of the folds are consecutive runs: one score launch serves them all),
-    the folds inside a bank in the given order."""
-    import copy
-    out = []
-    for name in names:
-        for fold in folds:
-            a = copy.copy(args)
-            a.fold, a.bank, a.result_dir = fold, name, bankgrid_dir(args.result_dir, name)
-            out.append(a)
-    return out
+    the folds inside a bank in the given order (grid_runs)."""
+    return grid_runs(args, names, folds, lambda name: dict(bank=name, result_dir=bankgrid_dir(args.result_dir, name)))
 
 
 def bankgrid_bytes(fold_footprints, D, itemsize, C, n_banks):
@@ -982,21 +991,11 @@ def bankgrid_bytes(fold_footprints, D, itemsize, C, n_banks):
 
 
 def write_bankgrid_summary(result_dir, names, folds, shot):
-    """{result_dir}/bank_grid_summary.csv: one line per bank in the given order -- the number of runs (folds) and the mean and
-    population standard deviation over them of the best validation AUC and of the test AUC at it, read from the banks'
-    best_results_* files (`best_val`, `test_at_best_val`).  -> path."""
-    rows = []
-    for name in names:
-        vals = []
-        for fold in folds:
-            with open(os.path.join(bankgrid_dir(result_dir, name), f"best_results_shot_{shot}_fold_{fold}.json")) as f:
-                r = json.load(f)
-            vals.append((r["best_val"], r["test_at_best_val"]))
-        v = np.asarray(vals, dtype=np.float64)
-        rows.append({"bank": name, "runs": len(vals), "best_val_mean": v[:, 0].mean(), "best_val_std": v[:, 0].std(),
-                     "test_auc_mean": v[:, 1].mean(), "test_auc_std": v[:, 1].std()})
+    """{result_dir}/bank_grid_summary.csv: one line per bank in the given order over its runs (the folds): summary_row's
+    columns.  -> path."""
+    rows = [{"bank": name, **summary_row([(bankgrid_dir(result_dir, name), fold) for fold in folds], shot)} for name in names]
     path = os.path.join(result_dir, "bank_grid_summary.csv")
-    pd.DataFrame(rows).to_csv(path, index=False, float_format="%.17g")
+    pd.DataFrame(rows).to_csv(path, index=False, float_format="%.17g")      # (moc_amd.sweep's bank_summary.csv format: the two tables are read side by side)
     return path
 
 
@@ -1008,23 +1007,13 @@ def main_banks(args_list, names, folds, models, optimizers, loaders_of_fold, dev
     what main() does for it alone with its bank installed.  -> list of result dicts, in run order."""
     G, F = len(names), len(folds)
     run = lambda g, i: g * F + i
-    tag = lambda a: f"[bank {a.bank}] [fold {a.fold}]"
     a0 = args_list[0]
-    st = [None] * (G * F)
-    for i in range(F):
-        zs = [(-1,) * G] * 3
-        if a0.check_zeroshot:
+    books = [ResultBook(a, prefix=f"[bank {a.bank}] [fold {a.fold}] ") for a in args_list]
+    if a0.check_zeroshot:
+        for i in range(F):      # fold-major: one zs_evaluation_banks per split of a fold gives every bank's numbers
             zs = [M.zs_evaluation_banks(ld, device, a0, banks) for ld in loaders_of_fold[i]]
-        for g in range(G):
-            a = args_list[run(g, i)]
-            os.makedirs(a.result_dir, exist_ok=True)
-            z = (zs[0][g], zs[1][g], zs[2][g])
-            if a0.check_zeroshot:
-                print(f"{tag(a)} Zero-shot Train: {z[0]}, Val: {z[1]}, Test: {z[2]}")
-                with open(os.path.join(a.result_dir, f"zs_results_shot_{a.shot}_fold_{a.fold}.json"), "w") as f:
-                    json.dump({"zs_train": z[0], "zs_val": z[1], "zs_test": z[2]}, f, indent=4)
-            st[run(g, i)] = dict(zs=z, best_val=0, test_at_best_val=0, test_acc_at_best_val=0, best_epoch=0,
-                                 model_path=os.path.join(a.result_dir, f"best_model_shot_{a.shot}_fold_{a.fold}.pt"))
+            for g in range(G):
+                books[run(g, i)].zero_shot(zs[0][g], zs[1][g], zs[2][g])
     trains = [loaders_of_fold[i][0] for _ in range(G) for i in range(F)]
     of_run = [g for g in range(G) for _ in range(F)]
     for epoch in range(getattr(a0, "epochs", 25)):
@@ -1035,26 +1024,11 @@ def main_banks(args_list, names, folds, models, optimizers, loaders_of_fold, dev
             ms = [models[run(g, i)] for g in range(G)]
             ev_tr = M.evaluation_banks(ms, tr, device, a0, banks)
             ev_va = M.evaluation_banks(ms, va, device, a0, banks)
-            better = [g for g in range(G) if ev_va[g]["auc"] > st[run(g, i)]["best_val"]]
+            better = [g for g in range(G) if books[run(g, i)].improves(ev_va[g])]
             ev_te = dict(zip(better, M.evaluation_banks([ms[g] for g in better], te, device, a0, [banks[g] for g in better]))) if better else {}
             for g in range(G):
-                a, s_ = args_list[run(g, i)], st[run(g, i)]
-                if g in ev_te:
-                    print(f"{tag(a)} Epoch: {epoch}, Train: {ev_tr[g]}, Val: {ev_va[g]}, Test: {ev_te[g]}")
-                    s_.update(best_val=ev_va[g]["auc"], test_at_best_val=ev_te[g]["auc"], test_acc_at_best_val=ev_te[g]["acc"], best_epoch=epoch)
-                    torch.save(models[run(g, i)].state_dict(), s_["model_path"])
-                else:
-                    print(f"{tag(a)} Epoch: {epoch}, Train: {ev_tr[g]}, Val: {ev_va[g]}")
-    out = []
-    for r, (a, s_) in enumerate(zip(args_list, st)):
-        print(f"{tag(a)} Best Val: {s_['best_val']}, Test at Best Val: {s_['test_at_best_val']}, Test acc: {s_['test_acc_at_best_val']}, "
-              f"Best Epoch: {s_['best_epoch']}")
-        res = {"zero_shot_train": s_["zs"][0], "zero_shot_val": s_["zs"][1], "zero_shot_test": s_["zs"][2],
-               "best_val": s_["best_val"], "test_at_best_val": s_["test_at_best_val"], "test_acc_at_best_val": s_["test_acc_at_best_val"],
-               "best_epoch": s_["best_epoch"], "best_model_path": s_["model_path"]}
-        with open(os.path.join(a.result_dir, f"best_results_shot_{a.shot}_fold_{a.fold}.json"), "w") as f:
-            json.dump(res, f, indent=4)
-        out.append(res)
+                books[run(g, i)].epoch(epoch, ms[g], ev_tr[g], ev_va[g], ev_te.get(g))
+    out = [book.close() for book in books]
     print("\nEnd training.")
     return out
 
@@ -1063,51 +1037,40 @@ def cli_bankgrid(args, bank_files):
     """`--banks` (with --folds or the one --fold): every (bank, fold) run in this process."""
     names = [n for n, _, _ in bank_files]
     folds = folds_of_rank(args.folds, 0, 1) if args.folds else [int(args.fold)]
-    C_ = _synthetic_classes(args) if args.synthetic else len(_label_map(args))
+    C_, itemsize = task_shape(args)
     for name, W, _ in bank_files:
         if W.size(1) != C_ or W.size(0) != FEATURE_DIM:
             raise SystemExit(f"--banks: {name}: W is [{W.size(0)}, {W.size(1)}]; this task needs [{FEATURE_DIM}, {C_}]")
-    device = torch.device("cuda", torch.cuda.current_device())
-    torch.cuda.set_device(device)
+    device = grid_device()      # one GPU: check_bankgrid_args refuses a launcher
     from . import runs as RUNS
+    # whole FOLDS per block, not whole banks as the other grids cut whole cells: a fold's banks share the score pass
     blocks = bankgrid_blocks(len(names), len(folds), RUNS.MAX_RUNS)
-    # the footprint of the largest block before a bag is loaded
-    itemsize = 2 if args.bag_dtype in ("bf16", "fp16") else 4
-    fps = {a.fold: split_footprints(a) for a in bankgrid_runs(args, names[:1], folds)}
-    need = bankgrid_bytes([fps[folds[i]] for i in blocks[0]], FEATURE_DIM, itemsize, C_, len(names))
-    free = torch.cuda.mem_get_info(device)[0]
-    if need > free:
-        raise SystemExit(f"--banks: a block of {len(names)} bank(s) x {len(blocks[0])} fold(s) needs about {need / 2**30:.1f} GiB of "
-                         f"device memory, {free / 2**30:.1f} GiB are free: name fewer folds")
+    fps = fold_footprints(args, folds)
+    refuse_unless_fits(f"--banks: a block of {len(names)} bank(s) x {len(blocks[0])} fold(s)",
+                       bankgrid_bytes([fps[folds[i]] for i in blocks[0]], FEATURE_DIM, itemsize, C_, len(names)), device)
     banks = [(W.to(device), We.to(device)) for _, W, We in bank_files]
     adam = {"lr": args.lr, "weight_decay": args.weight_decay}
     out = {}
+    # The block loop stands here and not in train_blocks: the splits belong to a fold, not to a run (prepare() also installs
+    # and prints a classifier bank, so it runs once per fold, not once per run), and the block goes to main_banks.
     for block in blocks:
         fs = [folds[i] for i in block]
         args_list = bankgrid_runs(args, names, fs)
-        loaders_of_fold, share = [], {}
-        for a in args_list[:len(fs)]:
-            loaders = prepare(a, device, share=share, share_train=True)
-            assert all(isinstance(ld, M.ResidentBags) for ld in loaders), "a bank grid needs resident splits (--resident 1)"
-            loaders_of_fold.append(loaders)
+        share = {}              # fresh per block: the blocks name different folds, so nothing recurs and the last block's splits can go
+        loaders_of_fold = [resident_splits(a, device, share, True, "a bank grid") for a in args_list[:len(fs)]]
         models, optimizers, gens = [], [], []
         for a in args_list:
-            a.n_classes = args_list[0].n_classes
-            # exactly what the bank's own `--fold F --seed S` command does with the default generator: seed, build the
-            # meta-learner, and the masks follow from wherever that leaves the stream -- the banks' runs of a fold start from
-            # equal parameters and equal generator states and share their masks
-            torch.manual_seed(args.seed)
-            model = M.senet(FEATURE_DIM, 4).to(device)
-            g = torch.Generator()
-            g.set_state(torch.get_rng_state())
+            a.n_classes = args_list[0].n_classes        # (prepare() left it on the first bank's namespaces only)
+            # every bank's run of a fold is seeded with --seed: equal parameters, equal generator states, shared masks
+            model, optimizer, g = build_run(args.seed, device, **adam)
             models.append(model)
-            optimizers.append(torch.optim.Adam(model.parameters(), **adam))
+            optimizers.append(optimizer)
             gens.append(g)
         res = main_banks(args_list, names, fs, models, optimizers, loaders_of_fold, device, gens, banks)
         for a, r in zip(args_list, res):
             out[(a.bank, a.fold)] = r
     print("bank grid summary:", write_bankgrid_summary(args.result_dir, names, folds, args.shot))
-    return [out[(n, f)] for n in names for f in folds]
+    return [out[(n, f)] for n in names for f in folds]         # bank-major over ALL folds, whatever the blocks were
 
 
 def cli(argv=None):
