@@ -866,10 +866,13 @@ __global__ __launch_bounds__(1024) void pool_w1_step_kernel(FusedArgs g, float* 
 //    (32-bit score keys: quad maxima, one ds_bpermute, fifteen row rotations for the ranks), lists the records >= T0
 //    (places by ballot, no LDS counter), requests the candidates' row ids / gates / candidate scores -- one round trip
 //    that the ranking loop hides -- and leaves the pooled rows' operands in LDS.  No second gather round for them.
+//    The class wave's work ENDS with the winners: nothing behind the barrier that the other waves' requests wait at
+//    needs the pooled mean.
 //  * Then ONE more round trip: the pairs' 256-column row pieces (three waves); the fourth wave requests their hidden
-//    activation of unit h, does the cross entropy under that request (butterflies by DPP) and forms dz / dh of the
-//    pairs itself, so that ONE barrier stands between the round trip and the gradient sums; the parameters this
-//    workgroup steps were requested at the top.
+//    activation of unit h, forms the C pooled means from the winners' values (lane c: class c, largest first), does the
+//    cross entropy under that request (butterflies by DPP) and forms dz / dh of the pairs itself, so that ONE barrier
+//    stands between the round trip and the gradient sums; the parameters this workgroup steps were requested at the
+//    top.  The publishing workgroup's fourth wave stores the slide's outputs as the last thing it does.
 // Falls back to the full scores inside the kernel when the records cannot prove exactness.
 struct TileStepArgs {
     // ---- first cache line (64 bytes): what the first loads need -- they are issued before the other lines are touched
@@ -1184,32 +1187,19 @@ __global__ __launch_bounds__(256, 4) void pool_w1_step_tiles_kernel(ArgsT args) 
             const int64_t rid = a.trid[s_c + jrec];
             const float4 lam = a.tlam[s_c + jrec];
             const float4 scv = a.tsc[s_c + jrec];
+            // (the list from LDS, one broadcast read per candidate: a loop of v_readlane on the score words with a count of
+            // equal words beside it -- ten instructions per candidate -- was measured LONGER, 0.56 -> 0.68-0.72 us)
             int rank = 0;
             for (int l = 0; l < n; ++l) rank += list[(size_t)c * PS_CAP + l] > mine ? 1 : 0;
             MOC_STAMP(12);
+            // The class wave's work ends with the winners: the waves behind the barrier need prid / topk_s for their
+            // requests.  The pooled mean (topv) is the fourth wave's business, under its own round trip.
             if (lane < n && rank < k) {
                 topk_s[c * K + rank] = (int)(~(unsigned)mine);
                 topv[c * 16 + rank] = key_to_float((unsigned)(mine >> 32));
                 const int p = c * k + rank;
                 prid[p] = rid; plam[p] = lam; psc[p] = scv;
             }
-            __builtin_amdgcn_wave_barrier();
-            // summed largest first: ONE LDS read puts value r on lane r, the chain of additions takes them from there
-            // (k dependent LDS reads on one lane were k round trips in front of the barrier every wave waits at)
-            const float tv = lane < k ? topv[c * 16 + lane] : 0.f;
-            float sum = 0.f;
-#pragma nounroll                                         // (unrolled, its sixteen conditions r < k live in SGPRs across the class loop)
-            for (int r = 0; r < k; ++r) sum += __uint_as_float((unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(tv), r));
-            if (lane == 0) {
-                pooled_s[c] = sum / (float)k;
-                if (wg0) {
-                    a.pooled_out[(int64_t)b * C + c] = pooled_s[c];
-                    if (a.topk_cnt_out) a.topk_cnt_out[(int64_t)b * C + c] = k;
-                }
-            }
-            if (a.topk_idx_out && wg0)
-                for (int r = lane; r < K; r += 64)
-                    a.topk_idx_out[((int64_t)b * C + c) * K + r] = r < k ? topk_s[c * K + r] : -1;
         }
     }
     __syncthreads();
@@ -1292,6 +1282,7 @@ __global__ __launch_bounds__(256, 4) void pool_w1_step_tiles_kernel(ArgsT args) 
     MOC_STAMP(15);
     // ---- round trip 2: the pairs' row pieces (three waves) and their hidden activation of unit h (the fourth)
     const int P = C * k;
+    float xv_out = 0.f;                                                              // fourth wave, lane c: class c's pooled logit
     if (wave == 3) {
         // Lane p is pair p: P <= 64, for step_plan gives this kernel only shapes with C * K <= 64 (pool_one with train;
         // launch_tile_step_as refuses others).  The wave REQUESTS the pairs' hidden activation, does the cross entropy of
@@ -1307,7 +1298,20 @@ __global__ __launch_bounds__(256, 4) void pool_w1_step_tiles_kernel(ArgsT args) 
         }
         // cross entropy, argmax and d loss / d pooled.  The logits sit on lanes 0 .. 15 (C <= 16): the two butterflies over
         // them (partners xor 8, 4, 2, 1; ties to the smaller class) move their operands by DPP, not through the LDS pipe
-        const float xv = lane < C ? pooled_s[lane] : -INFINITY;
+        // The logits.  Records path: lane c forms class c's pooled mean itself from the winners' values the class wave left
+        // in topv -- sixteen independent LDS reads in one batch, then the chain of additions, largest first, k of them (a
+        // sum padded with + 0.f would turn a -0 into +0).  Fall-back: pooled_s is there.
+        float xv = -INFINITY;
+        if (fast) {
+            float tv[16];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) tv[r] = topv[(lane < C ? lane : 0) * 16 + r];
+            float sum = 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) sum = r < k ? sum + tv[r] : sum;           // (a select, not an exit: no indexed registers)
+            if (lane < C) xv = sum / (float)k;
+        } else if (lane < C) xv = pooled_s[lane];
+        xv_out = xv;
         float mx = xv;
         int arg = lane < C ? lane : 0x7fffffff;
 #define MOC_CE_MAX(OFF)                                                                                               \
@@ -1323,8 +1327,9 @@ __global__ __launch_bounds__(256, 4) void pool_w1_step_tiles_kernel(ArgsT args) 
         se += row16_xor<8>(se); se += row16_xor<4>(se); se += row16_xor<2>(se); se += row16_xor<1>(se);
         const float lse = mx + logf(se);
         if (lane < C) dpool[lane] = expf(xv - lse) - (lane == y ? 1.f : 0.f);
+        const float xy = fast ? __uint_as_float((unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(xv), y & 15)) : pooled_s[y];
         if (lane == 0 && wg0) {
-            a.loss[b] = lse - pooled_s[y];
+            a.loss[b] = lse - xy;
             a.pred[b] = arg;
         }
         __builtin_amdgcn_wave_barrier();
@@ -1391,8 +1396,24 @@ __global__ __launch_bounds__(256, 4) void pool_w1_step_tiles_kernel(ArgsT args) 
     __syncthreads();                                     // the ONE barrier in front of the gradient loops: row pieces, dz, dh, h1s
     MOC_STAMP(16);
     MOC_STAMP(17);
+    // the slide's outputs of the records path (the fall-back has published its own), by the fourth wave of the publishing
+    // workgroup as the LAST thing it does: stores in front of the gradient sums or of Adam would stand in the way of
+    // their waits for the parameters' loads
+    auto publish = [&]() {
+        if (fast && wg0 && wave == 3) {
+            if (lane < C) {
+                a.pooled_out[(int64_t)b * C + lane] = xv_out;
+                if (a.topk_cnt_out) a.topk_cnt_out[(int64_t)b * C + lane] = k;
+            }
+            if (a.topk_idx_out)
+                for (int c = 0; c < C; ++c)
+                    for (int r = lane; r < K; r += 64)
+                        a.topk_idx_out[((int64_t)b * C + c) * K + r] = r < k ? topk_s[c * K + r] : -1;
+        }
+    };
     // ---- gradients of the owned elements, every sum over the pairs in ascending order (operands four pairs at a time:
-    // the additions stay in order, the LDS reads do not wait for each other)
+    // the additions stay in order, the LDS reads do not wait for each other.  All operands of up to 24 pairs requested
+    // in front of the first fmaf -- thirty reads, one counted wait -- was measured LONGER: 0.76-0.80 -> 1.08 us)
     float gr = 0.f;
     if (!tail_wg) {
         int p = 0;
@@ -1434,6 +1455,7 @@ __global__ __launch_bounds__(256, 4) void pool_w1_step_tiles_kernel(ArgsT args) 
         if (tail >= H + 4 * H) a.g_b2[tail - 5 * H] = gt;
         else if (tail >= H) a.g_W2[tail - H] = gt;
         else if (tail >= 0) a.g_b1[tail] = gt;
+        publish();
         return;
     }
     const float gs = ak.grad_scale;
@@ -1449,6 +1471,7 @@ __global__ __launch_bounds__(256, 4) void pool_w1_step_tiles_kernel(ArgsT args) 
         else if (tail >= H) { const int i = tail - H; a.W2out[w2outo + i] = pT; a.m_W2[po + i] = pTm; a.v_W2[po + i] = pTv; }
         else { a.b1[po + tail] = pT; a.m_b1[po + tail] = pTm; a.v_b1[po + tail] = pTv; }
     }
+    publish();
     MOC_STAMP(18);
     MOC_STAMP_MAX(35);
 }
