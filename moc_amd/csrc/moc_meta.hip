@@ -20,6 +20,7 @@
 #include "moc_meta_internal.h"
 #include <type_traits>
 #include "moc_p2p.h"
+#include "moc_step_lds.h"   // the step kernels' dynamic LDS: one layout per kernel, for the launch and for the carve
 
 int moc_check_batch(const moc_batch_t* B, const char* who);
 int moc_launch_topk_mean(const float* keys, int64_t key_stride, const float* vals, int64_t val_stride,
@@ -27,6 +28,10 @@ int moc_launch_topk_mean(const float* keys, int64_t key_stride, const float* val
                          int smallest, float* pooled, int32_t* idx_out, int32_t* cnt_out, hipStream_t s);
 
 using namespace moc_meta_internal;
+namespace lds = moc_step_lds;
+static_assert(lds::H == MOC_HIDDEN, "moc_step_lds.h carries the hidden width on its own");
+using lds::FIN_CHUNK;
+using lds::WD_PCH_MIN;
 
 namespace {
 
@@ -91,8 +96,6 @@ __device__ __forceinline__ AdamCoef step_coef(const FinishArgs& a) {
     return k;
 }
 
-constexpr int FIN_CHUNK = 256;   // pairs whose H1 rows are staged in LDS at a time (64 KiB)
-
 // grid (n): one workgroup per slide.  Eval: CE + argmax only.  Train (n == 1): also the
 // gradient "pairs" and the gradient/Adam of b1, W2, b2.
 __global__ __launch_bounds__(256) void finish_kernel(FinishArgs a) {
@@ -126,8 +129,9 @@ __global__ __launch_bounds__(256) void finish_kernel(FinishArgs a) {
     __syncthreads();
 
     // pairs p = (c, r): r-th pooled row of class c.  n_pair = sum_c cnt[c] <= C*K
-    float* dz = reinterpret_cast<float*>(smem);                 // [P][4]
-    int* prow = reinterpret_cast<int*>(dz + (size_t)C * a.K * 4);   // [P] position s of the pair's row
+    const lds::FinishLds Y = lds::finish_lds(C, a.K, 1);
+    float* dz = reinterpret_cast<float*>(smem + Y.dz);
+    int* prow = reinterpret_cast<int*>(smem + Y.prow);
     // every class pools the same number of rows: cnt = min(K, S)
     const int P = C * cnt;
     for (int p = threadIdx.x; p < P; p += 256) {
@@ -150,8 +154,8 @@ __global__ __launch_bounds__(256) void finish_kernel(FinishArgs a) {
     // H1 rows of the pairs go through LDS in chunks of FIN_CHUNK pairs (one coalesced round of gathers
     // per chunk): read per element from global memory, the W2 / b1 reductions below were P dependent
     // gathers long (68 us at C*K = 300).
-    float* H1s = reinterpret_cast<float*>(prow + (size_t)C * a.K);   // [FIN_CHUNK][H]
-    float* W2s = H1s + FIN_CHUNK * H;                                // [4][H]
+    float* H1s = reinterpret_cast<float*>(smem + Y.H1s);
+    float* W2s = reinterpret_cast<float*>(smem + Y.W2s);
     const int t = threadIdx.x, h = t & 63, g4 = t >> 6;
     W2s[t] = a.W2[t];
     float gW2 = 0.f, gb1 = 0.f;                 // W2[g4][h]; partial of b1[h] over the pairs p = g4 (mod 4)
@@ -220,9 +224,7 @@ __global__ __launch_bounds__(256) void finish_kernel(FinishArgs a) {
 // They go to a short LDS list per class, and one wave per class extracts them in value order
 // (K wave-wide max reductions over the short list, DPP row operations, no LDS round trips).
 constexpr int PS_VPT = 4;       // values per thread per class  (S <= 4096)
-constexpr int FS_MAX_DYN_LDS = 160 * 1024 - 64;   // the step kernel also holds a few static LDS words
 constexpr int FS_MAX_XS = 20480; // one-launch step: pair rows staged in LDS, C*K*D <= this many floats (80 KiB)
-constexpr int PS_CAP_MAX = 1024; // candidate list entries per class (the launch picks cap <= this)
 
 __device__ __forceinline__ float key_to_float(unsigned u) {
     return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u);
@@ -237,6 +239,12 @@ struct PoolLds {
     float *pooled_s, *dpool;             // [C] pooled logits, d loss / d pooled
     int *ncand, *topk_s;                 // [C] candidate counts, [C][K] pooled rows in value order
 };
+// the pooling block of a kernel's layout, as pointers
+__device__ __forceinline__ PoolLds pool_lds(unsigned char* smem, const lds::PoolBlockLds& B) {
+    return {reinterpret_cast<unsigned long long*>(smem + B.list), reinterpret_cast<unsigned long long*>(smem + B.wmax),
+            reinterpret_cast<float*>(smem + B.pooled_s), reinterpret_cast<float*>(smem + B.dpool),
+            reinterpret_cast<int*>(smem + B.ncand), reinterpret_cast<int*>(smem + B.topk_s)};
+}
 
 // cross entropy of the pooled logits, argmax and (train) d loss / d pooled: wave 0, one class per lane;
 // CE_OFF = widest xor offset (8: C <= 16, 32: C <= 64)
@@ -446,16 +454,11 @@ __global__ __launch_bounds__(1024) void pool_step_kernel(FinishArgs a, float* po
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int b = a.slide0 + blockIdx.x, C = a.C, K = a.K;
     // LDS carve (all dynamic)
-    unsigned long long* list = reinterpret_cast<unsigned long long*>(smem);          // [C][PS_CAP]
-    unsigned long long* wmax = list + (size_t)C * PS_CAP;                           // [C][16]
-    float* pooled_s = reinterpret_cast<float*>(wmax + (size_t)C * 16);               // [C]
-    float* dpool = pooled_s + C;                                                     // [C]
-    int* ncand = reinterpret_cast<int*>(dpool + C);                                  // [C]
-    int* topk_s = ncand + C;                                                         // [C][K]
-    float* dz = reinterpret_cast<float*>(topk_s + C * K);                            // [P][4]   (train)
-    float* H1s = dz + (size_t)C * K * 4;                                             // [P][H]
-    float* dhs = H1s + (size_t)C * K * H;                                            // [P][H]
-    float* W2s = dhs + (size_t)C * K * H;                                            // [4][H]
+    const lds::PoolStepLds Y = lds::pool_step_lds(C, K, PS_CAP, 1);   // (evaluation returns before it touches the train part)
+    float* dz = reinterpret_cast<float*>(smem + Y.dz);
+    float* H1s = reinterpret_cast<float*>(smem + Y.H1s);
+    float* dhs = reinterpret_cast<float*>(smem + Y.dhs);
+    float* W2s = reinterpret_cast<float*>(smem + Y.W2s);
     MOC_STAMP(10);
     // operands that do not depend on this slide's scores: requested first, consumed last
     float pW = 0.f, pM = 0.f, pV = 0.f;       // parameter / exp_avg / exp_avg_sq this thread will step
@@ -466,7 +469,9 @@ __global__ __launch_bounds__(1024) void pool_step_kernel(FinishArgs a, float* po
         else if (t >= 320 && t < 320 + H) { pW = a.b1[t - 320]; if (a.apply_adam) { pM = a.m_b1[t - 320]; pV = a.v_b1[t - 320]; } }
     }
     int64_t base;
-    const PoolLds L = {list, wmax, pooled_s, dpool, ncand, topk_s};
+    const PoolLds L = pool_lds(smem, Y.pool);
+    float* const dpool = L.dpool;
+    int* const topk_s = L.topk_s;
     const int k = pool_phase(a, b, L, PS_CAP, true, pooled_out, topk_idx_out, topk_cnt_out, &base);
     MOC_STAMP(14);
     if (!a.train) return;
@@ -582,21 +587,18 @@ __global__ __launch_bounds__(1024) void pool_w1_step_kernel(FusedArgs g, float* 
     // workgroups: half the Adam arithmetic per thread -- sixteen waves on one CU make that the kernel's last 2 us)
     const int HW = H / (int)gridDim.x, JN = HW >> 1;
     const int wg = blockIdx.x, h_lo = wg * HW;
-    unsigned long long* list = reinterpret_cast<unsigned long long*>(smem);          // [C][PS_CAP]
-    unsigned long long* wmax = list + (size_t)C * PS_CAP;                           // [C][16]
-    float* pooled_s = reinterpret_cast<float*>(wmax + (size_t)C * 16);               // [C]
-    float* dpool = pooled_s + C;                                                     // [C]
-    int* ncand = reinterpret_cast<int*>(dpool + C);                                  // [C]
-    int* topk_s = ncand + C;                                                         // [C][K]
-    float* dz = reinterpret_cast<float*>(topk_s + C * K);                            // [P][4]
-    float* H1s = dz + (size_t)C * K * 4;                                             // [P][H]
-    float* dhs = H1s + (size_t)C * K * H;                                            // [P][H]
-    float* W2s = dhs + (size_t)C * K * H;                                            // [4][H]
-    // (offsets from smem, which is 16-byte aligned, not address arithmetic through integers: the latter loses the LDS
-    // address space and every access through the pointer becomes a flat_ operation)
-    const size_t row_off = ((size_t)(reinterpret_cast<unsigned char*>(W2s + 4 * H) - smem) + 7) & ~(size_t)7;
-    int64_t* row_s = reinterpret_cast<int64_t*>(smem + row_off);                     // [P] bag rows of the pairs
-    float* xs = reinterpret_cast<float*>(smem + ((row_off + (size_t)C * K * 8 + 15) & ~(size_t)15));             // [P][D], 16-B aligned
+    // (offsets from smem, which is 16-byte aligned, rounded in the layout -- not address arithmetic through integers: that
+    // loses the LDS address space and every access through the pointer becomes a flat_ operation)
+    const lds::NarrowStepLds Y = lds::narrow_step_lds(C, K, D, PS_CAP);
+    const PoolLds L = pool_lds(smem, Y.pool);
+    float* const dpool = L.dpool;
+    int* const topk_s = L.topk_s;
+    float* dz = reinterpret_cast<float*>(smem + Y.dz);
+    float* H1s = reinterpret_cast<float*>(smem + Y.H1s);
+    float* dhs = reinterpret_cast<float*>(smem + Y.dhs);
+    float* W2s = reinterpret_cast<float*>(smem + Y.W2s);
+    int64_t* row_s = reinterpret_cast<int64_t*>(smem + Y.row_s);
+    float* xs = reinterpret_cast<float*>(smem + Y.xs);
     MOC_STAMP(10);
     // thread t: column d = t % D' of hidden units h_lo + JN*(t / D') + {0 .. JN-1}, D' = min(D, 512)
     const int t = threadIdx.x;
@@ -608,7 +610,6 @@ __global__ __launch_bounds__(1024) void pool_w1_step_kernel(FusedArgs g, float* 
     // hides them, and W2 with the pairs' gathers: at the top they sat in front of the slide's scores -- the first thing
     // the kernel waits for, and loads return in issue order -- and held 12 registers through the pooling.
     int64_t base;
-    const PoolLds L = {list, wmax, pooled_s, dpool, ncand, topk_s};
     const int k = pool_phase(a, b, L, PS_CAP, wg == 0, pooled_out, topk_idx_out, topk_cnt_out, &base);
     __syncthreads();
     MOC_STAMP(15);
@@ -1004,7 +1005,7 @@ __global__ __launch_bounds__(256, 4) void pool_w1_step_tiles_kernel(ArgsT args) 
     const bool tail_wg = !a.tail_inside && cb == (D >> 8); // (grid.x = D / 256 + 1; not gridDim: that pulls 256 bytes of hidden arguments into the segment)
     const bool tail_role = a.tail_inside ? cb == 0 : tail_wg;
     const bool wg0 = cb == 0 && h == 0;                                              // (of its run: publishes the slide's outputs)
-    constexpr int CL = 64;                                                            // candidates per class
+    constexpr int CL = lds::TILE_CL;                                                  // candidates per class
     MOC_STAMP(10);
     MOC_STAMP_MIN(33);
     MOC_STAMP_MAX(34);
@@ -1097,24 +1098,25 @@ __global__ __launch_bounds__(256, 4) void pool_w1_step_tiles_kernel(ArgsT args) 
     const int S = (!RUNS && a.S_host >= 0) ? a.S_host : a.n_sel[b];
     const int y = (int)a.labels[b];
     const int k = K < S ? K : S;
-    // LDS carve: the 16-byte things first
-    float4* plam = reinterpret_cast<float4*>(smem);                                  // [P] pairs' gates
-    float4* psc = plam + (size_t)C * K;                                              // [P] ... candidate scores
-    float* xs = reinterpret_cast<float*>(psc + (size_t)C * K);                       // [P][256] pairs' row pieces
-    float* dhs = xs + (size_t)C * K * 256;                                           // [P (+3)] dh of unit h, 16-byte aligned
-    float* dz = dhs + (((size_t)C * K + 3) & ~(size_t)3);                            // [P][4]
-    unsigned long long* list = reinterpret_cast<unsigned long long*>(dz + (size_t)C * K * 4);   // [C][PS_CAP]
-    unsigned long long* t0s = list + (size_t)C * PS_CAP;                             // [C] the bound T0 (as a key)
-    int64_t* prid = reinterpret_cast<int64_t*>(t0s + C);                             // [P]
-    int* lsrc = reinterpret_cast<int*>(prid + (size_t)C * K);                        // [C][CL] record of a candidate
-    float* topv = reinterpret_cast<float*>(lsrc + (size_t)C * CL);                   // [C][16]
-    float* pooled_s = topv + (size_t)C * 16;                                         // [C]
-    float* dpool = pooled_s + C;                                                     // [C]
-    int* ncand = reinterpret_cast<int*>(dpool + C);                                  // [C] the fall-back's counters (the records' lists are placed by ballot)
-    int* flagc = ncand + C;                                                          // [C] 1: the records cannot prove exactness
-    int* topk_s = flagc + C;                                                         // [C][K]
-    float* h1s = reinterpret_cast<float*>(topk_s + C * K);                           // [P]
-    float* w2s = h1s + (size_t)C * K;                                                // [4]
+    // LDS carve (the sink above is Y.sink: it reaches the kernel as a.sink_off, ahead of everything this needs)
+    const lds::TileStepLds Y = lds::tile_step_lds(C, K, PS_CAP);
+    float4* plam = reinterpret_cast<float4*>(smem + Y.plam);
+    float4* psc = reinterpret_cast<float4*>(smem + Y.psc);
+    float* xs = reinterpret_cast<float*>(smem + Y.xs);
+    float* dhs = reinterpret_cast<float*>(smem + Y.dhs);
+    float* dz = reinterpret_cast<float*>(smem + Y.dz);
+    unsigned long long* list = reinterpret_cast<unsigned long long*>(smem + Y.list);
+    unsigned long long* t0s = reinterpret_cast<unsigned long long*>(smem + Y.t0s);
+    int64_t* prid = reinterpret_cast<int64_t*>(smem + Y.prid);
+    int* lsrc = reinterpret_cast<int*>(smem + Y.lsrc);
+    float* topv = reinterpret_cast<float*>(smem + Y.topv);
+    float* pooled_s = reinterpret_cast<float*>(smem + Y.pooled_s);
+    float* dpool = reinterpret_cast<float*>(smem + Y.dpool);
+    int* ncand = reinterpret_cast<int*>(smem + Y.ncand);
+    int* flagc = reinterpret_cast<int*>(smem + Y.flagc);
+    int* topk_s = reinterpret_cast<int*>(smem + Y.topk_s);
+    float* h1s = reinterpret_cast<float*>(smem + Y.h1s);
+    float* w2s = reinterpret_cast<float*>(smem + Y.w2s);
     if (t < 4) { w2s[t] = w2v; if (tail >= H) pT = w2v; }
     const int ntile = (S + 15) >> 4;
     for (int c = wave; c < C; c += 4) {                                              // ---- class c: this wave's, start to end
@@ -1487,8 +1489,6 @@ __global__ __launch_bounds__(256, 4) void pool_w1_step_tiles_kernel(ArgsT args) 
 // its hidden row: dh[p][h] = mask_p[h] ? sum_i dz[p][i] W2[i][h] : 0 is re-formed on the fly.  The small
 // tensors are split by hidden unit: workgroup g also owns W2[:, 4g..4g+3] and b1[4g..4g+3] (16 wave-wide
 // reductions over the pairs), workgroup 0 b2.
-constexpr int WD_PCH_MIN = 128;  // pairs per chunk of the W1 gradient, at least (wide_pch: all pairs in one chunk when they fit)
-
 
 __global__ __launch_bounds__(1024) void pool_w1_step_wide_kernel(FusedArgs g, float* pooled_out, int32_t* topk_idx_out,
                                                                  int32_t* topk_cnt_out, int PS_CAP, int region_bytes,
@@ -1501,25 +1501,21 @@ __global__ __launch_bounds__(1024) void pool_w1_step_wide_kernel(FusedArgs g, fl
     moc_kernarg_touch<sizeof(FusedArgs)>();
     MOC_STAMP(40);
     const int esz = a.xdt == MOC_F32 ? 4 : 2;
-    const int PMAX = C * K;
     // ---- LDS carve
-    unsigned char* region = smem;                                                    // [C][PS_CAP] u64  |  [P][DS] raw
-    unsigned long long* list = reinterpret_cast<unsigned long long*>(region);
-    unsigned long long* wmax = reinterpret_cast<unsigned long long*>(smem + region_bytes);   // [C][16]
-    float* pooled_s = reinterpret_cast<float*>(wmax + (size_t)C * 16);
-    float* dpool = pooled_s + C;
-    int* ncand = reinterpret_cast<int*>(dpool + C);
-    int* topk_s = ncand + C;                                                         // [C][K]
-    // (16-byte aligned; sixteen rows of slack behind the pairs: the product below walks them in groups of sixteen)
-    // (the offset is rounded, not the address: a pointer rebuilt from an integer is a FLAT pointer to the compiler)
-    float* dz = reinterpret_cast<float*>(smem + (((reinterpret_cast<unsigned char*>(topk_s + PMAX) - smem) + 15) & ~(ptrdiff_t)15));   // [P + 16][4]
-    float* h1o = dz + (size_t)(PMAX + 16) * 4;                                       // [P][4]
-    const int PM = (PMAX + 16 + 3) & ~3;                                             // pairs per plane of the ReLU masks
-    unsigned* mask = reinterpret_cast<unsigned*>(h1o + (size_t)PMAX * 4);            // [2][PM]: bits of hidden units 0..31 | 32..63
-    int* sidx_s = reinterpret_cast<int*>(mask + (size_t)PM * 2);                     // [P]
-    float* W2s = reinterpret_cast<float*>(sidx_s + PMAX);                            // [4][H]
-    float* red = W2s + 4 * H;                                                        // [32]
-    int64_t* prow_s = reinterpret_cast<int64_t*>(smem + (((reinterpret_cast<unsigned char*>(red + 32) - smem) + 7) & ~(ptrdiff_t)7));   // [P]
+    const lds::WideStepLds Y = lds::wide_step_lds_behind(C, K, region_bytes);   // (the host's wide_step_lds: region_bytes is p.wide_region)
+    unsigned char* region = smem + Y.region;
+    const PoolLds L = pool_lds(smem, Y.pool);
+    float* const pooled_s = L.pooled_s;
+    float* const dpool = L.dpool;
+    int* const topk_s = L.topk_s;
+    float* dz = reinterpret_cast<float*>(smem + Y.dz);
+    float* h1o = reinterpret_cast<float*>(smem + Y.h1o);
+    const int PM = Y.PM;
+    unsigned* mask = reinterpret_cast<unsigned*>(smem + Y.mask);
+    int* sidx_s = reinterpret_cast<int*>(smem + Y.sidx_s);
+    float* W2s = reinterpret_cast<float*>(smem + Y.W2s);
+    float* red = reinterpret_cast<float*>(smem + Y.red);
+    int64_t* prow_s = reinterpret_cast<int64_t*>(smem + Y.prow_s);
 
     // ---- operands that do not depend on this slide: requested first, consumed last.
     // The W1 gradient of this workgroup is a [64 x DS] tile product on the fp32 matrix cores: wave w < 4*DS/16
@@ -1628,7 +1624,6 @@ __global__ __launch_bounds__(1024) void pool_w1_step_wide_kernel(FusedArgs g, fl
                 dz[pr * 4 + i] = (a.use_bits >> i & 1u) ? gk * sc[i] * lv[i] * (1.f - lv[i]) : 0.f;
         }
     } else {
-        const PoolLds L = {list, wmax, pooled_s, dpool, ncand, topk_s};
         k = pool_phase<8, 32, 2>(a, b, L, PS_CAP, wg == 0, pooled_out, topk_idx_out, topk_cnt_out, &base);
         if (t < 4 * H) W2s[t] = w2r;
         __syncthreads();
@@ -1807,7 +1802,7 @@ __global__ __launch_bounds__(1024) void pool_w1_step_wide_kernel(FusedArgs g, fl
     }
     __syncthreads();
     if (ksplit) {                                          // second halves -> LDS (the chunk buffers are free), first halves add them
-        float* part = reinterpret_cast<float*>(region);    // [8 tiles][4][64]
+        float* part = reinterpret_cast<float*>(smem + Y.part);   // [8 tiles][4][64]
         if (wave >= 8) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) part[(twave * 4 + i) * 64 + lane] = gacc[i];
@@ -2072,40 +2067,9 @@ int launch_pool(const moc_batch_t* B, const moc_meta_ws_t* ws, int slide0, int n
                                 slide0, n, B->C, B->topk, 0, ws->pooled, ws->topk_idx, ws->topk_cnt, s);
 }
 
-// ---- the step kernels' dynamic LDS, by shape
-size_t fused_step_smem(const moc_batch_t* B, int cap) {
-    const size_t C = B->C, K = B->topk, PK = C * K;
-    return C * cap * 8 + C * 16 * 8 + C * 4 * 3 + C * K * 4 + PK * (4 * 4 + 2 * H * 4) + 4 * H * 4 + PK * 8 + 16 +
-           PK * (size_t)B->D * 4;
-}
-// (+ 1 KiB at the very end: the prefetch's sink)
-constexpr size_t TILES_SINK = 1024;
-size_t tiles_step_smem(const moc_batch_t* B, int cap) {
-    const size_t C = B->C, K = B->topk, P = C * K, CL = 64;
-    return TILES_SINK + P * 32 + P * 256 * 4 + (P + 4) * 4 + P * 16 + C * cap * 8 + C * 8 + P * 8 + C * CL * 4 + C * 16 * 4 + C * 4 * 4 + P * 4 + P * 4 + 16 + 64;
-}
-int wide_cap(const moc_batch_t* B) {
-    int cap = 1024;
-    while (cap > 64 && (size_t)B->C * cap * 8 > 64 * 1024) cap >>= 1;
-    return cap;
-}
-size_t wide_region(const moc_batch_t* B, int pch) {
-    const size_t lists = (size_t)B->C * wide_cap(B) * 8;
-    const size_t rows = (size_t)pch * ((B->D / 16) * moc_elem_size(B->dtype));   // row pieces of one chunk (dh is formed in the product loop)
-    return ((lists > rows ? lists : rows) + 15) & ~(size_t)15;
-}
-size_t wide_smem(const moc_batch_t* B, int pch) {
-    const size_t C = B->C, PK = C * B->topk;
-    return wide_region(B, pch) + C * 16 * 8 + C * 4 * 3 + PK * 4 + PK * 16 * 2 + PK * 8 + PK * 4 + (4 * H + 32) * 4 + 8 + PK * 8
-           + 16 + 16 * 16 + 2 * 20 * 4;      // dz aligned to 16 bytes, its sixteen slack rows, the mask planes' padding
-}
-// pairs per chunk of the W1 gradient: all C * K of them in ONE chunk when its row pieces fit beside the rest
-// (EBRAINS-30: 300 pairs, 38 KiB at fp32; the 64-way shape: 640 pairs, 80 KiB at fp16) -- one gather round trip and one
-// barrier instead of one per chunk; else the largest multiple of 32 that fits, at least WD_PCH_MIN
-int wide_pch(const moc_batch_t* B) {
-    int pch = (B->C * B->topk + 31) & ~31;
-    while (pch > WD_PCH_MIN && wide_smem(B, pch) > (size_t)FS_MAX_DYN_LDS) pch -= 32;
-    return pch < WD_PCH_MIN ? WD_PCH_MIN : pch;
+// the wide step's layout of a batch, at `pch` pairs per chunk
+lds::WideStepLds wide_lds(const moc_batch_t* B, int pch) {
+    return lds::wide_step_lds(B->C, B->topk, B->D, (int)moc_elem_size(B->dtype), pch, lds::wide_cap(B->C));
 }
 }  // namespace
 
@@ -2114,26 +2078,28 @@ StepPlan moc_meta_internal::step_plan(const moc_batch_t* B, const moc_meta_ws_t*
     static const bool tiles_off = getenv("MOC_TILE_RECORDS") && atoi(getenv("MOC_TILE_RECORDS")) == 0;   // diagnostic: the round-3 step
     StepPlan p = {};
     const int sb = s_bound(B);
-    p.cap = B->C <= 8 ? PS_CAP_MAX : PS_CAP_MAX / 2;
+    p.cap = lds::step_cap(B->C);
     p.pool_one = B->topk <= 16 && B->C <= 16 && sb <= 64 * 16 * PS_VPT && (!train || B->C * B->topk <= 64);
     if (!train || !ws->W2_alt) return p;                    // the one-launch steps ping-pong W2
-    const size_t lds = FS_MAX_DYN_LDS, narrow = fused_step_smem(B, p.cap), tiles = tiles_step_smem(B, p.cap);
     // narrow (pool_w1_step_kernel): pool_step_kernel's shapes, when the pairs' rows fit in LDS
-    if (p.pool_one && B->D <= 1024 && (int64_t)B->C * B->topk * B->D <= FS_MAX_XS && narrow <= lds) {
-        p.kind = STEP_NARROW; p.smem = narrow;
+    // (a layout is asked only behind its kernel's shape limits: its offsets are 32-bit)
+    const bool rows_fit = p.pool_one && B->D <= 1024 && (int64_t)B->C * B->topk * B->D <= FS_MAX_XS;
+    if (rows_fit && lds::narrow_step_lds(B->C, B->topk, B->D, p.cap).bytes <= lds::NARROW_MAX_LDS) {
+        p.kind = STEP_NARROW; p.smem = lds::narrow_step_lds(B->C, B->topk, B->D, p.cap).bytes;
+        const int tiles = lds::tile_step_lds(B->C, B->topk, p.cap).bytes;
         // over the forward's tile records (pool_w1_step_tiles_kernel): the caller has given the record arrays, a class's
         // records are at most sixteen keys per lane; its workgroups exchange nothing
         const bool records = ws->tile_ws && B->row_off_host &&
                              ws->tile_ws_bytes >= (int64_t)tile_bytes(tile_slots(B->total_rows, B->n_slides, B->C));
-        if (!exchange && !tiles_off && records && moc_cdiv(sb, 16) * TILE_R <= 16 * 64 && tiles <= lds) {
+        if (!exchange && !tiles_off && records && moc_cdiv(sb, 16) * TILE_R <= 16 * 64 && tiles <= lds::TILE_MAX_LDS) {
             p.kind = STEP_TILES; p.smem = tiles;
         }
         return p;
     }
     // wide (pool_w1_step_wide_kernel): C <= 64, K <= 16, D/16 = 32 or 64 columns per workgroup, every pair's piece in LDS
-    if (B->topk <= 16 && B->C <= 64 && B->D % 512 == 0 && B->D <= 1024 && wide_smem(B, WD_PCH_MIN) <= lds) {
-        p.kind = STEP_WIDE; p.pch = wide_pch(B); p.wide_cap = wide_cap(B);
-        p.wide_region = (int)wide_region(B, p.pch); p.smem = wide_smem(B, p.pch);
+    if (B->topk <= 16 && B->C <= 64 && B->D % 512 == 0 && B->D <= 1024 && wide_lds(B, WD_PCH_MIN).bytes <= lds::WIDE_MAX_LDS) {
+        p.kind = STEP_WIDE; p.pch = lds::wide_pch(B->C, B->topk, B->D, (int)moc_elem_size(B->dtype)); p.wide_cap = lds::wide_cap(B->C);
+        p.wide_region = wide_lds(B, p.pch).region_bytes; p.smem = wide_lds(B, p.pch).bytes;
         // pooling inside the kernel: every one of the 16 workgroups ranks all C classes for itself -- fine for a few
         // ten thousand scores, not for EBRAINS-30's 30 x 7,500 (measured: 88 us against 11.4 + 28 with one workgroup per
         // class in topk_mean_kernel first); beyond 8,192 rows it does not fit the registers at all
@@ -2154,14 +2120,14 @@ int step_attrs() {
             if (!failed[0] && hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess)
                 snprintf(failed, sizeof(failed), "%s to %d bytes", name, bytes);
         };
-        raise("finish_kernel", (const void*)finish_kernel, 159 * 1024);
-        raise("pool_step_kernel", (const void*)pool_step_kernel, 160 * 1024);
-        raise("pool_w1_step_kernel", (const void*)pool_w1_step_kernel, FS_MAX_DYN_LDS);
-        raise("pool_w1_step_wide_kernel", (const void*)pool_w1_step_wide_kernel, FS_MAX_DYN_LDS);
+        raise("finish_kernel", (const void*)finish_kernel, lds::FINISH_MAX_LDS);
+        raise("pool_step_kernel", (const void*)pool_step_kernel, lds::POOL_STEP_MAX_LDS);
+        raise("pool_w1_step_kernel", (const void*)pool_w1_step_kernel, lds::NARROW_MAX_LDS);
+        raise("pool_w1_step_wide_kernel", (const void*)pool_w1_step_wide_kernel, lds::WIDE_MAX_LDS);
 #define MOC_TILES_ATTR(VQ)                                                                                                    \
-        raise("pool_w1_step_tiles_kernel", (const void*)pool_w1_step_tiles_kernel<VQ, TileStepArgs>, FS_MAX_DYN_LDS);        \
-        raise("pool_w1_step_tiles_kernel(runs)", (const void*)pool_w1_step_tiles_kernel<VQ, TileStepArgsRuns>, FS_MAX_DYN_LDS); \
-        raise("pool_w1_step_tiles_kernel(runs_hp)", (const void*)pool_w1_step_tiles_kernel<VQ, TileStepArgsRunsHp>, FS_MAX_DYN_LDS)
+        raise("pool_w1_step_tiles_kernel", (const void*)pool_w1_step_tiles_kernel<VQ, TileStepArgs>, lds::TILE_MAX_LDS);     \
+        raise("pool_w1_step_tiles_kernel(runs)", (const void*)pool_w1_step_tiles_kernel<VQ, TileStepArgsRuns>, lds::TILE_MAX_LDS); \
+        raise("pool_w1_step_tiles_kernel(runs_hp)", (const void*)pool_w1_step_tiles_kernel<VQ, TileStepArgsRunsHp>, lds::TILE_MAX_LDS)
         MOC_TILES_ATTR(4); MOC_TILES_ATTR(8); MOC_TILES_ATTR(12); MOC_TILES_ATTR(16);
 #undef MOC_TILES_ATTR
     });
@@ -2199,9 +2165,10 @@ int launch_finish(const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws_t
     FinishArgs a = finish_args(B, M, ws, labels, slide0, train, apply_adam, use_bits, k);
     a.topk_idx = ws->topk_idx; a.topk_cnt = ws->topk_cnt;
     a.pair_dh = ws->pair_dh; a.pair_row = ws->pair_row; a.n_pair = ws->n_pair;
-    const size_t smem = train ? (size_t)B->C * B->topk * (4 * sizeof(float) + sizeof(int)) +
-                                (size_t)(FIN_CHUNK + 4) * H * sizeof(float) : 0;
-    MOC_REQUIRE(smem <= 159 * 1024, "finish: C*topk = %d too large", B->C * B->topk);
+    // (the layout counts in 32 bits, and topk has no bound of its own: the pairs are checked, which is the same check)
+    MOC_REQUIRE(!train || (int64_t)B->C * B->topk <= lds::FINISH_MAX_PAIRS, "finish_kernel: C = %d, topk = %d: more than %d pairs (%d B of LDS)",
+                B->C, B->topk, lds::FINISH_MAX_PAIRS, lds::FINISH_MAX_LDS);
+    const int smem = lds::finish_lds(B->C, B->topk, train).bytes;
     finish_kernel<<<n, 256, smem, s>>>(a);
     MOC_CHECK_LAUNCH("moc_finish");
     return MOC_OK;
@@ -2217,8 +2184,9 @@ int launch_pool_finish(const StepPlan& p, const moc_batch_t* B, const moc_meta_t
     FinishArgs a = finish_args(B, M, ws, labels, slide0, train, apply_adam, use_bits, k);
     finish_rows(a, B, ws, slide0, n == 1);
     a.pair_dh = ws->pair_dh; a.pair_row = ws->pair_row; a.n_pair = ws->n_pair;
-    const size_t C = B->C, K = B->topk, PK = train ? C * K : 0;
-    const size_t smem = C * p.cap * 8 + C * 16 * 8 + C * 4 * 3 + C * K * 4 + PK * (4 * 4 + 2 * H * 4) + 4 * H * 4;
+    const int smem = lds::pool_step_lds(B->C, B->topk, p.cap, train).bytes;   // (pool_one: C, topk <= 16)
+    MOC_REQUIRE(smem <= lds::POOL_STEP_MAX_LDS, "pool_step_kernel: C = %d, topk = %d, cap = %d, train = %d need %d B of LDS (> %d)",
+                B->C, B->topk, p.cap, train, smem, lds::POOL_STEP_MAX_LDS);
     pool_step_kernel<<<n, 1024, smem, s>>>(a, ws->pooled, ws->topk_idx, ws->topk_cnt, p.cap);
     MOC_CHECK_LAUNCH("moc_pool_step");
     return MOC_OK;
@@ -2256,7 +2224,7 @@ TileStepArgs tile_step_args(const StepPlan& p, const moc_batch_t* B, const moc_m
     ta.base = B->row_off_host[slide]; ta.adam = k;
     ta.row_off = B->row_off; ta.prefetch_next = 0;
     ta.S_host = B->n_sel_host ? B->n_sel_host[slide] : -1;
-    ta.sink_off = (int)(p.smem - TILES_SINK);
+    ta.sink_off = lds::tile_step_lds(B->C, B->topk, p.cap).sink;
     if (tab) { ta.adam_tab = tab->tab; ta.adam_ctr = tab->ctr; ta.adam_pos = tab->pos; }
     ta.apply_adam = apply_adam; ta.use_bits = use_bits; ta.img_dt = B->dtype;
     ta.H1 = ws->H1; ta.X = (const unsigned char*)B->X;
@@ -2274,6 +2242,8 @@ template <typename ArgsT>
 int launch_tile_step_as(const StepPlan& p, const moc_batch_t* B, const ArgsT& args, int runs, int tb, hipStream_t s) {
     const TileStepArgs& ta = tile_common(args);
     MOC_REQUIRE(B->C * B->topk <= 64, "moc_fused_step(tiles): C * topk = %d pairs, one wave forms at most 64", B->C * B->topk);
+    MOC_REQUIRE(p.smem == (size_t)lds::tile_step_lds(B->C, B->topk, p.cap).bytes && p.smem <= (size_t)lds::TILE_MAX_LDS,
+                "pool_w1_step_tiles_kernel: C = %d, topk = %d, cap = %d need %zu B of LDS (> %d)", B->C, B->topk, p.cap, p.smem, lds::TILE_MAX_LDS);
     const dim3 grid(B->D / 256 + (ta.tail_inside ? 0 : 1), H, runs);   // D / 256 column blocks of W1 (+ the tail workgroup), per hidden unit
 #define MOC_TILES_LAUNCH(VQ) pool_w1_step_tiles_kernel<VQ, ArgsT><<<grid, 256, p.smem, s>>>(args)
     const int vq = moc_cdiv((int64_t)tb * TILE_R, 64);                 // keys per lane of a class wave
@@ -2321,11 +2291,17 @@ int launch_fused_step(const StepPlan& p, const moc_batch_t* B, const moc_meta_t*
             if (int rc = launch_pool(B, ws, slide, 1, s)) return rc;
             a.topk_idx = ws->topk_idx; a.topk_cnt = ws->topk_cnt;
         }
+        MOC_REQUIRE(p.smem == (size_t)wide_lds(B, p.pch).bytes && p.wide_region == wide_lds(B, p.pch).region_bytes && p.smem <= (size_t)lds::WIDE_MAX_LDS,
+                    "pool_w1_step_wide_kernel: C = %d, topk = %d, D = %d, pch = %d need %zu B of LDS (> %d)", B->C, B->topk, B->D, p.pch,
+                    p.smem, lds::WIDE_MAX_LDS);
         pool_w1_step_wide_kernel<<<H / 4, 1024, p.smem, s>>>(g, ws->pooled, ws->topk_idx, ws->topk_cnt, p.wide_cap, p.wide_region,
                                                              p.external, p.pch);
         MOC_CHECK_LAUNCH("moc_fused_step(wide)");
         return MOC_OK;
     }
+    MOC_REQUIRE(p.smem == (size_t)lds::narrow_step_lds(B->C, B->topk, B->D, p.cap).bytes && p.smem <= (size_t)lds::NARROW_MAX_LDS,
+                "pool_w1_step_kernel: C = %d, topk = %d, D = %d, cap = %d need %zu B of LDS (> %d)", B->C, B->topk, B->D, p.cap, p.smem,
+                lds::NARROW_MAX_LDS);
     // 32 workgroups of two hidden units each, unless the gradient is exchanged inside the kernel (16 channels)
     pool_w1_step_kernel<<<g.x.world > 1 ? H / 4 : H / 2, 1024, p.smem, s>>>(g, ws->pooled, ws->topk_idx, ws->topk_cnt, p.cap);
     MOC_CHECK_LAUNCH("moc_fused_step");

@@ -160,3 +160,63 @@ def assert_adam_params_close(got, exp, v_exp, step, grad_noise, lr=1e-3, base=2e
     bad = np.abs(got - exp) > allowed
     assert not bad.any(), (f"{what}: {int(bad.sum())} params outside the Adam noise bound; worst "
                            f"{np.abs(got - exp)[bad].max():.3e} (allowed {allowed[bad].min():.3e})")
+
+
+# ---- the gradient-only step (moc_train_grad) against autograd on the oracle: test_gpu_parity.py, test_gpu_step_lds.py
+GRAD_STEP_TOPJ, GRAD_STEP_SIZES = 40, (700, 900, 800)
+_grad_step_tasks = {}
+
+
+def grad_step_task(C, K, D, dtype):
+    """Bank, three slides in `dtype`, labels, and autograd's gradients of the oracle's loss for each slide (computed once
+    per shape)."""
+    from oracle import moc_oracle as O
+    key = (C, K, D, dtype)
+    if key not in _grad_step_tasks:
+        W, We = synth.make_bank(600 + C, D, C)
+        bags, labels = synth.make_slide_set(6600 + C, list(GRAD_STEP_SIZES), D, We, C)
+        bags = [b.to(dtype) for b in bags]
+        torch.manual_seed(9)
+        ref = O.Senet(D, 4)
+        exp = []
+        for bag, label in zip(bags, labels):
+            sr = O.slide_process(bag.to(torch.float32), W, We, C, GRAD_STEP_TOPJ, mask=None)
+            pooled = O.pool_top(O.mix_train(ref(sr["selected_feat"]), sr), [K])[1][K]
+            loss = torch.nn.functional.cross_entropy(pooled, torch.tensor([label]))
+            grads = torch.autograd.grad(loss, list(ref.parameters()))
+            exp.append(torch.cat([t.reshape(-1) for t in grads]).numpy())
+        _grad_step_tasks[key] = (W, We, bags, labels, exp)
+    return _grad_step_tasks[key]
+
+
+def grad_step_batch(dev, C, K, D, dtype, masked=False):
+    """The task's slides as a batch after phase A, its labels on the device and a meta-learner initialised as the oracle's.
+    masked: the batch carries a mask of ones -- the same rows, but a batch that trains, for which the engine allocates the
+    forward's tile records (engine.TILE_RECORDS)."""
+    from moc_amd import engine as E, main_moc as M
+    W, We, bags, labels, _ = grad_step_task(C, K, D, dtype)
+    torch.manual_seed(9)
+    model = M.senet(D, 4).to(dev)
+    M.set_classifier_bank(W.to(dev), We.to(dev))
+    X, sz = M._pack(bags, dev, dtype)
+    mask = torch.ones(sum(GRAD_STEP_SIZES), dtype=torch.uint8) if masked else None
+    batch = E.SlideBatch(X, sz, C, C + 4, GRAD_STEP_TOPJ, K, [], mask=mask)
+    batch.phase_a(E.Bank.get(M.zeroshot_weights, M.zeroshot_weights_ext, dtype, dev))
+    lab = torch.tensor(labels, dtype=torch.int64, device=dev)
+    return batch, lab, E.MetaState(model, None, need_grads=True)
+
+
+def grad_step_grads(batch, lab, meta):
+    """moc_train_grad slide by slide -> (the flat gradients, what the step left in n_pair[0]) per slide"""
+    from moc_amd import engine as E
+    out = []
+    for s_i in range(len(GRAD_STEP_SIZES)):
+        E.train_grad(batch, meta, lab, s_i, 15)
+        got = torch.cat([t.reshape(-1) for t in meta.grads]).cpu().numpy()
+        out.append((got, int(batch.meta_ws()[0]["n_pair"].cpu()[0])))
+    return out
+
+
+def assert_grad_step_matches_autograd(got, C, K, D, dtype):
+    for (g, _), exp in zip(got, grad_step_task(C, K, D, dtype)[4]):
+        np.testing.assert_allclose(g, exp, atol=2e-6, rtol=1e-4)

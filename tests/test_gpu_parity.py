@@ -486,30 +486,7 @@ def test_reference_loop_body_kept_by_the_caller_runs_on_hip(dev):
 def test_gradient_only_step_matches_autograd(dev, C, K, D, dtype):
     """moc_train_grad (the data-parallel step's first half: gradients out, no update) on the narrow and the
     wide one-launch kernels against autograd on the oracle."""
-    M, E = _mm(), _engine()
-    j, sizes = 40, [700, 900, 800]
-    W, We = synth.make_bank(600 + C, D, C)
-    bags, labels = synth.make_slide_set(6600 + C, sizes, D, We, C)
-    bags = [b.to(dtype) for b in bags]
-    torch.manual_seed(9)
-    ref = O.Senet(D, 4)
-    torch.manual_seed(9)
-    model = M.senet(D, 4).to(dev)
-    M.set_classifier_bank(W.to(dev), We.to(dev))
-    X, sz = M._pack(bags, dev, dtype)
-    batch = E.SlideBatch(X, sz, C, C + 4, j, K, [])
-    batch.phase_a(E.Bank.get(M.zeroshot_weights, M.zeroshot_weights_ext, dtype, dev))
-    lab = torch.tensor(labels, dtype=torch.int64, device=dev)
-    meta = E.MetaState(model, None, need_grads=True)
-    for s_i in range(len(sizes)):
-        E.train_grad(batch, meta, lab, s_i, 15)
-        got = torch.cat([t.reshape(-1) for t in meta.grads]).cpu().numpy()
-        sr = O.slide_process(bags[s_i].to(torch.float32), W, We, C, j, mask=None)
-        pooled = O.pool_top(O.mix_train(ref(sr["selected_feat"]), sr), [K])[1][K]
-        loss = torch.nn.functional.cross_entropy(pooled, torch.tensor([labels[s_i]]))
-        grads = torch.autograd.grad(loss, list(ref.parameters()))
-        exp = torch.cat([t.reshape(-1) for t in grads]).numpy()
-        np.testing.assert_allclose(got, exp, atol=2e-6, rtol=1e-4)
+    H.assert_grad_step_matches_autograd(H.grad_step_grads(*H.grad_step_batch(dev, C, K, D, dtype)), C, K, D, dtype)
 
 
 def test_train_function_matches_oracle_epoch(dev):
