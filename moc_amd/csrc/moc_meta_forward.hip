@@ -1389,7 +1389,7 @@ int check_fwd_runs(const moc_batch_t* B, const moc_runs_t* R, const char* who, c
     MOC_REQUIRE(R, "%s: null runs", who);
     MOC_REQUIRE(R->n_runs >= 1 && R->n_runs <= MOC_MAX_RUNS, "%s: n_runs=%d outside 1 .. %d", who, R->n_runs, MOC_MAX_RUNS);
     MOC_REQUIRE(R->slide_stride == 0, "%s: slide_stride=%d must be 0 (%s)", who, R->slide_stride, stride0_why);
-    MOC_REQUIRE(R->par_stride >= (int64_t)H * B->D + H + 4 * H + 4, "%s: par_stride=%lld smaller than one meta-learner", who,
+    MOC_REQUIRE(R->par_stride >= n_params(B->D), "%s: par_stride=%lld smaller than one meta-learner", who,
                 (long long)R->par_stride);
     MOC_REQUIRE(R->image_stride >= (int64_t)moc_w1_image_bytes(B->D, B->dtype), "%s: image_stride=%lld < moc_w1_image_bytes=%lld",
                 who, (long long)R->image_stride, (long long)moc_w1_image_bytes(B->D, B->dtype));

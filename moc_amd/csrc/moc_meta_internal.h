@@ -1,8 +1,11 @@
-// What the two halves of phase B share: moc_meta_forward.hip (the meta forward) and moc_meta.hip (the step).  Private to
-// those two sources; nothing here is exported from the library.
+// What the sources of phase B share: moc_meta_forward.hip (the meta forward), moc_meta.hip (the training entries and which
+// step kernel they run) and the step kernels' sources moc_step_{pool,fused,tiles}.hip.  Private to those sources; nothing
+// here is exported from the library.
 #pragma once
 #include <mutex>   // std::call_once: both halves raise their kernels' LDS limits once, from any thread
 #include "moc_common.h"
+
+struct P2pArgs;   // the in-kernel gradient exchange's kernel argument (moc_p2p_proto.h)
 
 namespace moc_meta_internal __attribute__((visibility("hidden"))) {
 
@@ -21,6 +24,9 @@ constexpr int H = MOC_HIDDEN;
 // forward still writes.  Same rows, same (value desc, row asc) order, same sum: same bits.
 constexpr int TILE_R = 4;
 constexpr int MOC_MAX_RUNS = 16;        // meta-learners one launch can serve (moc_train_steps_runs)
+constexpr int MOC_HP_RUNS = 8;          // ... with Adam coefficients per run (moc_train_steps_runs_hp; TileStepArgsRunsHp, moc_step_tiles.hip)
+// floats of one meta-learner: W1 [H][D], b1 [H], W2 [4][H], b2 [4]
+constexpr int64_t n_params(int D) { return (int64_t)MOC_HIDDEN * D + MOC_HIDDEN + 4 * MOC_HIDDEN + 4; }
 constexpr int MOC_TILE_PATH_RECORDS = 1000001, MOC_TILE_PATH_FULL = 1000002;   // left in ws->n_pair[0] by the tile-record step
 struct TileWs {
     float4* lam;                 // [slots] gates of the record's row
@@ -165,6 +171,60 @@ struct StepPlan {
 };
 // exchange: a P2pArgs will be passed to the step (never the tile-record kind); train = 0: pooling + loss only
 StepPlan step_plan(const moc_batch_t* B, const moc_meta_ws_t* ws, bool exchange, int train = 1);
+
+int step_attrs();   // raises the step kernels' dynamic-LDS limits, once per process: every entry, before its first launch
+
+// ------------------------------------------------------------------ the step kernels' host side (moc_step_*.hip)
+// Scalars exactly as torch hands them to its fp32 kernels: computed in Python doubles,
+// rounded to fp32 once.
+struct AdamCoef {
+    float wd, one_minus_b1, beta2, one_minus_b2, eps;
+    float neg_step_size;   // -(lr / (1 - beta1^t))
+    float bc2_sqrt;        // sqrt(1 - beta2^t)
+    float grad_scale;
+};
+// device-resident Adam coefficients for graph replay: the step's coefficients are tab[ctr[0] + pos]
+struct StepTab { const AdamCoef* tab; const int32_t* ctr; int pos; };
+AdamCoef adam_coef(const moc_meta_t* M, int64_t step, float grad_scale);   // the coefficients of Adam step `step` (moc_meta.hip)
+// M advanced to run r: every tensor by r * par_stride, the W1 image by r * image_stride
+inline moc_meta_t meta_of_run(const moc_meta_t* M, const moc_runs_t* R, int r) {
+    moc_meta_t Mr = *M;
+    const int64_t po = (int64_t)r * R->par_stride;
+    Mr.W1 += po; Mr.b1 += po; Mr.W2 += po; Mr.b2 += po;
+    Mr.m_W1 += po; Mr.m_b1 += po; Mr.m_W2 += po; Mr.m_b2 += po;
+    Mr.v_W1 += po; Mr.v_b1 += po; Mr.v_W2 += po; Mr.v_b2 += po;
+    Mr.W1_image = (unsigned char*)M->W1_image + (int64_t)r * R->image_stride;
+    return Mr;
+}
+// Each source raises the dynamic-LDS limit of its own kernels (hipFuncSetAttribute must name the kernel); step_attrs calls
+// the three, in this order, and reports the first failure.
+typedef void (*raise_lds_fn)(const char* name, const void* kernel, int bytes);
+void pool_step_attrs(raise_lds_fn raise);
+void fused_step_attrs(raise_lds_fn raise);
+void tile_step_attrs(raise_lds_fn raise);
+// ---- moc_step_pool.hip: the three-launch step
+int launch_pool(const moc_batch_t* B, const moc_meta_ws_t* ws, int slide0, int n, hipStream_t s);   // topk_mean_kernel over the mixed scores
+// pooling + loss (+ pair gradients and the small-parameter step) for slides [slide0, slide0+n)
+int launch_pool_finish(const StepPlan& p, const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws_t* ws, const int64_t* labels,
+                       int slide0, int n, int train, int apply_adam, uint32_t use_bits, const AdamCoef& k, hipStream_t s);
+int launch_w1(const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws_t* ws, int apply_adam, const AdamCoef& k, hipStream_t s,
+              bool padded_pairs);
+// plain Adam over all four tensors from the gradients in M->g_* (+ the W1 image when `img` is given)
+int launch_adam_all(const moc_meta_t* M, const AdamCoef& k, unsigned char* img, int img_dt, hipStream_t s, const char* who);
+// ---- moc_step_fused.hip: the narrow and the wide one-launch step (x: the gradient exchange, or null)
+int launch_fused_kernel(const StepPlan& p, const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws_t* ws, const int64_t* labels,
+                        int slide, uint32_t use_bits, const AdamCoef& k, float* W2out, hipStream_t s, int apply_adam,
+                        const P2pArgs* x, const StepTab* tab);
+// ---- moc_step_tiles.hip: the one-launch step over the forward's tile records.  One meta-learner ...
+int launch_tile_step(const StepPlan& p, const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws_t* ws, const int64_t* labels,
+                     int slide, uint32_t use_bits, const AdamCoef& k, float* W2out, hipStream_t s, int apply_adam,
+                     const StepTab* tab, int next_slide);
+// ... or runs [r0, r0 + nr) of R in one launch (nr <= MOC_MAX_RUNS; per-run coefficients: nr <= MOC_HP_RUNS), each on its
+// slide `slide` + run * slide_stride.  cur / nxt: the W2 buffers of run 0 this step reads / writes, a run's 4 H floats
+// cur_stride / nxt_stride apart.  k: ONE AdamCoef for all runs, or (k_per_run) run r0 + r's at k[r].
+int launch_tile_runs(const StepPlan& p, const moc_batch_t* B, const moc_meta_t* M, const moc_runs_t* R, const moc_meta_ws_t* ws,
+                     const int64_t* labels, int slide, bool more_steps, uint32_t use_bits, int r0, int nr, const AdamCoef* k,
+                     bool k_per_run, float* cur, int64_t cur_stride, float* nxt, int64_t nxt_stride, hipStream_t s);
 
 // ------------------------------------------------------------------ the forward's host side, as the step calls it
 // (moc_meta_forward.hip)

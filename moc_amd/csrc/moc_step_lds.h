@@ -1,5 +1,5 @@
-// The step kernels' dynamic LDS (moc_meta.hip): ONE layout per kernel, byte offsets from the start of dynamic LDS plus
-// `bytes`, the total to launch with.  The host sizes the launch with the same function the kernel carves with, so a
+// The step kernels' dynamic LDS (the kernels of moc_step_pool.hip, moc_step_fused.hip and moc_step_tiles.hip; step_plan
+// in moc_meta.hip): ONE layout per kernel, byte offsets from the start of dynamic LDS plus `bytes`, the total to launch with.  The host sizes the launch with the same function the kernel carves with, so a
 // carve cannot move without the launch moving with it.  Plain C++17, no HIP name: tests/native/step_lds_host.cpp
 // includes it with g++ and checks order, extents, alignment and the totals over a grid of shapes.
 //
@@ -18,7 +18,7 @@
 
 namespace moc_step_lds {
 
-constexpr int H = 64;                             // hidden units (MOC_HIDDEN: asserted where moc_meta.hip includes this)
+constexpr int H = 64;                             // hidden units (MOC_HIDDEN: asserted in moc_step_shared.h, which includes this)
 constexpr int FIN_CHUNK = 256;                    // finish_kernel: pairs whose H1 rows are staged in LDS at a time (64 KiB)
 constexpr int PS_CAP_MAX = 1024;                  // candidate list entries per class (the launch picks cap <= this)
 constexpr int TILE_CL = 64;                       // tile-record step: candidates per class

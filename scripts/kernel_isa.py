@@ -2,7 +2,8 @@
 """Per-kernel fingerprint of the gfx950 device code of a built tree.  Host only, no GPU.
 
     kernel_isa.py TREE            one line per kernel: object, symbol, sha1 of its disassembly, instruction count
-    kernel_isa.py BEFORE AFTER    the kernels that differ, are missing or are new; exit 1 if there are any
+    kernel_isa.py BEFORE AFTER    the kernels that differ, are missing or are new; exit 1 if there are any.  A missing
+                                  kernel whose code reappears under a new symbol is reported as renamed, and is identical
 
 TREE is the repository root (or its moc_amd/csrc) after `make`.  Every .hip object there is unbundled
 (clang-offload-bundler), disassembled (llvm-objdump -d) and cut at the kernel symbols; addresses, encodings and
@@ -92,7 +93,18 @@ def main(argv):
         print("%d kernels" % sum(len(v) for v in a.values()))
         return 0
     b = tree_kernels(argv[2])
-    bad = moved = 0
+    na, nb = sum(map(len, a.values())), sum(map(len, b.values()))
+    bad = moved = renamed = 0
+    # a symbol that is gone and a new one with the same code (hash and instruction count): the kernel was renamed, e.g.
+    # because a type in its signature changed namespace.  Paired in symbol order, each new symbol at most once.
+    fresh = sorted(s for s in set(b) - set(a) if len(b[s]) == 1)
+    for old in sorted(s for s in set(a) - set(b) if len(a[s]) == 1):
+        new = next((s for s in fresh if b[s][0][1:] == a[old][0][1:]), None)
+        if new is not None:
+            fresh.remove(new)
+            renamed += 1
+            print("renamed  %s -> %s  (%s -> %s)" % (old, new, a[old][0][0], b[new][0][0]))
+            del a[old], b[new]
     for sym in sorted(set(a) | set(b)):
         va, vb = a.get(sym, []), b.get(sym, [])
         if len(va) != 1 or len(vb) != 1:
@@ -106,8 +118,8 @@ def main(argv):
             continue
         bad += 1
         print("%-8s %s  %s" % (what, ",".join(o for o, _, _ in va + vb), sym))
-    print("kernel_isa: %d kernels before, %d after: %d identical (%d of them moved), %d differ / missing / new"
-          % (sum(map(len, a.values())), sum(map(len, b.values())), len(set(a) | set(b)) - bad, moved, bad))
+    print("kernel_isa: %d kernels before, %d after: %d identical (%d of them moved, %d renamed), %d differ / missing / new"
+          % (na, nb, len(set(a) | set(b)) - bad + renamed, moved, renamed, bad))
     return 1 if bad else 0
 
 

@@ -1,4 +1,4 @@
-"""Which step kernel a shape gets is decided in one place (StepPlan, moc_meta.hip).  moc_train_runs_mode and
+"""Which step kernel a shape gets is decided in one place (StepPlan: step_plan in moc_amd/csrc/moc_meta.hip).  moc_train_runs_mode and
 moc_p2p_step_supported are pure host functions over that decision: their answers over a grid of shapes were recorded
 before the decision was gathered into the plan (tests/golden/step_dispatch.json) and must not move."""
 import ctypes as C
