@@ -1,6 +1,8 @@
 """Shared helpers for the parity tests (test-side only)."""
 from __future__ import annotations
 
+import itertools
+import math
 import os
 import types
 
@@ -148,18 +150,173 @@ def bank_and_bag(seed, N, C, label, D=512):
     return W, We, synth.make_bag(seed + 500, N, D, We, C, label=label)
 
 
-def assert_adam_params_close(got, exp, v_exp, step, grad_noise, lr=1e-3, base=2e-6, what=""):
+def assert_adam_params_close(got, exp, v_exp, step, grad_noise, lr=1e-3, base=2e-6, what="", beta2=0.999):
     """Parameters after `step` Adam steps.  Adam's update is lr*m_hat/(sqrt(v_hat)+eps):
     for an element whose gradient is comparable to the gradient noise between two
     correct fp32 implementations (`grad_noise`, absolute), the update is sign-like and
     may differ by up to lr per step; elsewhere the difference scales with
     grad_noise/|g|.  Bound each element accordingly."""
     got, exp, v_exp = (np.asarray(a, dtype=np.float64) for a in (got, exp, v_exp))
-    v_hat = v_exp / (1.0 - 0.999 ** step)
+    v_hat = v_exp / (1.0 - beta2 ** step)
     allowed = base + lr * step * np.minimum(1.0, 4.0 * grad_noise / (np.sqrt(v_hat) + 1e-8))
     bad = np.abs(got - exp) > allowed
     assert not bad.any(), (f"{what}: {int(bad.sum())} params outside the Adam noise bound; worst "
                            f"{np.abs(got - exp)[bad].max():.3e} (allowed {allowed[bad].min():.3e})")
+
+
+# ---- Adam's update at the precision moc_step_shared.h states it: test_adam_restatement_cpu.py, test_gpu_adam.py
+# adam_update() is torch's single-tensor Adam with coupled L2, operation by operation, each operation rounded to fp32 on
+# its own, with coefficients formed in double and cast once (adam_coef() in moc_meta.hip).  adam_coef32 / adam_ops32 restate
+# exactly that in numpy float32 -- the BIT reference of the GPU tests (torch's CPU Adam is not: its vectorised kernels fuse);
+# adam_f64 is the textbook update in float64, and adam_err_units measures a result against it in units that do not depend
+# on the magnitudes.
+ADAM_HP = ((1e-3, 0.9, 0.999, 1e-8, 1e-4), (3e-3, 0.9, 0.999, 1e-8, 0.0), (3e-4, 0.8, 0.99, 1e-6, 1e-2))   # lr, b1, b2, eps, wd
+ADAM_STEPS = (1, 2, 7, 1000, 100000)
+ADAM_GRAD_SCALES = (1.0, 1.0 / 8, 1.0 / 3)
+ADAM_VARIANTS = ("no_wd", "no_bc1", "no_bc2", "eps_in_root", "decoupled_wd")
+# The largest error of adam_ops32 against adam_f64 over adam_inputs(D, t) for D in (256, 1024), every ADAM_HP, ADAM_STEPS
+# and ADAM_GRAD_SCALES, in adam_err_units' units (exp_avg, exp_avg_sq, parameter), as printed by
+#   python -m pytest tests/test_adam_restatement_cpu.py -k measured -s
+# The GPU tests' bound is twice that, rounded up to whole units: the factor covers a division or a square root that is
+# faithfully rather than correctly rounded on the device.  Taken from this float64 comparison, never from a GPU run.
+ADAM_MEASURED = (1.12, 5.13, 0.98)
+ADAM_BOUND = tuple(int(np.ceil(2.0 * e)) for e in ADAM_MEASURED)
+
+
+def adam_coef32(lr, beta1, beta2, eps, wd, step, grad_scale=1.0):
+    """adam_coef(): the arithmetic in double (Python floats), one cast to fp32 each.
+    -> (wd, one_minus_b1, beta2, one_minus_b2, eps, neg_step_size, bc2_sqrt, grad_scale)"""
+    bc1 = 1.0 - beta1 ** step
+    bc2 = 1.0 - beta2 ** step
+    return tuple(np.float32(x) for x in (wd, 1.0 - beta1, beta2, 1.0 - beta2, eps, -(lr / bc1), math.sqrt(bc2), grad_scale))
+
+
+def adam_ops32(p, m, v, g, coef):
+    """adam_update() on float32 arrays, every operation its own numpy operation on float32 operands (so nothing is kept
+    wider than fp32 in between); `g * grad_scale` first, as every kernel that inlines it does.  -> (p', m', v')"""
+    wd, one_minus_b1, beta2, one_minus_b2, eps, neg_step_size, bc2_sqrt, grad_scale = coef
+    p, m, v, g = (np.asarray(a, dtype=np.float32) for a in (p, m, v, g))
+    g = g * grad_scale
+    g = g + wd * p
+    m = m + one_minus_b1 * (g - m)
+    v = v * beta2 + (one_minus_b2 * g) * g
+    denom = np.sqrt(v) / bc2_sqrt + eps
+    p = p + (neg_step_size * m) / denom
+    assert p.dtype == m.dtype == v.dtype == np.float32
+    return p, m, v
+
+
+def adam_f64(p, m, v, g, lr, beta1, beta2, eps, wd, step, grad_scale=1.0, variant=None):
+    """The textbook Adam step with coupled L2 in float64 (hyper-parameters as the Python floats they are; grad_scale as the
+    fp32 value the C entry is handed).  `variant`: one of ADAM_VARIANTS, a WRONG update -- only to show what the bounds
+    reject.  -> namespace p, m, v (the stepped values), g_abs (|g * grad_scale|), wd"""
+    assert variant is None or variant in ADAM_VARIANTS
+    p, m, v, g = (np.asarray(a, dtype=np.float64) for a in (p, m, v, g))
+    g = g * float(np.float32(grad_scale))
+    g_abs = np.abs(g)
+    if variant == "decoupled_wd":
+        p = p * (1.0 - lr * wd)
+    elif variant != "no_wd":
+        g = g + wd * p
+    m = beta1 * m + (1.0 - beta1) * g
+    v = beta2 * v + (1.0 - beta2) * g * g
+    m_hat = m if variant == "no_bc1" else m / (1.0 - beta1 ** step)
+    v_hat = v if variant == "no_bc2" else v / (1.0 - beta2 ** step)
+    denom = np.sqrt(v_hat + eps) if variant == "eps_in_root" else np.sqrt(v_hat) + eps
+    return types.SimpleNamespace(p=p - lr * m_hat / denom, m=m, v=v, g_abs=g_abs, wd=wd)
+
+
+def _ulp32(x):
+    return np.spacing(np.abs(np.asarray(x, dtype=np.float64)).astype(np.float32)).astype(np.float64)
+
+
+def adam_err_elements(got_p, got_m, got_v, p, m, v, g, ref64):
+    """The error of every element of (got_p, got_m, got_v) against adam_f64's `ref64` from the state (p, m, v), in units of
+      exp_avg ....... ulp of max(|m|, |g| + wd |p|)   (g: the scaled gradient)
+      exp_avg_sq .... ulp of the float64 v'
+      parameter ..... ulp(p) + 8 ulp(|p' - p|)
+    -> (err_m, err_v, err_p), arrays.  (The ulp of zero is the smallest denormal: no unit is zero.)"""
+    p64, m64 = np.asarray(p, dtype=np.float64), np.asarray(m, dtype=np.float64)
+    unit_m = _ulp32(np.maximum(np.abs(m64), ref64.g_abs + ref64.wd * np.abs(p64)))
+    unit_v = _ulp32(ref64.v)
+    unit_p = _ulp32(p64) + 8.0 * _ulp32(ref64.p - p64)
+    err = lambda got, ref, unit: np.abs(np.asarray(got, dtype=np.float64) - ref) / unit
+    return err(got_m, ref64.m, unit_m), err(got_v, ref64.v, unit_v), err(got_p, ref64.p, unit_p)
+
+
+def adam_err_units(got_p, got_m, got_v, p, m, v, g, ref64):
+    """The largest of adam_err_elements per tensor -> (err_m, err_v, err_p), floats"""
+    return tuple(float(e.max()) for e in adam_err_elements(got_p, got_m, got_v, p, m, v, g, ref64))
+
+
+def adam_numel(D):
+    return 64 * D + 64 + 4 * 64 + 4          # W1 [64, D], b1, W2 [4, 64], b2, flat in that order
+
+
+ADAM_ZERO_BLOCK, ADAM_V0_BLOCK = slice(100, 164), slice(200, 264)
+
+
+def adam_zero_blocks(D):
+    """the blocks with g = m = v = 0: one in W1, one in W2, the last two elements of b2"""
+    n = adam_numel(D)
+    return (ADAM_ZERO_BLOCK, slice(64 * D + 64 + 8, 64 * D + 64 + 24), slice(n - 2, n))
+
+
+_adam_inputs = {}
+
+
+def _adam_cancels(a, b):
+    """a + b, of opposite signs and within a factor of four of one another in magnitude"""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = np.abs(a) / np.abs(b)
+    return (a * b < 0) & (r > 0.25) & (r < 4.0)
+
+
+def adam_inputs(D, t):
+    """Crafted (p, m, v, g), flat over a senet(D, 4)'s four tensors, for Adam step `t`: magnitudes spread over nine decades
+    (v: eighteen) with both signs, every seventh gradient exactly zero, blocks with g = m = v = 0 (there p moves by the
+    weight-decay term alone), a block with v = 0 and g != 0; at t = 1 the moments are zero.
+    Every intermediate of the update is then zero or a normal fp32 value -- the smallest non-zero square is
+    (1 - beta2) (wd p)^2 >= 1e-3 * (1e-4 * 1e-9)^2 = 1e-29, far above 1e-37, unless g * grad_scale and wd * p cancel to
+    their last bits, which test_adam_restatement_cpu.py checks they do not: denormal handling is not what these inputs
+    are for.  Computed once per (D, t); read-only."""
+    if (D, t) not in _adam_inputs:
+        n = adam_numel(D)
+        rng = np.random.default_rng([2024, D, t])
+
+        def spread(lo, signed=True):
+            x = 10.0 ** rng.uniform(lo, 0.0, n)
+            return (x * rng.choice([-1.0, 1.0], n) if signed else x).astype(np.float32)
+        p, m, v, g = spread(-9), spread(-9), spread(-18, signed=False), spread(-9)
+        # No sum of the update cancels by more than (1 + 4) / (4 - 1) = 5/3 under any tested hyper-parameters: a sum that
+        # cancels a thousandfold carries its operands' rounding a thousandfold into what follows (g * g, the update), and
+        # the error in ulps of exp_avg_sq or of the update would then measure the input, not the arithmetic.
+        #   g * grad_scale + wd * p: where the two oppose within a factor of four of one another, g takes p's sign
+        #   beta1 * m + (1 - beta1) * g: where they do, m takes the other sign, or (if that opposes under other
+        #   hyper-parameters) sixteen times the magnitude
+        p64, wds = p.astype(np.float64), sorted({hp[4] for hp in ADAM_HP})
+        for wd, gs in itertools.product(wds[1:], ADAM_GRAD_SCALES):
+            g = np.where(_adam_cancels(g * np.float64(gs), wd * p64), -g, g)
+        g[::7] = 0.0
+        g[ADAM_V0_BLOCK] = np.where(g[ADAM_V0_BLOCK] == 0.0, np.copysign(np.float32(1e-3), p[ADAM_V0_BLOCK]), g[ADAM_V0_BLOCK])
+        for blk in adam_zero_blocks(D):
+            g[blk] = 0.0
+        for _ in range(8):
+            terms = [((1.0 - hp[1]) * (g * np.float64(gs) + wd * p64), hp[1])
+                     for hp, wd, gs in itertools.product(ADAM_HP, wds, ADAM_GRAD_SCALES)]
+            bad = lambda mm: np.any([_adam_cancels(a, b1 * mm) for a, b1 in terms], axis=0)
+            bad_now, bad_flipped = bad(m.astype(np.float64)), bad(-m.astype(np.float64))
+            m = np.where(bad_now & ~bad_flipped, -m, np.where(bad_now & bad_flipped, m * np.float32(16.0), m))
+        v[ADAM_V0_BLOCK] = 0.0
+        for blk in adam_zero_blocks(D):
+            m[blk] = v[blk] = 0.0
+        if t == 1:
+            m[:] = 0.0
+            v[:] = 0.0
+        for a in (p, m, v, g):
+            a.setflags(write=False)
+        _adam_inputs[(D, t)] = (p, m, v, g)
+    return _adam_inputs[(D, t)]
 
 
 # ---- the gradient-only step (moc_train_grad) against autograd on the oracle: test_gpu_parity.py, test_gpu_step_lds.py
@@ -189,10 +346,11 @@ def grad_step_task(C, K, D, dtype):
     return _grad_step_tasks[key]
 
 
-def grad_step_batch(dev, C, K, D, dtype, masked=False):
+def grad_step_batch(dev, C, K, D, dtype, masked=False, adam=None):
     """The task's slides as a batch after phase A, its labels on the device and a meta-learner initialised as the oracle's.
     masked: the batch carries a mask of ones -- the same rows, but a batch that trains, for which the engine allocates the
-    forward's tile records (engine.TILE_RECORDS)."""
+    forward's tile records (engine.TILE_RECORDS).  adam: keywords of a torch.optim.Adam over the model, which the
+    meta-learner then steps (default: none, gradients only)."""
     from moc_amd import engine as E, main_moc as M
     W, We, bags, labels, _ = grad_step_task(C, K, D, dtype)
     torch.manual_seed(9)
@@ -203,7 +361,8 @@ def grad_step_batch(dev, C, K, D, dtype, masked=False):
     batch = E.SlideBatch(X, sz, C, C + 4, GRAD_STEP_TOPJ, K, [], mask=mask)
     batch.phase_a(E.Bank.get(M.zeroshot_weights, M.zeroshot_weights_ext, dtype, dev))
     lab = torch.tensor(labels, dtype=torch.int64, device=dev)
-    return batch, lab, E.MetaState(model, None, need_grads=True)
+    opt = torch.optim.Adam(model.parameters(), **adam) if adam is not None else None
+    return batch, lab, E.MetaState(model, opt, need_grads=True)
 
 
 def grad_step_grads(batch, lab, meta):

@@ -18,7 +18,9 @@ def _state(model, opt):
             [opt.state[p]["exp_avg_sq"].detach().cpu().clone() for p in ps] + [torch.tensor([float(opt.state[p]["step"]) for p in ps])])
 
 
-def _run(dev, graph, C, sizes, dtype, lengths, j=100, K=10, table_steps=None, poke=None, seed=5):
+def _run(dev, graph, C, sizes, dtype, lengths, j=100, K=10, table_steps=None, poke=None, seed=5, adam=None, start_step=0):
+    """adam: keywords of the optimizer (default: lr 1e-3, weight decay 1e-4); start_step: the Adam steps it has already
+    taken, with zero moments"""
     from moc_amd import engine as E, main_moc as M
     keep = (E.STEP_GRAPH, E.GRAPH_TABLE_STEPS)
     E.STEP_GRAPH = graph
@@ -31,7 +33,10 @@ def _run(dev, graph, C, sizes, dtype, lengths, j=100, K=10, table_steps=None, po
         res = M.ResidentBags(bags, labels, dev, dtype=dtype)
         torch.manual_seed(seed)
         model = M.senet(512, 4).to(dev)
-        opt = torch.optim.Adam(model.parameters(), lr=1e-3, weight_decay=1e-4)
+        opt = torch.optim.Adam(model.parameters(), **(adam or dict(lr=1e-3, weight_decay=1e-4)))
+        if start_step:
+            for p in model.parameters():        # the state torch.optim.Adam initialises lazily, at another step count
+                opt.state[p] = dict(step=torch.tensor(float(start_step)), exp_avg=torch.zeros_like(p), exp_avg_sq=torch.zeros_like(p))
         args = H.make_args(C, j, K)
         torch.manual_seed(seed + 1)
         losses = []
@@ -57,17 +62,26 @@ def _same(a, b):
         assert torch.equal(x, y)
 
 
-@pytest.mark.parametrize("C,dtype,sizes", [(2, torch.float32, [900, 1300, 700, 1100, 1000]),
-                                           (2, torch.bfloat16, [900, 1300, 700, 1100]),
-                                           (3, torch.float16, [800, 1200, 600]),
-                                           (30, torch.bfloat16, [1200, 900, 1100]),      # wide step, pooling inside
-                                           (30, torch.bfloat16, [4000, 3600])])          # wide step behind topk_mean_kernel
-def test_graph_pass_is_bit_identical_to_stream_launches(gpu_device, C, dtype, sizes):
+# an optimizer off torch's defaults in every field, 990 steps in: the 25 steps' table entries cross t = 1000, where
+# 1 - beta1^t has become 1 to fp32 and 1 - beta2^t has not
+OTHER_ADAM = dict(adam=dict(lr=3e-4, betas=(0.8, 0.99), eps=1e-6, weight_decay=1e-2), start_step=990)
+
+
+@pytest.mark.parametrize("C,dtype,sizes,opt_kw", [(2, torch.float32, [900, 1300, 700, 1100, 1000], {}),
+                                                  (2, torch.bfloat16, [900, 1300, 700, 1100], {}),
+                                                  (3, torch.float16, [800, 1200, 600], {}),
+                                                  (30, torch.bfloat16, [1200, 900, 1100], {}),      # wide step, pooling inside
+                                                  (30, torch.bfloat16, [4000, 3600], {}),           # wide step behind topk_mean_kernel
+                                                  (2, torch.float32, [900, 1300, 700, 1100, 1000], OTHER_ADAM)],
+                         ids=["2-dtype0-sizes0", "2-dtype1-sizes1", "3-dtype2-sizes2", "30-dtype3-sizes3", "30-dtype4-sizes4",
+                              "2-f32-other-adam-from-990"])      # (the first five: the names these cases have always had)
+def test_graph_pass_is_bit_identical_to_stream_launches(gpu_device, C, dtype, sizes, opt_kw):
     n = len(sizes)
     lengths = [n, n, n - 1, n, 1, n]            # whole passes, partial passes (odd and even lengths), a one-step pass
-    g = _run(gpu_device, True, C, sizes, dtype, lengths)
-    e = _run(gpu_device, False, C, sizes, dtype, lengths)
+    g = _run(gpu_device, True, C, sizes, dtype, lengths, **opt_kw)
+    e = _run(gpu_device, False, C, sizes, dtype, lengths, **opt_kw)
     _same(g, e)
+    assert g[0][-1].tolist() == [opt_kw.get("start_step", 0) + sum(lengths)] * 4
     captures, replays, eager = g[2]
     assert replays == len(lengths) and eager == 0, g[2]
     assert captures <= 2 * 3, g[2]               # one graph per (pass length, work-array set): three lengths, two sets

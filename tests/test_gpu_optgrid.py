@@ -41,10 +41,18 @@ def _bags(C_, dtype, D=512):
 _alone_cache = {}
 
 
-def _alone(dev, lr, wd, C_=2, dtype=torch.float32, j=100, K=5):
-    """main_moc.train for EPOCHS passes with Adam(lr, weight_decay) -> what a cell of the grid must reproduce (computed
-    once per cell and shared by the tests; never modified)."""
-    key = (lr, wd, C_, dtype, j, K)
+def _adam(params, hp):
+    """hp: (lr, weight_decay), or the full (lr, (beta1, beta2), eps, weight_decay)"""
+    if len(hp) == 2:
+        return torch.optim.Adam(params, lr=hp[0], weight_decay=hp[1])
+    lr, betas, eps, wd = hp
+    return torch.optim.Adam(params, lr=lr, betas=betas, eps=eps, weight_decay=wd)
+
+
+def _alone(dev, lr, wd, C_=2, dtype=torch.float32, j=100, K=5, betas=None, eps=None):
+    """main_moc.train for EPOCHS passes with Adam(lr, weight_decay) -- and, where given, betas and eps -> what a cell of the
+    grid must reproduce (computed once per cell and shared by the tests; never modified)."""
+    key = (lr, wd, C_, dtype, j, K, betas, eps)
     if key not in _alone_cache:
         from moc_amd import main_moc as M
         W, We = _bank(C_)
@@ -52,7 +60,7 @@ def _alone(dev, lr, wd, C_=2, dtype=torch.float32, j=100, K=5):
         bags, labels = _bags(C_, dtype)
         torch.manual_seed(MODEL_SEED)
         model = M.senet(512, 4).to(dev)
-        opt = torch.optim.Adam(model.parameters(), lr=lr, weight_decay=wd)
+        opt = _adam(model.parameters(), (lr, wd) if betas is None else (lr, betas, eps, wd))
         res = M.ResidentBags(bags, labels, dev)
         args = H.make_args(C_, j, K)
         torch.manual_seed(GEN_SEED)
@@ -74,11 +82,11 @@ def _grid(dev, hps, C_=2, dtype=torch.float32, j=100, K=5, per_run_adam=True, ep
     bags, labels = _bags(C_, dtype)
     split = M.ResidentBags(bags, labels, dev)
     models, opts, gens = [], [], []
-    for lr, wd in hps:
+    for hp in hps:
         torch.manual_seed(MODEL_SEED)
         model = M.senet(512, 4).to(dev)
         models.append(model)
-        opts.append(torch.optim.Adam(model.parameters(), lr=lr, weight_decay=wd))
+        opts.append(_adam(model.parameters(), hp))
         g = torch.Generator()
         g.manual_seed(GEN_SEED)
         gens.append(g)
@@ -119,6 +127,25 @@ def test_every_cell_of_a_lockstep_chain_is_its_run_alone(dev, monkeypatch):
     for r, s in ((0, 1), (0, 2), (1, 2)):                                                  # ... and cells that differ, differ
         assert not np.array_equal(_bits(got, r)[0], _bits(got, s)[0]), (r, s)
         assert not np.array_equal(_bits(got, r)[2], _bits(got, s)[2]), (r, s)
+
+
+FULL = [(1e-3, (0.9, 0.999), 1e-8, 1e-4), (3e-4, (0.8, 0.99), 1e-6, 1e-2), (3e-3, (0.95, 0.9999), 1e-7, 0.0)]
+
+
+def test_runs_with_their_own_betas_and_eps_are_their_runs_alone(dev, monkeypatch):
+    """Three runs in one lockstep chain whose records differ in every field -- betas and eps too, which no other GPU test
+    moves off torch's defaults: run r > 0 must read ITS beta1 / beta2 / eps (test_gpu_adam.py anchors the run alone to the
+    update's arithmetic)."""
+    monkeypatch.delenv("MOC_RUNS_GROUPS", raising=False)
+    monkeypatch.delenv("MOC_RUNS_SHARE", raising=False)
+    got = _grid(dev, FULL)
+    rs = got["rs"]
+    assert rs.mode == 1 and rs.per_run_adam and len(rs.groups) == 1 and rs.groups[0]["runs"].n_runs == 3
+    for r, (lr, betas, eps, wd) in enumerate(FULL):
+        _assert_run(got, r, _alone(dev, lr, wd, betas=betas, eps=eps), f"run {r} lr {lr} betas {betas} eps {eps} wd {wd}")
+    for r, s in ((0, 1), (0, 2), (1, 2)):
+        for a, b in zip(_bits(got, r), _bits(got, s)):
+            assert not np.array_equal(a, b), (r, s)
 
 
 @pytest.mark.parametrize("groups_env,n_groups", [(None, 2), ("1", 1)])
