@@ -577,6 +577,19 @@ int moc_nystrom_token_values(const float* qkv, int64_t n_pad, int heads, int dim
                              const float* k_l, const float* Y, const float* conv_w /* [h, taps] or NULL */, int taps,
                              float scale, float* out /* [n_pad, h*d] */, moc_stream_t stream);
 
+/* The same layer's landmark pseudo-inverse (moc_amd/nystrom.py: moore_penrose_iter_pinv) as a chain of fp32 products on
+ * the whole chip, for heads = 8 and landmarks = 256 only.  A = attn2 [8, 256, 256] device fp32, never written:
+ *   c = max over all heads and rows of sum_j |A[h, i, j]|, r = likewise of the column sums;  Z0 = A^T / (c r)
+ *   iters times:  XZ = A Z;  Z <- 0.25 Z (13 I - XZ (15 I - XZ (7 I - XZ)))
+ * Z [8, 256, 256] receives the result (Z0 for iters = 0) and is written by the last product only.  Two init launches and
+ * four products per iteration in stream order; no atomics, no grid-wide barrier: the same bits on every call.  The
+ * intermediates live in `ws` (moc_nystrom_pinv_workspace bytes: five matrices and the partial maxima).  MOC_EUNSUPPORTED
+ * for another shape; MOC_EINVAL for null or not 16-byte aligned pointers, A and Z (or ws) overlapping, a short workspace,
+ * iters outside 0..64 -- all before the first launch.  Additive to ABI 20: the version number is unchanged. */
+size_t moc_nystrom_pinv_workspace(int heads, int landmarks);          /* 0: unsupported shape */
+int moc_nystrom_pinv(const float* A /* [h, m, m] */, int heads, int landmarks, int iters,
+                     float* Z /* [h, m, m] */, void* ws, size_t ws_bytes, moc_stream_t stream);
+
 /* a10-a15 fused: `n` consecutive meta-steps (one slide each, slides slide0..slide0+n-1 in
  * order, one Adam step per slide: main_moc.py:380-410), parameters and Adam moments
  * updated in place.  Per-slide loss/pooled land in ws->loss / ws->pooled. */

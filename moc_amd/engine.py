@@ -1364,3 +1364,21 @@ def nystrom_token_values(qkv: torch.Tensor, k_l: torch.Tensor, Y: torch.Tensor, 
                                          ptr(Y), ptr(conv_w), taps, C.c_float(float(scale)), ptr(out), _stream()),
           "moc_nystrom_token_values")
     return out
+
+
+def nystrom_pinv(attn2: torch.Tensor, iters: int) -> torch.Tensor:
+    """The landmark pseudo-inverse of the fused Nystrom forward (moc_nystrom_pinv): nystrom.moore_penrose_iter_pinv of
+    attn2 [8, 256, 256] -- Z0 = attn2^T / (max row sum x max column sum of |attn2| over all heads), then `iters` times
+    Z <- 1/4 Z (13 I - XZ (15 I - XZ (7 I - XZ))) -- as 2 + 4 iters launches of fp32 MFMA products.  No gradient."""
+    what = "nystrom_pinv"
+    assert attn2.is_cuda and attn2.dtype == torch.float32, f"{what}: fp32 tensors on the GPU (no CPU fallback)"
+    assert attn2.shape == (NYSTROM_HEADS, NYSTROM_LANDMARKS, NYSTROM_LANDMARKS), f"{what}: attn2 must be [8, 256, 256]"
+    iters = int(iters)
+    assert 0 <= iters <= 64, f"{what}: iters={iters} must be in 0..64"
+    attn2 = attn2.detach().contiguous()
+    Z = torch.empty_like(attn2)
+    nbytes = lib().moc_nystrom_pinv_workspace(NYSTROM_HEADS, NYSTROM_LANDMARKS)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=attn2.device)
+    check(lib().moc_nystrom_pinv(ptr(attn2), NYSTROM_HEADS, NYSTROM_LANDMARKS, iters, ptr(Z), ptr(ws), nbytes, _stream()),
+          "moc_nystrom_pinv")
+    return Z

@@ -158,6 +158,15 @@ class TransMIL(nn.Module):
     def fused(self, on: bool):
         self.layer1.attn.fused = self.layer2.attn.fused = bool(on)
 
+    @property
+    def fused_pinv(self) -> bool:
+        """Both layers' pseudo-inverse on moc_nystrom_pinv (nystrom.NystromAttention.fused_pinv); acts only where `fused` does."""
+        return bool(self.layer1.attn.fused_pinv and self.layer2.attn.fused_pinv)
+
+    @fused_pinv.setter
+    def fused_pinv(self, on: bool):
+        self.layer1.attn.fused_pinv = self.layer2.attn.fused_pinv = bool(on)
+
     def _tokens(self, data):
         """fc1, wrap-around padding to a square, class token, layer 1, PPEG, layer 2 (:236-266)."""
         if len(data.shape) == 2:

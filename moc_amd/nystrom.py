@@ -11,7 +11,9 @@ so that a TransMIL checkpoint trained with it loads.  Checked here against what 
 attention in the limit where every token is its own landmark, the pseudo-inverse against `torch.linalg.pinv`, shapes
 and padding (tests/test_baselines_cpu.py).  Plain torch operations: this is a signature shim (SURVEY.md section 8,
 f3); with `fused = True` the no-grad forward runs on the kernels of csrc/moc_nystrom.hip instead, which are checked
-against THIS restatement (tests/test_gpu_nystrom.py) and pin nothing more than it does."""
+against THIS restatement (tests/test_gpu_nystrom.py) and pin nothing more than it does; `fused_pinv = True` on top of it
+takes the pseudo-inverse from csrc/moc_nystrom_pinv.hip, checked against moore_penrose_iter_pinv below
+(tests/test_gpu_nystrom_pinv.py)."""
 from __future__ import annotations
 
 from math import ceil
@@ -50,6 +52,9 @@ class NystromAttention(nn.Module):
 
     # True: forward takes forward_fused (the HIP kernels of moc_nystrom.hip wherever they apply, this torch code elsewhere)
     fused = False
+    # True: forward_fused, where its kernels apply, takes the pseudo-inverse from engine.nystrom_pinv (moc_nystrom_pinv.hip)
+    # instead of moore_penrose_iter_pinv; no effect on any call that runs the torch code
+    fused_pinv = False
 
     def forward(self, x, mask=None, return_attn=False):
         if self.fused:
@@ -71,7 +76,7 @@ class NystromAttention(nn.Module):
 
     def forward_fused(self, x, mask=None, return_attn=False):
         """The no-grad forward on the HIP kernels: to_qkv, the landmark means, attn2 and its
-        pseudo-inverse in torch; W = softmax(q_l k^T) v (kernel A); Y = pinv W; softmax(q k_l^T) Y + res_conv(v) (kernel
+        pseudo-inverse in torch (the pseudo-inverse on moc_nystrom_pinv with `fused_pinv`); W = softmax(q_l k^T) v (kernel A); Y = pinv W; softmax(q k_l^T) Y + res_conv(v) (kernel
         B); to_out.  Neither [8, n, 256] score matrix is formed.  Wherever the kernels do not apply -- a gradient is
         wanted, x is not a contiguous fp32 [1, n, dim] CUDA tensor, another layer shape, mask / return_attn -- this is
         the torch code above, bit for bit."""
@@ -89,8 +94,11 @@ class NystromAttention(nn.Module):
         q_l = (means[:, :inner] * self.scale).reshape(m, h, -1).transpose(0, 1).contiguous()                        # h m d
         k_l = means[:, inner:].reshape(m, h, -1).transpose(0, 1).contiguous()
         attn2 = (q_l @ k_l.transpose(-1, -2)).softmax(dim=-1)
-        pinv = moore_penrose_iter_pinv(attn2.unsqueeze(0), self.pinv_iterations)[0]
-        W = engine.nystrom_landmark_values(qkv, q_l)      # softmax over the tokens of q_l k^T, times v
+        if self.fused_pinv:
+            pinv = engine.nystrom_pinv(attn2, self.pinv_iterations)
+        else:
+            pinv = moore_penrose_iter_pinv(attn2.unsqueeze(0), self.pinv_iterations)[0]
+        W =engine.nystrom_landmark_values(qkv, q_l)      # softmax over the tokens of q_l k^T, times v
         conv_w = self.res_conv.weight.reshape(h, -1) if self.residual else None
         out = engine.nystrom_token_values(qkv, k_l, pinv @ W, conv_w, self.scale)
         return self.to_out(out.unsqueeze(0))[:, -n:]

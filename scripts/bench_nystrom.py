@@ -1,13 +1,15 @@
 """Row f3: time TransMIL's fused Nystrom forward (NystromAttention.forward_fused: moc_nystrom_landmark_values +
 moc_nystrom_token_values around the torch pieces) against the torch path (`fused = False`, unchanged from before the
-kernels existed), all under no_grad: the whole model on one bag, one attention layer alone, and each kernel alone against
-its two bounds -- the bytes of qkv it must read (plus the output it writes) and its products at the fp32 matrix peak
-(v_mfma_f32_16x16x4_f32).
+kernels existed), and the same with the pseudo-inverse on moc_nystrom_pinv (`fused_pinv = True`) against `fused` alone,
+all under no_grad: the whole model on one bag, one attention layer alone, and each kernel alone against its two bounds --
+the bytes it must move and its products at the fp32 matrix peak (v_mfma_f32_16x16x4_f32); moc_nystrom_pinv also against
+moore_penrose_iter_pinv on the same attn2.
 
 Each figure is the median and the minimum of `--iters` single runs, each between two events, after `--warmup` untimed
-runs.  "faster" is claimed only where the fused median is below the torch path's minimum.
+runs.  "faster" is claimed only where a median is below the minimum of the path it is compared with.
 
     python scripts/bench_nystrom.py [--n 15000] [--iters 30] [--json out.json]
+    rocprofv3 --kernel-trace --stats ... -- python scripts/bench_nystrom.py --trace-layers 8
 """
 import argparse
 import json
@@ -21,6 +23,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from moc_amd import engine  # noqa: E402
 from moc_amd.model_mil import TransMIL  # noqa: E402
+from moc_amd.nystrom import moore_penrose_iter_pinv  # noqa: E402
 
 F32_MFMA_PEAK = 157.3e12      # v_mfma_f32_16x16x4_f32: 64 flop / clock / SIMD
 HBM_PEAK = 8.0e12
@@ -43,16 +46,21 @@ def times_us(fn, iters, warmup):
 
 
 def pair(label, fn, switch, iters, warmup):
-    """fn timed with the flag off, then on."""
+    """fn timed on the torch path, with `fused`, and with `fused` + `fused_pinv`; switch(fused, fused_pinv) sets the flags."""
     r = {}
-    for fused in (False, True):
-        switch(fused)
-        r["fused" if fused else "torch"] = times_us(fn, iters, warmup)
-    t, f = r["torch"], r["fused"]
+    for key, flags in (("torch", (False, False)), ("fused", (True, False)), ("fused_pinv", (True, True))):
+        switch(*flags)
+        r[key] = times_us(fn, iters, warmup)
+    switch(False, False)
+    t, f, p = r["torch"], r["fused"], r["fused_pinv"]
     r["fused_is_faster"] = f["median_us"] < t["min_us"]
+    r["fused_pinv_is_faster_than_fused"] = p["median_us"] < f["min_us"]
     print(f"{label:24s}: torch median {t['median_us']:9.1f} us (min {t['min_us']:9.1f})   fused median {f['median_us']:9.1f} us "
           f"(min {f['min_us']:9.1f})   {'fused faster' if r['fused_is_faster'] else 'NOT faster'} "
           f"(x{t['median_us'] / f['median_us']:.2f} on the medians)")
+    print(f"{'':24s}  fused + fused_pinv median {p['median_us']:9.1f} us (min {p['min_us']:9.1f})   "
+          f"{'faster than fused' if r['fused_pinv_is_faster_than_fused'] else 'NOT faster than fused'} "
+          f"(x{f['median_us'] / p['median_us']:.2f} on the medians)")
     return r
 
 
@@ -75,6 +83,8 @@ def main():
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--trace-layers", type=int, default=0,
+                    help="time nothing: run this many layers with fused + fused_pinv and exit (for a kernel trace of the layer)")
     a = ap.parse_args()
     assert a.iters >= 20
     dev = torch.device("cuda:0")
@@ -89,9 +99,17 @@ def main():
         n_tok = side * side + 1
         out["tokens"] = n_tok
         x = torch.nn.functional.layer_norm(torch.randn(1, n_tok, 512, generator=g), (512,)).to(dev)
-        out["model"] = pair(f"TransMIL {a.n} x 512", lambda: model(bag), lambda on: setattr(model, "fused", on), a.iters, a.warmup)
-        out["layer"] = pair(f"one layer, {n_tok} tokens", lambda: attn(x), lambda on: setattr(attn, "fused", on), a.iters, a.warmup)
-        model.fused = False
+        if a.trace_layers:
+            attn.fused = attn.fused_pinv = True
+            for _ in range(a.trace_layers):
+                attn(x)
+            torch.cuda.synchronize()
+            return
+
+        def flags(module):
+            return lambda on, pv: (setattr(module, "fused", on), setattr(module, "fused_pinv", pv))
+        out["model"] = pair(f"TransMIL {a.n} x 512", lambda: model(bag), flags(model), a.iters, a.warmup)
+        out["layer"] = pair(f"one layer, {n_tok} tokens", lambda: attn(x), flags(attn), a.iters, a.warmup)
 
         n_pad = -(-n_tok // M) * M
         out["n_pad"] = n_pad
@@ -106,6 +124,17 @@ def main():
                                         2 * n_pad * 512 * 4, 2 * scores, a.iters, a.warmup)
         out["token_values"] = kernel("moc_nystrom_token_values", lambda: engine.nystrom_token_values(qkv, k_l, Y, w, attn.scale),
                                      3 * n_pad * 512 * 4, 2 * scores + 2.0 * n_pad * 512 * 48, a.iters, a.warmup)
+        # the pseudo-inverse alone: 2 + 4 x 6 launches, each reading or writing two to three 2 MiB matrices (counted as 4 MiB
+        # a launch), 24 products of 8 x 256^3 multiply-adds; beside it the torch function on the same attn2
+        attn2 = (q_l @ k_l.transpose(-1, -2)).softmax(dim=-1).contiguous()
+        its = attn.pinv_iterations
+        out["pinv"] = kernel("moc_nystrom_pinv", lambda: engine.nystrom_pinv(attn2, its), (2 + 4 * its) * 4 * 2 ** 20,
+                             4 * its * 2.0 * H * M ** 3, a.iters, a.warmup)
+        out["pinv_torch"] = times_us(lambda: moore_penrose_iter_pinv(attn2.unsqueeze(0), its), a.iters, a.warmup)
+        k, t = out["pinv"], out["pinv_torch"]
+        out["pinv_is_faster"] = k["median_us"] < t["min_us"]
+        print(f"{'moore_penrose_iter_pinv':24s}: median {t['median_us']:8.1f} us (min {t['min_us']:8.1f})   moc_nystrom_pinv "
+              f"{'faster' if out['pinv_is_faster'] else 'NOT faster'} (x{t['median_us'] / k['median_us']:.2f} on the medians)")
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
         with open(a.json, "w") as f:
