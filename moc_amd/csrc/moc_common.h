@@ -46,6 +46,9 @@ void moc_set_error(const char* fmt, ...);
             MOC_FAIL(MOC_ELAUNCH, "%s: launch failed: %s", name, hipGetErrorString(e__)); \
     } while (0)
 
+// what every entry that takes a batch checks first (moc_scores.hip); `who` names the entry in the error text
+int moc_check_batch(const moc_batch_t* B, const char* who);
+
 static inline int moc_elem_size(int dtype) { return dtype == MOC_F32 ? 4 : 2; }
 static inline int moc_cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 

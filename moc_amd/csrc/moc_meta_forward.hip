@@ -15,8 +15,6 @@
 #include <cstdlib>
 #include "moc_meta_internal.h"
 
-int moc_check_batch(const moc_batch_t* B, const char* who);
-
 using namespace moc_meta_internal;
 
 namespace {

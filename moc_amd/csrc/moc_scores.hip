@@ -19,6 +19,7 @@
 #include "moc_common.h"
 #include "moc_scores_stream.h"
 #include <hip/hip_ext.h>
+#include <mutex>
 #include <type_traits>
 
 namespace {
@@ -616,11 +617,7 @@ __global__ __launch_bounds__(256, NT == 1 ? 2 : 1) void scores_stream_kernel(Sco
 // row is read once; the image slice is read once per 256 rows and each B fragment feeds 4 MFMAs.  All LDS
 // reads of the loop are hand-issued with counted waits (an ordinary LDS read makes hipcc wait vmcnt(0)
 // first -- the DMA in flight writes LDS too -- which would serialise DMA and MFMA).
-constexpr int WD_R = 4;               // row tiles per wave
-// k-steps (of 32 columns) per chunk: up to 6 n-tiles one k-step per chunk and TWO workgroups per CU (62 KiB of LDS
-// and at most 246 registers each: one's DMA waits and row epilogues run beside the other's MFMAs, +12 % at
-// 5 n-tiles); wider banks need the registers of a whole SIMD and take two k-steps per chunk
-constexpr int wd_kc(int NT) { return NT <= 6 ? 1 : 2; }
+// (WD_R, row tiles per wave, and wd_kc, k-steps per chunk: moc_scores_plan.h -- the host sizes the launch with them)
 
 template <int NT, bool F16>
 __global__ __launch_bounds__(256, (NT <= 6 ? 2 : 1)) void scores_wide_kernel(ScoresArgs a) {
@@ -928,12 +925,8 @@ __global__ __launch_bounds__(256) void stats_from_cache_kernel(const float* all,
 }  // namespace
 
 // ------------------------------------------------------------------ host entry points
-static int bank_nt(int Ce) { return (Ce + 15) / 16; }
-
 extern "C" size_t moc_bank_bytes(int D, int Ce, int dtype) {
-    if (D <= 0 || Ce <= 0) return 0;
-    const size_t per_nt = dtype != MOC_F32 ? (size_t)(D / 32) * 3 * 1024 : (size_t)(D / 16) * 1024;
-    return per_nt * bank_nt(Ce);
+    return D <= 0 || Ce <= 0 ? 0 : score_img_bytes(D, dtype) * bank_nt(Ce);
 }
 
 extern "C" int moc_prepare_bank(const float* W, const float* W_ext, int D, int C, int Ce, int dtype,
@@ -995,200 +988,128 @@ extern "C" int moc_mask_compact(const moc_batch_t* B, moc_stream_t stream) {
     return MOC_OK;
 }
 
+// ------------------------------------------------------------------ the score pass's launches
+// moc_scores_plan.h decides form, LDS, grid and chunk (score_plan); here score_launch raises an instantiation's
+// dynamic-LDS limit -- once per process, under call_once: worker threads call the entries side by side -- and launches
+// it, and plain ladders over the plan name the instantiations.
 // ev0 / ev1 (nullable): HIP events that take the score kernel's OWN start and end time stamps (hipExtLaunchKernel: the
 // dispatch's profiling stamps, not the moment a marker packet reaches the queue -- an event pair recorded around the
 // launch on a busy GPU measured 59 us for a kernel rocprofv3 times at 47).  A batch launched in chunks: first / last.
-// the ticketed form of the streaming kernel (up to three n-tiles; see scores_impl)
-template <int NF, bool BF, int NTT, bool FH>
-static void launch_stream_ticketed(const ScoresArgs& a, int wgs, size_t smem, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1,
-                                   int s0, int ns) {
-    if constexpr (NTT < 4) {
-        static bool attr_set = false;
-        if (!attr_set) {
-            (void)hipFuncSetAttribute((const void*)scores_stream_kernel<NF, BF, NTT, FH, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            attr_set = true;
-        }
-        hipExtLaunchKernelGGL((scores_stream_kernel<NF, BF, NTT, FH, true>), dim3(wgs), dim3(256), smem, s, ev0, ev1, 0, a, s0, ns);
+struct ScoreLaunch {
+    const ScoresArgs& a;
+    const ScorePlan& P;
+    hipStream_t s;
+    hipEvent_t ev0, ev1;
+    bool bf, f16;
+};
+template <auto KERNEL, typename... Tail>
+static void score_launch(const ScoreLaunch& l, Tail... tail) {
+    static std::once_flag attr;
+    std::call_once(attr, [] { (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SCORE_MAX_LDS); });
+    hipExtLaunchKernelGGL(KERNEL, dim3(l.P.gx, l.P.gy), dim3(256), l.P.smem, l.s, l.ev0, l.ev1, 0, l.a, tail...);
+}
+
+// streaming form; the ticketed walk exists for up to three n-tiles (score_plan never asks for it with four)
+template <int NF, bool BF, int NT, bool FH>
+static void launch_stream(const ScoreLaunch& l, int s0, int ns) {
+    if constexpr (NT < 4) {
+        if (l.P.ticketed) return score_launch<scores_stream_kernel<NF, BF, NT, FH, true>>(l, s0, ns);
     }
+    score_launch<scores_stream_kernel<NF, BF, NT, FH, false>>(l, s0, ns);
+}
+template <int NF, bool BF, bool FH>
+static void launch_stream_nt(const ScoreLaunch& l, int s0, int ns) {
+    if (l.P.NT == 1) launch_stream<NF, BF, 1, FH>(l, s0, ns);
+    else if (l.P.NT == 2) launch_stream<NF, BF, 2, FH>(l, s0, ns);
+    else if (l.P.NT == 3) launch_stream<NF, BF, 3, FH>(l, s0, ns);
+}
+static void launch_stream_chunk(const ScoreLaunch& l, int s0, int ns) {
+    if (l.P.unit == 16) {
+        if (l.f16) launch_stream_nt<16, true, true>(l, s0, ns);
+        else if (l.bf) launch_stream_nt<16, true, false>(l, s0, ns);
+        else if (l.P.NT == 4) launch_stream<16, false, 4, false>(l, s0, ns);           // fp32 only: four n-tiles
+        else launch_stream_nt<16, false, false>(l, s0, ns);
+    } else {   // 16-bit bags only: fp32 rows are a multiple of 1 KiB because D % 256 == 0
+        if (l.f16) launch_stream_nt<8, true, true>(l, s0, ns);
+        else launch_stream_nt<8, true, false>(l, s0, ns);
+    }
+}
+template <bool FH>
+static void launch_wide(const ScoreLaunch& l) {
+    switch (l.P.NT) {
+        case 4: score_launch<scores_wide_kernel<4, FH>>(l); break;
+        case 5: score_launch<scores_wide_kernel<5, FH>>(l); break;
+        case 6: score_launch<scores_wide_kernel<6, FH>>(l); break;
+        case 7: score_launch<scores_wide_kernel<7, FH>>(l); break;
+        default: score_launch<scores_wide_kernel<8, FH>>(l); break;
+    }
+}
+template <bool FH>
+static void launch_ring(const ScoreLaunch& l) {
+    if (l.P.NT == 4) score_launch<scores_wide_ring_kernel<4, FH>>(l);
+    else score_launch<scores_wide_ring_kernel<5, FH>>(l);
+}
+template <int CH>
+static void launch_generic(const ScoreLaunch& l) {
+    if (l.f16) score_launch<scores_kernel<CH, true, true>>(l);
+    else if (l.bf) score_launch<scores_kernel<CH, true, false>>(l);
+    else score_launch<scores_kernel<CH, false, false>>(l);
 }
 
 #ifndef MOC_LOOKAHEAD_WGS_DEFAULT
 #define MOC_LOOKAHEAD_WGS_DEFAULT 0
 #endif
+// workgroups of a look-ahead launch, at most (score_plan): MOC_LOOKAHEAD_WGS overrides (0: no cap); read once
+static int lookahead_cap() {
+    static const int cap_env = getenv("MOC_LOOKAHEAD_WGS") ? atoi(getenv("MOC_LOOKAHEAD_WGS")) : MOC_LOOKAHEAD_WGS_DEFAULT;
+    return cap_env;
+}
+
 static int scores_impl(const moc_batch_t* B, const void* bank, moc_stream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
     if (int rc = moc_check_batch(B, "moc_scores")) return rc;
     MOC_REQUIRE(bank && B->stats && B->sel_flag, "moc_scores: null bank/stats/sel_flag");
-    ScoresArgs a;
-    a.X = (const unsigned char*)B->X;
-    a.bank = (const unsigned char*)bank;
-    a.row_off = B->row_off;
-    a.x_off = B->x_off;
-    a.kept = B->mask ? B->kept : nullptr;
-    a.n_kept = B->n_kept;
-    a.stats = B->stats;
-    a.sel_flag = B->sel_flag;
-    a.stride = B->total_rows;
-    a.D = B->D; a.C = B->C; a.Ce = B->Ce; a.NT = bank_nt(B->Ce);
-    a.compact = (B->flags & MOC_STATS_COMPACT) ? 1 : 0;
-    a.cu_reserved = nullptr;
-    a.ticket = nullptr;
-    const bool bf = B->dtype != MOC_F32;          // 16-bit storage (bf16 or fp16): 3-term image, K = 32 per MFMA
-    const bool f16 = B->dtype == MOC_F16;
-    a.oscale = f16 ? 1.f / MOC_F16_BANK_SCALE : 1.f;
-    const size_t img = bf ? (size_t)(B->D / 32) * 3 * 1024 : (size_t)(B->D / 16) * 1024;
-    hipStream_t s = (hipStream_t)stream;
-    // streaming form: persistent workgroups over the flat tile list, the whole bank image (all NT
-    // n-tiles) resident in LDS.  Applies while image + epilogue tiles + at least one slide's metadata fit.
-    const size_t fixed = (size_t)a.NT * img + 4 * 16 * (a.NT * 16 + 1) * sizeof(float) + 16;
-    // (bf16 stops at 3 n-tiles: with 4, the 12 B fragments per batch leave hipcc short of registers and it
-    // parks in-flight load destinations in AGPRs -- tests/test_isa_hazards_cpu.py)
-    if (a.NT <= (bf ? 3 : 4) && fixed + 24 <= 160 * 1024) {
-        a.tpw = 0;
+    const ScoreShape shape = {B->D, B->dtype, bank_nt(B->Ce), B->n_slides, B->total_rows, B->max_rows,
+                              B->tile_ticket != nullptr, B->cu_reserved != nullptr, B->tile_ticket ? lookahead_cap() : 0, false};
+    const ScorePlan P = score_plan(shape);
+    MOC_REQUIRE(P.err != SCORE_PLAN_SLIDES_LDS, "moc_scores: D=%d / n_slides=%d need %zu B of LDS (> 160 KiB)", B->D, B->n_slides, P.need);
+    MOC_REQUIRE(P.err != SCORE_PLAN_RESERVED, "moc_scores: cu_reserved needs tile_ticket");
+    MOC_REQUIRE(P.err != SCORE_PLAN_ROW_LDS, "moc_scores: D=%d needs %zu B of LDS (> 160 KiB)", B->D, P.need);
+    ScoresArgs a = scores_args(B, bank, P.NT);
+    a.tpw = P.tpw;
+    const ScoreLaunch whole = {a, P, (hipStream_t)stream, ev0, ev1, B->dtype != MOC_F32, B->dtype == MOC_F16};
+    switch (P.form) {
+    case SCORE_STREAM:
 #ifdef MOC_STAMPS
         if (const char* em = getenv("MOC_EPI_MODE")) a.tpw = atoi(em);     // diagnostic: row_stats_emit
 #endif
-        const int chunk_max = (int)((160 * 1024 - fixed) / 24);
-        const int chunk = B->n_slides < chunk_max ? B->n_slides : chunk_max;
-        const size_t smem = fixed + (size_t)chunk * 24;
-        MOC_REQUIRE(a.NT > 1 || chunk == B->n_slides, "moc_scores: D=%d / n_slides=%d need %zu B of LDS (> 160 KiB)",
-                    B->D, B->n_slides, fixed + (size_t)B->n_slides * 24);
-        int64_t tiles = 0;   // upper bound from the host-known sizes
-        tiles = (B->total_rows + 15) / 16 + 2 * (int64_t)B->n_slides;
-        int wgs = (int)((tiles + 3) / 4);
-        const int resident = 256 * (smem <= 80 * 1024 ? 2 : 1);
-        if (wgs > resident) wgs = resident;
-        // A look-ahead launch (tile_ticket set: it runs beside the meta-steps of the pass before) is kept to fewer
-        // persistent workgroups: every wave of this kernel holds up to 32 KiB of loads in flight, 2,048 waves 64 MB --
-        // several times what 8 TB/s x the memory latency can use, and every dependent load of a meta-step queues
-        // behind them (profiles/NOTES.md round 4: the steps crawl while a full-width score pass streams, whether or
-        // not it leaves them compute units).  MOC_LOOKAHEAD_WGS overrides (0: no cap).
-        if (B->tile_ticket) {
-            static const int cap_env = getenv("MOC_LOOKAHEAD_WGS") ? atoi(getenv("MOC_LOOKAHEAD_WGS")) : MOC_LOOKAHEAD_WGS_DEFAULT;
-            if (cap_env > 0 && wgs > cap_env) wgs = cap_env;
-        }
-        const int row_b = B->D * moc_elem_size(B->dtype);
-#define MOC_LAUNCH_STREAM(NF, BF, NTT, FH)                                                              \
-        do {                                                                                            \
-            static bool attr_set = false;                                                               \
-            if (!attr_set) {                                                                            \
-                (void)hipFuncSetAttribute((const void*)scores_stream_kernel<NF, BF, NTT, FH>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-                attr_set = true;                                                                        \
-            }                                                                                           \
-            if (a.ticket) launch_stream_ticketed<NF, BF, NTT, FH>(a, wgs, smem, s, (s0 == 0 ? ev0 : nullptr),       \
-                                                                   (s0 + ns == B->n_slides ? ev1 : nullptr), s0, ns); \
-            if (!a.ticket)                                                                                      \
-                hipExtLaunchKernelGGL((scores_stream_kernel<NF, BF, NTT, FH, false>), dim3(wgs), dim3(256), smem, s,  \
-                                      (s0 == 0 ? ev0 : nullptr), (s0 + ns == B->n_slides ? ev1 : nullptr), 0, a, s0, ns); \
-        } while (0)
-#define MOC_LAUNCH_STREAM_NT(NF, BF, FH)                                                                \
-        do {                                                                                            \
-            if (a.NT == 1) MOC_LAUNCH_STREAM(NF, BF, 1, FH);                                            \
-            else if (a.NT == 2) MOC_LAUNCH_STREAM(NF, BF, 2, FH);                                       \
-            else if (a.NT == 3) MOC_LAUNCH_STREAM(NF, BF, 3, FH);                                       \
-        } while (0)
-        MOC_REQUIRE(B->cu_reserved == nullptr || B->tile_ticket != nullptr, "moc_scores: cu_reserved needs tile_ticket");
-        a.ticket = B->tile_ticket;
-        a.cu_reserved = B->cu_reserved;
-        // (four n-tiles, fp32 only: the ticketed form leaves the compiler short of registers and it re-uses load
-        // destinations still in flight -- tests/test_isa_hazards_cpu.py; that shape keeps the static walk, whole chip)
-        if (a.NT == 4) { a.ticket = nullptr; a.cu_reserved = nullptr; }
-        for (int s0 = 0; s0 < B->n_slides; s0 += chunk) {
-            const int ns = B->n_slides - s0 < chunk ? B->n_slides - s0 : chunk;
-            if (a.ticket && hipMemsetAsync(a.ticket, 0, sizeof(int32_t) * (MOC_TICKET_QUEUES + 8) * MOC_TICKET_STRIDE, s) != hipSuccess)
+        if (P.ticketed) { a.ticket = B->tile_ticket; a.cu_reserved = B->cu_reserved; }
+        for (int s0 = 0; s0 < B->n_slides; s0 += P.chunk) {
+            const int ns = B->n_slides - s0 < P.chunk ? B->n_slides - s0 : P.chunk;
+            if (a.ticket && hipMemsetAsync(a.ticket, 0, sizeof(int32_t) * (MOC_TICKET_QUEUES + 8) * MOC_TICKET_STRIDE, whole.s) != hipSuccess)
                 MOC_FAIL(MOC_ELAUNCH, "moc_scores: clearing the tile counter failed");
-            if (row_b % 1024 == 0) {
-                if (f16) MOC_LAUNCH_STREAM_NT(16, true, true);
-                else if (bf) MOC_LAUNCH_STREAM_NT(16, true, false);
-                else if (a.NT == 4) MOC_LAUNCH_STREAM(16, false, 4, false);      // fp32 only: four n-tiles
-                else MOC_LAUNCH_STREAM_NT(16, false, false);
-            } else {
-                if (f16) MOC_LAUNCH_STREAM_NT(8, true, true);
-                else if (bf) MOC_LAUNCH_STREAM_NT(8, true, false);
-                else if (a.NT == 4) MOC_LAUNCH_STREAM(8, false, 4, false);
-                else MOC_LAUNCH_STREAM_NT(8, false, false);
-            }
+            ScoreLaunch part = whole;                                      // the events: first / last chunk
+            part.ev0 = s0 == 0 ? ev0 : nullptr;
+            part.ev1 = s0 + ns == B->n_slides ? ev1 : nullptr;
+            launch_stream_chunk(part, s0, ns);
             MOC_CHECK_LAUNCH("moc_scores(stream)");
         }
-#undef MOC_LAUNCH_STREAM_NT
-#undef MOC_LAUNCH_STREAM
+        return MOC_OK;
+    case SCORE_WIDE_RING:
+        if (whole.f16) launch_ring<true>(whole);
+        else launch_ring<false>(whole);
+        MOC_CHECK_LAUNCH("moc_scores(wide ring)");
+        return MOC_OK;
+    case SCORE_WIDE:
+        if (whole.f16) launch_wide<true>(whole);
+        else launch_wide<false>(whole);
+        MOC_CHECK_LAUNCH("moc_scores(wide)");
+        return MOC_OK;
+    default:
+        if (P.unit == 512) launch_generic<512>(whole);
+        else launch_generic<256>(whole);
+        MOC_CHECK_LAUNCH("moc_scores");
         return MOC_OK;
     }
-    // wide banks on 16-bit storage: the K-split form (every bag row read once)
-    if (bf && a.NT >= 4 && a.NT <= 8 && B->D % 64 == 0) {
-        const size_t kc = wd_kc(a.NT);
-        const size_t buf = (size_t)a.NT * kc * 3 * 1024 + (size_t)4 * WD_R * kc * 1024;
-        const size_t tiles = (size_t)4 * 16 * (a.NT * 16 + 1) * sizeof(float);
-        const size_t smem_w = 2 * buf > tiles ? 2 * buf : tiles;
-        dim3 grid_w(moc_cdiv(B->max_rows, 4 * WD_R * 16), B->n_slides);
-#define MOC_LAUNCH_WIDE(NTT)                                                                            \
-        do {                                                                                            \
-            static bool attr_set[2] = {false, false};                                                   \
-            if (!attr_set[f16]) {                                                                       \
-                if (f16) (void)hipFuncSetAttribute((const void*)scores_wide_kernel<NTT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-                else (void)hipFuncSetAttribute((const void*)scores_wide_kernel<NTT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-                attr_set[f16] = true;                                                                   \
-            }                                                                                           \
-            if (f16) hipExtLaunchKernelGGL((scores_wide_kernel<NTT, true>), grid_w, dim3(256), smem_w, s, ev0, ev1, 0, a); \
-            else hipExtLaunchKernelGGL((scores_wide_kernel<NTT, false>), grid_w, dim3(256), smem_w, s, ev0, ev1, 0, a);    \
-        } while (0)
-        if (a.NT <= 5) {                                               // (6 n-tiles: the register ring spills)
-            const size_t ring = (size_t)3 * ((size_t)((a.NT * 3 + 3) / 4) * 4 * 1024);         // three image slots
-            const size_t smem_r = ring > tiles ? ring : tiles;
-#define MOC_LAUNCH_RING(NTT)                                                                            \
-            do {                                                                                        \
-                static bool attr_set[2] = {false, false};                                               \
-                if (!attr_set[f16]) {                                                                   \
-                    if (f16) (void)hipFuncSetAttribute((const void*)scores_wide_ring_kernel<NTT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-                    else (void)hipFuncSetAttribute((const void*)scores_wide_ring_kernel<NTT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-                    attr_set[f16] = true;                                                               \
-                }                                                                                       \
-                if (f16) hipExtLaunchKernelGGL((scores_wide_ring_kernel<NTT, true>), grid_w, dim3(256), smem_r, s, ev0, ev1, 0, a); \
-                else hipExtLaunchKernelGGL((scores_wide_ring_kernel<NTT, false>), grid_w, dim3(256), smem_r, s, ev0, ev1, 0, a);    \
-            } while (0)
-            if (a.NT == 4) MOC_LAUNCH_RING(4);
-            else MOC_LAUNCH_RING(5);
-#undef MOC_LAUNCH_RING
-            MOC_CHECK_LAUNCH("moc_scores(wide ring)");
-            return MOC_OK;
-        }
-        if (smem_w < 160 * 1024) {
-            switch (a.NT) {
-                case 4: MOC_LAUNCH_WIDE(4); break;
-                case 5: MOC_LAUNCH_WIDE(5); break;
-                case 6: MOC_LAUNCH_WIDE(6); break;
-                case 7: MOC_LAUNCH_WIDE(7); break;
-                default: MOC_LAUNCH_WIDE(8); break;
-            }
-            MOC_CHECK_LAUNCH("moc_scores(wide)");
-            return MOC_OK;
-        }
-#undef MOC_LAUNCH_WIDE
-    }
-    a.tpw = 1;
-    const size_t smem = img + (size_t)4 * 16 * (a.NT * 16 + 1) * sizeof(float);
-    MOC_REQUIRE(smem <= 160 * 1024, "moc_scores: D=%d needs %zu B of LDS (> 160 KiB)", B->D, smem);
-    dim3 grid(moc_cdiv(B->max_rows, 64 * a.tpw), B->n_slides), block(256);
-#define MOC_LAUNCH_SCORES(CH, BF, FH)                                                                   \
-    do {                                                                                                \
-        static bool attr_set = false;                                                                   \
-        if (!attr_set) {                                                                                \
-            (void)hipFuncSetAttribute((const void*)scores_kernel<CH, BF, FH>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-            attr_set = true;                                                                            \
-        }                                                                                               \
-        hipExtLaunchKernelGGL((scores_kernel<CH, BF, FH>), grid, block, smem, s, ev0, ev1, 0, a);       \
-    } while (0)
-    if (B->D % 512 == 0) {
-        if (f16) MOC_LAUNCH_SCORES(512, true, true);
-        else if (bf) MOC_LAUNCH_SCORES(512, true, false);
-        else MOC_LAUNCH_SCORES(512, false, false);
-    } else {
-        if (f16) MOC_LAUNCH_SCORES(256, true, true);
-        else if (bf) MOC_LAUNCH_SCORES(256, true, false);
-        else MOC_LAUNCH_SCORES(256, false, false);
-    }
-#undef MOC_LAUNCH_SCORES
-    MOC_CHECK_LAUNCH("moc_scores");
-    return MOC_OK;
 }
 
 extern "C" int moc_scores(const moc_batch_t* B, const void* bank, moc_stream_t stream) {

@@ -12,6 +12,7 @@
 // units: an evaluation pass has the chip to itself), in a translation unit of its own so that the existing kernels'
 // code does not change by an instruction (scripts/kernel_isa.py).
 #include <stdlib.h>
+#include <mutex>
 #include "moc_common.h"
 #include "moc_scores_stream.h"
 
@@ -23,7 +24,7 @@ struct BankWindows {
     int Ce[4];
 };
 
-// NT = banks of the launch.  The two register limits recorded at moc_scores' dispatch hold here as they do there: four
+// NT = banks of the launch.  The two register limits recorded in score_plan (moc_scores_plan.h) hold here as they do there: four
 // n-tiles on fp32 bags only, three on 16-bit bags (twelve B fragments per batch leave hipcc short of registers).
 template <int NF, bool BF16, int NT, bool F16>
 __global__ __launch_bounds__(256, NT == 1 ? 2 : 1) void scores_banks_kernel(ScoresArgs a, BankWindows bw, int slide0, int n_slides) {
@@ -213,27 +214,30 @@ __global__ __launch_bounds__(256, NT == 1 ? 2 : 1) void scores_banks_kernel(Scor
 }  // namespace
 
 // ------------------------------------------------------------------ host entry points
-int moc_check_batch(const moc_batch_t* B, const char* who);
-
-static size_t bank_tile_bytes(int D, int dtype) {
-    return dtype != MOC_F32 ? (size_t)(D / 32) * 3 * 1024 : (size_t)(D / 16) * 1024;
-}
-// LDS of a launch over G banks without the per-slide metadata: images, the four waves' epilogue tiles, the slack word
-static size_t banks_fixed_lds(int D, int G, int dtype) {
-    return (size_t)G * bank_tile_bytes(D, dtype) + 4 * 16 * (G * 16 + 1) * sizeof(float) + 16;
-}
-
 extern "C" int moc_scores_banks_max(int D, int dtype) {
     if (D <= 0 || D % 256 != 0 || (dtype != MOC_F32 && dtype != MOC_BF16 && dtype != MOC_F16)) return 0;
-    // the n-tile limits of the streaming kernel (scores_impl: four on fp32 bags, three on 16-bit bags), then LDS
-    int g = dtype != MOC_F32 ? 3 : 4;
-    while (g > 0 && banks_fixed_lds(D, g, dtype) + 24 > 160 * 1024) --g;
-    return g;
+    return score_banks_max(D, dtype);
 }
 
 extern "C" size_t moc_bank_set_bytes(int D, int n_banks, int dtype) {
-    if (D <= 0 || n_banks <= 0) return 0;
-    return (size_t)n_banks * bank_tile_bytes(D, dtype);
+    return D <= 0 || n_banks <= 0 ? 0 : (size_t)n_banks * score_img_bytes(D, dtype);
+}
+
+// NT = banks of the launch: raises the instantiation's dynamic-LDS limit once per process (call_once: worker threads) and
+// launches it
+template <int NF, bool BF, int NT, bool FH>
+static void launch_banks(const ScoresArgs& a, const BankWindows& bw, const ScorePlan& P, hipStream_t s, int s0, int ns) {
+    static std::once_flag attr;
+    std::call_once(attr, [] {
+        (void)hipFuncSetAttribute((const void*)scores_banks_kernel<NF, BF, NT, FH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SCORE_MAX_LDS);
+    });
+    hipLaunchKernelGGL((scores_banks_kernel<NF, BF, NT, FH>), dim3(P.gx), dim3(256), P.smem, s, a, bw, s0, ns);
+}
+template <int NF, bool BF, bool FH>
+static void launch_banks_nt(const ScoresArgs& a, const BankWindows& bw, const ScorePlan& P, hipStream_t s, int s0, int ns) {
+    if (P.NT == 1) launch_banks<NF, BF, 1, FH>(a, bw, P, s, s0, ns);
+    else if (P.NT == 2) launch_banks<NF, BF, 2, FH>(a, bw, P, s, s0, ns);
+    else if (P.NT == 3) launch_banks<NF, BF, 3, FH>(a, bw, P, s, s0, ns);
 }
 
 extern "C" int moc_scores_banks(const moc_batch_t* B, const moc_bank_set_t* S, moc_stream_t stream) {
@@ -255,76 +259,39 @@ extern "C" int moc_scores_banks(const moc_batch_t* B, const moc_bank_set_t* S, m
                 "(tile_ticket / cu_reserved must be null)");
     MOC_REQUIRE(!(B->flags & MOC_STATS_COMPACT), "moc_scores_banks: full statistics layout only (MOC_STATS_COMPACT is for banks "
                 "wider than 16 columns)");
-    const int G = S->n_banks, gmax = moc_scores_banks_max(B->D, B->dtype);
+    // the streaming static form of moc_scores for G n-tiles: persistent workgroups, slides in chunks whose metadata fits
+    // beside the images
+    const int G = S->n_banks, gmax = score_banks_max(B->D, B->dtype);
+    const ScoreShape shape = {B->D, B->dtype, G, B->n_slides, B->total_rows, B->max_rows, false, false, 0, true};
+    const ScorePlan P = score_plan(shape);
     if (gmax == 0)
         MOC_FAIL(MOC_EUNSUPPORTED, "moc_scores_banks: D=%d needs %zu B of LDS for one bank's image, the epilogue tiles and one "
-                 "slide (> 160 KiB)", B->D, banks_fixed_lds(B->D, 1, B->dtype) + 24);
-    MOC_REQUIRE(G <= gmax, "moc_scores_banks: %d banks, but one launch serves at most %d at D=%d on this storage "
+                 "slide (> 160 KiB)", B->D, P.need);
+    MOC_REQUIRE(G <= gmax && !P.err, "moc_scores_banks: %d banks, but one launch serves at most %d at D=%d on this storage "
                 "(moc_scores_banks_max)", G, gmax, B->D);
-    ScoresArgs a;
-    a.X = (const unsigned char*)B->X;
-    a.bank = (const unsigned char*)S->image;
-    a.row_off = B->row_off;
-    a.x_off = B->x_off;
-    a.kept = B->mask ? B->kept : nullptr;
-    a.n_kept = B->n_kept;
-    a.stats = nullptr;
-    a.sel_flag = nullptr;
-    a.stride = B->total_rows;
-    a.D = B->D; a.C = S->C; a.Ce = 0; a.NT = G;
-    a.tpw = 0;
+    ScoresArgs a = scores_args(B, S->image, G);
+    a.C = S->C; a.Ce = 0;
+    a.stats = nullptr; a.sel_flag = nullptr;
     a.compact = 0;
-    a.cu_reserved = nullptr;
-    a.ticket = nullptr;
     const bool bf = B->dtype != MOC_F32, f16 = B->dtype == MOC_F16;
-    a.oscale = f16 ? 1.f / MOC_F16_BANK_SCALE : 1.f;
     BankWindows bw;
     for (int g = 0; g < 4; ++g) {
         const int h = g < G ? g : 0;
         bw.stats[g] = S->stats[h]; bw.sel_flag[g] = S->sel_flag[h]; bw.Ce[g] = S->Ce[h];
     }
     hipStream_t s = (hipStream_t)stream;
-    // as scores_impl launches the streaming form: persistent workgroups, slides in chunks whose metadata fits beside the images
-    const size_t fixed = banks_fixed_lds(B->D, G, B->dtype);
-    const int chunk_max = (int)((160 * 1024 - fixed) / 24);
-    const int chunk = B->n_slides < chunk_max ? B->n_slides : chunk_max;
-    const size_t smem = fixed + (size_t)chunk * 24;
-    const int64_t tiles = (B->total_rows + 15) / 16 + 2 * (int64_t)B->n_slides;
-    int wgs = (int)((tiles + 3) / 4);
-    const int resident = 256 * (smem <= 80 * 1024 ? 2 : 1);
-    if (wgs > resident) wgs = resident;
-    const int row_b = B->D * moc_elem_size(B->dtype);
-#define MOC_LAUNCH_BANKS(NF, BF, NTT, FH)                                                               \
-    do {                                                                                                \
-        static bool attr_set = false;                                                                   \
-        if (!attr_set) {                                                                                \
-            (void)hipFuncSetAttribute((const void*)scores_banks_kernel<NF, BF, NTT, FH>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-            attr_set = true;                                                                            \
-        }                                                                                               \
-        hipLaunchKernelGGL((scores_banks_kernel<NF, BF, NTT, FH>), dim3(wgs), dim3(256), smem, s, a, bw, s0, ns); \
-    } while (0)
-#define MOC_LAUNCH_BANKS_NT(NF, BF, FH)                                                                 \
-    do {                                                                                                \
-        if (G == 1) MOC_LAUNCH_BANKS(NF, BF, 1, FH);                                                    \
-        else if (G == 2) MOC_LAUNCH_BANKS(NF, BF, 2, FH);                                               \
-        else if (G == 3) MOC_LAUNCH_BANKS(NF, BF, 3, FH);                                               \
-    } while (0)
-    for (int s0 = 0; s0 < B->n_slides; s0 += chunk) {
-        const int ns = B->n_slides - s0 < chunk ? B->n_slides - s0 : chunk;
-        if (row_b % 1024 == 0) {
-            if (f16) MOC_LAUNCH_BANKS_NT(16, true, true);
-            else if (bf) MOC_LAUNCH_BANKS_NT(16, true, false);
-            else if (G == 4) MOC_LAUNCH_BANKS(16, false, 4, false);          // fp32 only: four n-tiles
-            else MOC_LAUNCH_BANKS_NT(16, false, false);
-        } else {
-            if (f16) MOC_LAUNCH_BANKS_NT(8, true, true);
-            else if (bf) MOC_LAUNCH_BANKS_NT(8, true, false);
-            else if (G == 4) MOC_LAUNCH_BANKS(8, false, 4, false);
-            else MOC_LAUNCH_BANKS_NT(8, false, false);
+    for (int s0 = 0; s0 < B->n_slides; s0 += P.chunk) {
+        const int ns = B->n_slides - s0 < P.chunk ? B->n_slides - s0 : P.chunk;
+        if (P.unit == 16) {
+            if (f16) launch_banks_nt<16, true, true>(a, bw, P, s, s0, ns);
+            else if (bf) launch_banks_nt<16, true, false>(a, bw, P, s, s0, ns);
+            else if (G == 4) launch_banks<16, false, 4, false>(a, bw, P, s, s0, ns);          // fp32 only: four n-tiles
+            else launch_banks_nt<16, false, false>(a, bw, P, s, s0, ns);
+        } else {   // 16-bit bags only: fp32 rows are a multiple of 1 KiB because D % 256 == 0
+            if (f16) launch_banks_nt<8, true, true>(a, bw, P, s, s0, ns);
+            else launch_banks_nt<8, true, false>(a, bw, P, s, s0, ns);
         }
         MOC_CHECK_LAUNCH("moc_scores_banks");
     }
-#undef MOC_LAUNCH_BANKS_NT
-#undef MOC_LAUNCH_BANKS
     return MOC_OK;
 }

@@ -1,8 +1,10 @@
 // Device pieces of the streaming score pass that more than one translation unit compiles: the kernel arguments, the
 // row statistics of a 16-row tile (row_stats_emit) and the hand-issued loads with their counted waits.  moc_scores.hip
 // (moc_scores) and moc_scores_banks.hip (moc_scores_banks) include it; the statements are the ones moc_scores.hip held.
+// The host side of both entries comes with it: the launch plan (moc_scores_plan.h) and the argument filler.
 #pragma once
 #include "moc_common.h"
+#include "moc_scores_plan.h"
 #include <type_traits>
 
 namespace {
@@ -25,6 +27,28 @@ struct ScoresArgs {
     const uint32_t* cu_reserved;   // nullable: compute units the streaming form stays off (moc_batch_t.cu_reserved)
     int32_t* ticket;               // nullable: the streaming form's tile counter (moc_batch_t.tile_ticket), zero at launch
 };
+
+// The arguments of a pass over batch B against the image `bank` of NT n-tiles, for both entries: static walk over the
+// whole chip (no ticket, no reserved set) and tpw = 0 until the caller's plan says otherwise.
+inline ScoresArgs scores_args(const moc_batch_t* B, const void* bank, int NT) {
+    ScoresArgs a;
+    a.X = (const unsigned char*)B->X;
+    a.bank = (const unsigned char*)bank;
+    a.row_off = B->row_off;
+    a.x_off = B->x_off;
+    a.kept = B->mask ? B->kept : nullptr;
+    a.n_kept = B->n_kept;
+    a.stats = B->stats;
+    a.sel_flag = B->sel_flag;
+    a.stride = B->total_rows;
+    a.D = B->D; a.C = B->C; a.Ce = B->Ce; a.NT = NT;
+    a.tpw = 0;
+    a.oscale = B->dtype == MOC_F16 ? 1.f / MOC_F16_BANK_SCALE : 1.f;
+    a.compact = (B->flags & MOC_STATS_COMPACT) ? 1 : 0;
+    a.cu_reserved = nullptr;
+    a.ticket = nullptr;
+    return a;
+}
 
 // The two partners of a lane under xor 16 / xor 32 without LDS (ds_bpermute) or its lgkmcnt: the gfx950 row swaps.
 // permlane16_swap(x, x) leaves (x[row 0], x[row 1]) in BOTH rows 0 and 1 of the pair (rows 2, 3 alike), permlane32_swap

@@ -16,8 +16,6 @@
 // order.  Marks from all columns land in one byte-per-row flag array = the union.
 #include "moc_common.h"
 
-int moc_check_batch(const moc_batch_t* B, const char* who);
-
 namespace {
 
 // ---- block-wide radix select -------------------------------------------------

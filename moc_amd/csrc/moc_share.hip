@@ -13,8 +13,6 @@
 // for i < n_kept[l].  A copy: no arithmetic touches a value.
 #include "moc_common.h"
 
-int moc_check_batch(const moc_batch_t* B, const char* who);
-
 namespace {
 
 constexpr int SH_THREADS = 256;

@@ -9,8 +9,6 @@
 #include "moc_p2p.h"
 #include "moc_step_lds.h"   // the step kernels' dynamic LDS: one layout per kernel, for the launch and for the carve
 
-int moc_check_batch(const moc_batch_t* B, const char* who);
-
 using namespace moc_meta_internal;
 namespace lds = moc_step_lds;
 static_assert(lds::H == MOC_HIDDEN, "moc_step_lds.h carries the hidden width on its own");

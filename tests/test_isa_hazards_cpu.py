@@ -1,4 +1,4 @@
-"""Static check of the kernels that issue loads through inline asm (moc_scores.hip): between an asm
+"""Static check of the kernels that issue loads through inline asm (moc_scores.hip, moc_scores_banks.hip): between an asm
 `global_load_dwordx4 v[a:b], ...` / `ds_read_b128 v[a:b], ...` and the hand-written `s_waitcnt
 vmcnt(N)` / `lgkmcnt(N)` that covers it, no instruction may read or write v[a:b] -- the compiler does
 not know the data is still in flight, and under register pressure it has been seen to copy such
@@ -12,6 +12,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "moc_amd", "csrc", "moc_scores.hip")
+SRC_BANKS = os.path.join(ROOT, "moc_amd", "csrc", "moc_scores_banks.hip")
 
 
 def _regs(tok):
@@ -83,15 +84,14 @@ def _check_kernel(name, lines, precise=True):
     return n_loads, n_waits
 
 
-@pytest.mark.timeout(300)
-def test_no_instruction_touches_inflight_asm_load_registers(tmp_path):
-    asm = tmp_path / "scores.s"
+def _kernels_of(src, pattern, tmp_path):
+    """{symbol: ISA lines} of the kernels of `src` whose name matches `pattern`"""
+    asm = tmp_path / (os.path.basename(src) + ".s")
     subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-S",
-                           "--cuda-device-only", "-o", str(asm), SRC], stderr=subprocess.DEVNULL)
-    text = asm.read_text().splitlines()
+                           "--cuda-device-only", "-o", str(asm), src], stderr=subprocess.DEVNULL)
     kernels, cur, name = {}, None, None
-    for ln in text:
-        m = re.match(r"^(_ZN\S*scores_(?:stream|wide|wide_ring)_kernel\S*):", ln)
+    for ln in asm.read_text().splitlines():
+        m = re.match(r"^(_ZN\S*(?:%s)\S*):" % pattern, ln)
         if m:
             name, cur = m.group(1), []
             continue
@@ -100,9 +100,28 @@ def test_no_instruction_touches_inflight_asm_load_registers(tmp_path):
             if "s_endpgm" in ln:
                 kernels[name] = cur
                 cur = None
+    return kernels
+
+
+@pytest.mark.timeout(300)
+def test_no_instruction_touches_inflight_asm_load_registers(tmp_path):
+    kernels = _kernels_of(SRC, "scores_(?:stream|wide|wide_ring)_kernel", tmp_path)
     assert len(kernels) >= 4, f"expected the asm-load kernels in the ISA, found {list(kernels)}"
     for k, lines in kernels.items():
         n_loads, n_waits = _check_kernel(k, lines, precise=True)
         if "scores_stream_kernel" in k:
             assert n_loads["vm"] >= 16 and n_waits["vm"] >= 2, (k, n_loads, n_waits)
+        assert n_loads["lgkm"] >= 8 and n_waits["lgkm"] >= 6, (k, n_loads, n_waits)
+
+
+@pytest.mark.timeout(300)
+def test_the_bank_kernels_hold_the_same_line(tmp_path):
+    """scores_banks_kernel is the streaming kernel's static walk with another epilogue: the same hand-issued loads, the
+    same counted waits, the same floor.  Sixteen instantiations: NF = 16 on fp32 bags (1 .. 4 banks), NF = 16 and 8 on
+    bf16 and fp16 bags (1 .. 3 banks)."""
+    kernels = _kernels_of(SRC_BANKS, "scores_banks_kernel", tmp_path)
+    assert len(kernels) == 16, sorted(kernels)
+    for k, lines in kernels.items():
+        n_loads, n_waits = _check_kernel(k, lines, precise=True)
+        assert n_loads["vm"] >= 16 and n_waits["vm"] >= 2, (k, n_loads, n_waits)
         assert n_loads["lgkm"] >= 8 and n_waits["lgkm"] >= 6, (k, n_loads, n_waits)
