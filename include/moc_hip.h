@@ -136,6 +136,24 @@ typedef struct moc_batch {
                                     less at the head of the forward (arguments -> sel_row -> rows), exact grids, fewer
                                     record keys per lane in the step.  The same results either way.  Ignored by
                                     moc_train_steps_graph: a captured pass serves later passes too, with other counts.  */
+    /* ---- the selected-row counts by mailbox (both nullable / 0; appended: a caller that zero-fills THIS struct is
+     * served as before.  The struct grew by 16 bytes and the library reads them, so callers are rebuilt against this
+     * header; the version number stays 20) ----
+     * The asynchronous copy above tells the host every count of a pass at once, and only when the whole of phase A and
+     * the copy behind it have run.  compact_kernel -- one workgroup per slide -- knows S long before: when n_sel_mail is
+     * set, its thread 0 stores ((uint64_t)n_sel_ticket << 32) | (uint32_t)S to n_sel_mail[b] beside n_sel[b], as ONE
+     * 64-bit system-scope store: count and ticket travel in one naturally aligned word, so no fence, counter or further
+     * launch is needed.  Slide b's word is valid exactly when its upper half equals the ticket the caller expects; the
+     * caller takes a fresh ticket for every launch that rewrites n_sel, so a word of an earlier phase A never passes.
+     * moc_phase_a and moc_gather_candidates write the words; moc_train_steps reads slide b's word ONCE, in front of
+     * step b's two launches (n_sel_host, when set, wins), and hands the count to both by value: a slide whose word has
+     * not arrived runs on the device count.  The only wait is a bounded one in front of a call's FIRST step, for that
+     * slide's word (MOC_N_SEL_SPIN_US microseconds at the most, default 100; 0: none): the words of a phase A arrive
+     * together, at its end.  The same results either way.  moc_train_steps_graph
+     * ignores both fields; the data-parallel, p2p and batched-run entries read n_sel_host only. */
+    uint64_t*       n_sel_mail;   /* HOST [n_slides], device-mapped pinned (hipHostMalloc / a pinned tensor), 8-byte
+                                     aligned; lives while launches that write it can be in flight */
+    uint32_t        n_sel_ticket; /* the ticket the caller expects in the words' upper halves; 0: none */
 } moc_batch_t;
 
 /* The meta-learner ("senet", main_moc.py:299-312) and its Adam state
@@ -597,6 +615,13 @@ int moc_train_steps(const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws
                     const int64_t* labels, int slide0, int n, uint32_t use_bits,
                     moc_stream_t stream);
 
+/* How often moc_train_steps knew a step's selected-row count on the host (moc_batch_t.n_sel_host or a valid word of
+ * n_sel_mail) before it launched the step: process-wide counters of the steps it has issued and of those among them with
+ * a host count.  Either pointer may be NULL; reset != 0 zeroes both after reading.  Tests and measurements read the
+ * share here, without a profiler.  Additive to ABI 20 (as the two mailbox fields at the end of moc_batch_t are): the
+ * version number is unchanged. */
+int moc_n_sel_stats(int64_t* known, int64_t* steps, int reset);
+
 /* The same pass as ONE graph launch (main_moc.py:380-410: the whole `for data in train_loader` body, n slides).
  * moc_train_steps issues 2 n + 1 kernel launches; at the start of a run -- or of a short timed region -- the stream is
  * empty and the chain of 20-us meta-steps cannot run ahead of the host.  A `moc_step_graph_t` keeps each distinct pass
@@ -609,8 +634,8 @@ int moc_train_steps(const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws
  *   - all calls on one handle must be ordered on one stream (the counter lives in stream order);
  *   - M->step is read on every call: if it is not where the handle left it (another optimizer stepped, a checkpoint
  *     was loaded), the device counter is put right first; new hyper-parameters or an exhausted table rebuild the table;
- *   - B->n_sel_host is ignored: a captured pass reads the device n_sel, whichever pass it was captured in (the
- *     stream-launch fall-back below does use it);
+ *   - B->n_sel_host, B->n_sel_mail and B->n_sel_ticket are ignored: a captured pass reads the device n_sel, whichever
+ *     pass it was captured in (the stream-launch fall-back below does use them);
  *   - shapes outside the one-launch steps, n > max_steps, or a runtime that refuses capture / instantiation fall back
  *     to moc_train_steps (moc_step_graph_stats tells which path ran).
  * The caller advances M->step by n afterwards, as with moc_train_steps. */

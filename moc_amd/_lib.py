@@ -39,6 +39,7 @@ class MocBatch(C.Structure):
         ("kept", _p), ("n_kept", _p), ("stats", _p), ("sel_flag", _p), ("sel_idx", _p),
         ("sel_row", _p), ("n_sel", _p), ("cand", _p),
         ("cu_reserved", _p), ("tile_ticket", _p), ("n_sel_host", _p),
+        ("n_sel_mail", _p), ("n_sel_ticket", C.c_uint32),
     ]
 
 
@@ -110,6 +111,7 @@ SIGNATURES = {
     "moc_senet_backward": (C.c_int, [_p, C.c_int, C.c_int64, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "moc_adam_step": (C.c_int, [_MP, C.c_float, _p]),
     "moc_train_steps": (C.c_int, [_BP, _MP, _WP, _p, C.c_int, C.c_int, C.c_uint32, _p]),
+    "moc_n_sel_stats": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]),
     "moc_train_steps_runs": (C.c_int, [_BP, _MP, C.POINTER(MocRuns), _WP, _p, C.c_int, C.c_int, C.c_uint32, _p]),
     "moc_train_runs_mode": (C.c_int, [_BP, _WP]),
     "moc_train_steps_runs_hp": (C.c_int, [_BP, _MP, C.POINTER(MocRuns), _WP, _p, C.c_int, C.c_int, C.c_uint32,

@@ -22,6 +22,8 @@
 //               (moc_step_pool.hip, which also holds the loss-only entries)
 // This file: the plan, the kernels' LDS limits, the training entries over those launchers, the step-graph handle.
 // What the step sources share: moc_step_shared.h; what crosses between them: moc_meta_internal.h.
+#include <atomic>
+#include <chrono>
 #include <cstring>
 #include <new>
 #include "moc_step_shared.h"
@@ -100,16 +102,51 @@ namespace {
 
 // The one-launch step of plan p.  next_slide: the slide the step after this one works on, in the same work arrays (-1: none /
 // unknown) -- the tile-record step prefetches its rows.  x: the gradient exchange, which the tile-record kernel has not got.
+// S_host: the slide's selected-row count as this step's forward was given it (host_n_sel; -1: not asked / not known).
 int launch_fused_step(const StepPlan& p, const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws_t* ws, const int64_t* labels,
                       int slide, uint32_t use_bits, const AdamCoef& k, float* W2out, hipStream_t s,
-                      int apply_adam = 1, const P2pArgs* x = nullptr, const StepTab* tab = nullptr, int next_slide = -1) {
+                      int apply_adam = 1, const P2pArgs* x = nullptr, const StepTab* tab = nullptr, int next_slide = -1,
+                      int S_host = -1) {
     MOC_REQUIRE(p.one_launch() && !(p.tiles() && x), "moc_fused_step: plan of kind %d%s", (int)p.kind, x ? " with a gradient exchange" : "");
     if (p.tiles())                                         // over the forward's tile records (the forward was told to leave them)
-        return launch_tile_step(p, B, M, ws, labels, slide, use_bits, k, W2out, s, apply_adam, tab, next_slide);
+        return launch_tile_step(p, B, M, ws, labels, slide, use_bits, k, W2out, s, apply_adam, tab, next_slide, S_host);
     return launch_fused_kernel(p, B, M, ws, labels, slide, use_bits, k, W2out, s, apply_adam, x, tab);
 }
 
+// moc_n_sel_stats: the steps moc_train_steps has issued, and those among them whose S the host knew (process-wide)
+std::atomic<int64_t> g_steps_issued{0}, g_steps_known{0};
+
+// Asked ONCE per step, in front of its two launches: slide b's selected-row count for both (host_n_sel), counted.
+int step_n_sel(const moc_batch_t* B, int b) {
+    const int S = host_n_sel(B, b);
+    g_steps_issued.fetch_add(1, std::memory_order_relaxed);
+    if (S >= 0) g_steps_known.fetch_add(1, std::memory_order_relaxed);
+    return S;
+}
+
+// A BOUNDED wait in front of a pass's first step (MOC_N_SEL_SPIN_US microseconds at the most; 0: none): the look-ahead phase A
+// of a pass is launched right before the host turns to that pass's steps, and compact_kernel -- its last launch -- stores
+// all slides' words within a few microseconds of each other, so the steps the host issues before that moment run on the
+// bound and the ones behind it on their count.  The GPU still has the previous pass's steps in its queue meanwhile.
+// Measured (profiles/NOTES.md): without the wait 38-70 % of the benchmark's steps know their S, with 100 us 88-99 %, with
+// 250 us all of them; `value` is highest at 100.  A word that never comes (no phase A under this ticket) costs the bound
+// once per call.
+void await_first_word(const moc_batch_t* B, int b) {
+    static const int spin_us = getenv("MOC_N_SEL_SPIN_US") ? atoi(getenv("MOC_N_SEL_SPIN_US")) : 100;
+    if (spin_us <= 0 || B->n_sel_host || !B->n_sel_mail || B->n_sel_ticket == 0 || host_n_sel(B, b) >= 0) return;
+    const auto until = std::chrono::steady_clock::now() + std::chrono::microseconds(spin_us);
+    while (host_n_sel(B, b) < 0 && std::chrono::steady_clock::now() < until) {}
+}
+
 }  // namespace
+
+extern "C" int moc_n_sel_stats(int64_t* known, int64_t* steps, int reset) {
+    const int64_t k = reset ? g_steps_known.exchange(0) : g_steps_known.load();
+    const int64_t n = reset ? g_steps_issued.exchange(0) : g_steps_issued.load();
+    if (known) *known = k;
+    if (steps) *steps = n;
+    return MOC_OK;
+}
 
 extern "C" int moc_train_grad(const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws_t* ws,
                               const int64_t* labels, int slide, uint32_t use_bits, moc_stream_t stream) {
@@ -234,12 +271,13 @@ extern "C" int moc_train_steps(const moc_batch_t* B, const moc_meta_t* M, const 
     hipStream_t s = (hipStream_t)stream;
     if (int rc = step_attrs()) return rc;
     const StepPlan p = step_plan(B, ws, false);
+    await_first_word(B, slide0);
     if (p.one_launch()) return issue_fused_pass(p, B, M, ws, labels, slide0, n, use_bits, s, nullptr);
     if (int rc = launch_w1_images(B, M, nullptr, s)) return rc;      // afterwards the W1 update keeps it in sync
     for (int t = 0; t < n; ++t) {
         const int b = slide0 + t;
         const AdamCoef k = adam_coef(M, M->step + 1 + t, 1.f);
-        if (int rc = launch_forward(B, M, ws, b, 1, use_bits, s)) return rc;
+        if (int rc = launch_forward(B, M, ws, b, 1, use_bits, s, false, nullptr, 0, step_n_sel(B, b))) return rc;
         if (int rc = launch_pool_finish(p, B, M, ws, labels, b, 1, 1, 1, use_bits, k, s)) return rc;
         if (int rc = launch_w1(B, M, ws, 1, k, s, p.pool_one)) return rc;
     }
@@ -450,8 +488,12 @@ int issue_fused_pass(const StepPlan& p, const moc_batch_t* B, const moc_meta_t* 
         if (G) { st.tab = G->tab; st.ctr = G->ctr; st.pos = t; }
         else k = adam_coef(M, M->step + 1 + t, 1.f);
         Mt.W2 = cur;
-        if (int rc = launch_forward(B, &Mt, ws, b, 1, use_bits, s, p.tiles())) return rc;
-        if (int rc = launch_fused_step(p, B, &Mt, ws, labels, b, use_bits, k, nxt, s, 1, nullptr, G ? &st : nullptr, t + 1 < n ? b + 1 : -1)) return rc;
+        // the slide's S where the host knows it by now, decided per step and the same for both launches (a captured pass
+        // serves other passes: never)
+        const int S_host = G ? -1 : step_n_sel(B, b);
+        if (int rc = launch_forward(B, &Mt, ws, b, 1, use_bits, s, p.tiles(), nullptr, 0, S_host)) return rc;
+        if (int rc = launch_fused_step(p, B, &Mt, ws, labels, b, use_bits, k, nxt, s, 1, nullptr, G ? &st : nullptr, t + 1 < n ? b + 1 : -1,
+                                       S_host)) return rc;
         float* tmp = cur; cur = nxt; nxt = tmp;
     }
     if (cur != M->W2) {   // odd number of steps: the current W2 lives in the scratch buffer
@@ -527,10 +569,12 @@ extern "C" int moc_train_steps_graph(moc_step_graph_t* G, const moc_batch_t* B, 
     // pass (moc_host_max_kept): a different number every pass.  A captured pass must not depend on it, so the graph is
     // built for the largest SLIDE of the range -- an upper bound of every pass's kept rows (surplus workgroups leave at
     // once on n_sel).
-    // Nor on a pass's selected-row counts: n_sel_host would bake one pass's S, forward grid and tile bound into the graph, and
-    // GraphKey has no field for them -- a captured pass always reads the device n_sel.
+    // Nor on a pass's selected-row counts: n_sel_host or the mailbox would bake one pass's S, forward grid and tile bound into
+    // the graph, and GraphKey has no field for them -- a captured pass always reads the device n_sel.
     moc_batch_t Bg = *B;
     Bg.n_sel_host = nullptr;
+    Bg.n_sel_mail = nullptr;
+    Bg.n_sel_ticket = 0;
     if (B->row_off_host) {
         int64_t mx = 1;
         for (int i = slide0; i < slide0 + n; ++i) {

@@ -1223,7 +1223,8 @@ int64_t dense_rows(const moc_batch_t* B, int slide0, int n) {
 }  // namespace
 
 int moc_meta_internal::launch_forward(const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws_t* ws, int slide0, int n,
-                                      uint32_t use_bits, hipStream_t s, bool emit_tiles, const moc_runs_t* runs, int64_t w2_stride) {
+                                      uint32_t use_bits, hipStream_t s, bool emit_tiles, const moc_runs_t* runs, int64_t w2_stride,
+                                      int S_host) {
     MOC_REQUIRE(!(B->flags & MOC_CAND_FROM_STATS) || (B->stats && B->sel_idx),
                 "moc_meta_forward: MOC_CAND_FROM_STATS needs the batch's stats and sel_idx");
     FwdArgs a = fwd_args(B, M, slide0, use_bits);
@@ -1241,10 +1242,12 @@ int moc_meta_internal::launch_forward(const moc_batch_t* B, const moc_meta_t* M,
     }
     dim3 grid(moc_cdiv(s_bound(B), 16), n);
     // one slide (a training step) whose S the host knows: S as an argument, and exactly the workgroups that have rows
+    // (S_host: the train step's host_n_sel, which its step kernel gets too; callers that do not ask: n_sel_host)
     const bool s_known = n == 1 && B->n_sel_host != nullptr;
-    if (s_known && !runs) {
-        a.S_host = B->n_sel_host[slide0];
-        MOC_REQUIRE(a.S_host >= 0 && a.S_host <= s_bound(B), "moc_meta_forward: n_sel_host[%d] = %d is not a row count of this batch (bound %d)",
+    if (S_host < 0 && s_known) S_host = B->n_sel_host[slide0];
+    if (n == 1 && !runs && (S_host >= 0 || s_known)) {
+        a.S_host = S_host;
+        MOC_REQUIRE(a.S_host >= 0 && a.S_host <= s_bound(B), "moc_meta_forward: the host's count of slide %d, %d, is not a row count of this batch (bound %d)",
                     slide0, a.S_host, s_bound(B));
         grid.x = a.S_host > 0 ? moc_cdiv(a.S_host, 16) : 1;
     }

@@ -215,10 +215,11 @@ int launch_adam_all(const moc_meta_t* M, const AdamCoef& k, unsigned char* img, 
 int launch_fused_kernel(const StepPlan& p, const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws_t* ws, const int64_t* labels,
                         int slide, uint32_t use_bits, const AdamCoef& k, float* W2out, hipStream_t s, int apply_adam,
                         const P2pArgs* x, const StepTab* tab);
-// ---- moc_step_tiles.hip: the one-launch step over the forward's tile records.  One meta-learner ...
+// ---- moc_step_tiles.hip: the one-launch step over the forward's tile records.  One meta-learner (S_host: the slide's
+// selected-row count as the forward of this step was given it, host_n_sel; -1: the device's n_sel) ...
 int launch_tile_step(const StepPlan& p, const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws_t* ws, const int64_t* labels,
                      int slide, uint32_t use_bits, const AdamCoef& k, float* W2out, hipStream_t s, int apply_adam,
-                     const StepTab* tab, int next_slide);
+                     const StepTab* tab, int next_slide, int S_host);
 // ... or runs [r0, r0 + nr) of R in one launch (nr <= MOC_MAX_RUNS; per-run coefficients: nr <= MOC_HP_RUNS), each on its
 // slide `slide` + run * slide_stride.  cur / nxt: the W2 buffers of run 0 this step reads / writes, a run's 4 H floats
 // cur_stride / nxt_stride apart.  k: ONE AdamCoef for all runs, or (k_per_run) run r0 + r's at k[r].
@@ -235,10 +236,21 @@ int check_meta(const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws_t* w
 int launch_w1_images(const moc_batch_t* B, const moc_meta_t* M, const moc_runs_t* R, hipStream_t s);
 // the most selected rows a slide of the batch can have
 int s_bound(const moc_batch_t* B);
+// Slide b's selected-row count S as the HOST knows it, or -1: n_sel_host[b] when the caller has seen a copy arrive, else
+// the slide's word of the pinned mailbox compact_kernel writes (moc_batch_t.n_sel_mail) when it carries the expected
+// ticket -- one acquire load, never a wait.  A train step asks ONCE, in front of its two launches, and hands both the
+// answer by value: forward and step agree on it, and nothing reads the mailbox after the launch.
+inline int host_n_sel(const moc_batch_t* B, int b) {
+    if (B->n_sel_host) return B->n_sel_host[b];
+    if (!B->n_sel_mail || B->n_sel_ticket == 0) return -1;
+    const uint64_t w = __atomic_load_n(B->n_sel_mail + b, __ATOMIC_ACQUIRE);
+    return (uint32_t)(w >> 32) == B->n_sel_ticket ? (int)(uint32_t)w : -1;
+}
 // The forward of slides [slide0, slide0 + n) into ws.  emit_tiles (StepPlan::tiles()): the one-launch step over tile records
 // follows (training step of one slide): leave the records.  runs != nullptr: the training forward of runs->n_runs meta-learners in one launch
-// (moc_train_steps_runs), `M->W2` / `w2_stride` = where their current W2 lives.
+// (moc_train_steps_runs), `M->W2` / `w2_stride` = where their current W2 lives.  S_host (one slide, one run): the slide's
+// selected-row count by host_n_sel, -1: not known; the runs read n_sel_host themselves.
 int launch_forward(const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws_t* ws, int slide0, int n, uint32_t use_bits,
-                   hipStream_t s, bool emit_tiles = false, const moc_runs_t* runs = nullptr, int64_t w2_stride = 0);
+                   hipStream_t s, bool emit_tiles = false, const moc_runs_t* runs = nullptr, int64_t w2_stride = 0, int S_host = -1);
 
 }  // namespace moc_meta_internal

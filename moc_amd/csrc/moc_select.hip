@@ -486,6 +486,8 @@ struct CompactArgs {
     int64_t stride;
     int C, row_bytes;
     int compact;                    // MOC_STATS_COMPACT layout of `stats`
+    unsigned long long* n_sel_mail; // nullable: HOST (device-mapped pinned) [n_slides], slide b's count for the train steps
+    uint32_t n_sel_ticket;          // ... under this ticket (moc_batch_t.n_sel_mail)
 };
 
 // candidate score k (0..C-1 s_p, C..2C-1 s_sigma, 2C s_delta, 2C+1 s_beta = MAX background logit: main_moc.py:359-366)
@@ -527,7 +529,14 @@ __global__ __launch_bounds__(1024) void compact_kernel(CompactArgs a) {
         }
         running += tot;
     }
-    if (threadIdx.x == 0) a.n_sel[b] = running;
+    if (threadIdx.x == 0) {
+        a.n_sel[b] = running;
+        // the host's copy, this slide alone and now: ticket and count in ONE naturally aligned 64-bit store, so the host
+        // reads either an older word (another ticket: not valid) or this one whole -- no fence, no counter, no launch
+        if (a.n_sel_mail)
+            __hip_atomic_store(a.n_sel_mail + b, ((unsigned long long)a.n_sel_ticket << 32) | (unsigned)running, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_SYSTEM);
+    }
     if (a.cand_inline) {
         // Few columns (C <= 4): the candidate columns are copied here, no second launch -- as a phase of its own,
         // one selected slot per thread: every load independent of the others and the stores coalesced (inside the
@@ -1098,6 +1107,8 @@ extern "C" int moc_gather_candidates(const moc_batch_t* B, void* selected_feat, 
     a.cand = B->cand; a.X = (const unsigned char*)B->X; a.selected_feat = (unsigned char*)selected_feat;
     a.stride = B->total_rows; a.C = B->C; a.row_bytes = B->D * moc_elem_size(B->dtype);
     a.compact = (B->flags & MOC_STATS_COMPACT) ? 1 : 0;
+    MOC_REQUIRE(((uintptr_t)B->n_sel_mail & 7) == 0, "moc_gather_candidates: n_sel_mail must be 8-byte aligned");
+    a.n_sel_mail = (unsigned long long*)B->n_sel_mail; a.n_sel_ticket = B->n_sel_ticket;
     hipStream_t s = (hipStream_t)stream;
     a.cand_inline = B->C <= 4;
     compact_kernel<<<B->n_slides, 1024, 0, s>>>(a);

@@ -637,26 +637,26 @@ __global__ __launch_bounds__(256, 4) void pool_w1_step_tiles_kernel(ArgsT args) 
 
 // ------------------------------------------------------------------ host side
 // the argument block of pool_w1_step_tiles_kernel for slide `slide` of B (one run)
-void tile_region(const moc_batch_t* B, int slide, int64_t* slot0, int* tcap, int* tb) {
+// sh: the slide's selected-row count where the host knows it (the caller's host_n_sel, or n_sel_host), -1: not known
+void tile_region(const moc_batch_t* B, int slide, int sh, int64_t* slot0, int* tcap, int* tb) {
     const int64_t base = B->row_off_host[slide], seg = B->row_off_host[slide + 1] - base;
     // the slide's region: cap tiles per class; the kernel's loads are issued before n_sel is known and clamped to the
     // tiles the slide can have at all (at most s_bound selected rows)
     *tcap = moc_cdiv(seg, 16) > 0 ? moc_cdiv(seg, 16) : 1;
     int tb_all = moc_cdiv(s_bound(B), 16);
-    if (B->n_sel_host) {                                    // the slide's own tile count: fewer record keys per lane in the step
-        const int sh = B->n_sel_host[slide];
-        if (sh >= 0 && moc_cdiv(sh, 16) < tb_all) tb_all = sh > 0 ? moc_cdiv(sh, 16) : 1;
-    }
+    // the slide's own tile count: fewer record keys per lane in the step
+    if (sh >= 0 && moc_cdiv(sh, 16) < tb_all) tb_all = sh > 0 ? moc_cdiv(sh, 16) : 1;
     *tb = *tcap < tb_all ? *tcap : tb_all;
     *slot0 = ((base >> 4) + slide) * (int64_t)B->C * TILE_R;
 }
 
 TileStepArgs tile_step_args(const StepPlan& p, const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws_t* ws, const int64_t* labels, int slide,
-                            uint32_t use_bits, const AdamCoef& k, float* W2out, int apply_adam, const StepTab* tab) {
+                            uint32_t use_bits, const AdamCoef& k, float* W2out, int apply_adam, const StepTab* tab, int S_host = -1) {
+    if (S_host < 0 && B->n_sel_host) S_host = B->n_sel_host[slide];   // (callers that do not ask host_n_sel themselves)
     const TileWs T = tile_carve(ws->tile_ws, tile_slots(B->total_rows, B->n_slides, B->C));
     TileStepArgs ta = {};
     ta.tkey = T.key; ta.trho = T.rho; ta.trid = T.rid; ta.tlam = T.lam; ta.tsc = T.sc;
-    tile_region(B, slide, &ta.slot0, &ta.cap, &ta.ntile_bound);
+    tile_region(B, slide, S_host, &ta.slot0, &ta.cap, &ta.ntile_bound);
     ta.C = B->C; ta.K = B->topk; ta.D = B->D; ta.slide0 = slide; ta.PS_CAP = p.cap;
     ta.xdt = B->dtype; ta.n_sel = B->n_sel; ta.labels = labels;
     ta.W1 = M->W1; ta.m_W1 = M->m_W1; ta.v_W1 = M->v_W1; ta.W2 = M->W2;
@@ -664,7 +664,7 @@ TileStepArgs tile_step_args(const StepPlan& p, const moc_batch_t* B, const moc_m
     ta.m_W2 = M->m_W2; ta.v_W2 = M->v_W2;
     ta.base = B->row_off_host[slide]; ta.adam = k;
     ta.row_off = B->row_off; ta.prefetch_next = 0;
-    ta.S_host = B->n_sel_host ? B->n_sel_host[slide] : -1;
+    ta.S_host = S_host;
     ta.sink_off = lds::tile_step_lds(B->C, B->topk, p.cap).sink;
     if (tab) { ta.adam_tab = tab->tab; ta.adam_ctr = tab->ctr; ta.adam_pos = tab->pos; }
     ta.apply_adam = apply_adam; ta.use_bits = use_bits; ta.img_dt = B->dtype;
@@ -723,8 +723,8 @@ void moc_meta_internal::tile_step_attrs(raise_lds_fn raise) {
 // next_slide: the slide the step after this one works on, in the same work arrays (-1: none / unknown) -- its rows are prefetched
 int moc_meta_internal::launch_tile_step(const StepPlan& p, const moc_batch_t* B, const moc_meta_t* M, const moc_meta_ws_t* ws,
                                         const int64_t* labels, int slide, uint32_t use_bits, const AdamCoef& k, float* W2out,
-                                        hipStream_t s, int apply_adam, const StepTab* tab, int next_slide) {
-    TileStepArgs ta = tile_step_args(p, B, M, ws, labels, slide, use_bits, k, W2out, apply_adam, tab);
+                                        hipStream_t s, int apply_adam, const StepTab* tab, int next_slide, int S_host) {
+    TileStepArgs ta = tile_step_args(p, B, M, ws, labels, slide, use_bits, k, W2out, apply_adam, tab, S_host);
     if (step_prefetch_on() && next_slide == slide + 1 && next_slide < B->n_slides && B->C < 4) ta.prefetch_next = 1;
     return launch_tile_step_as(p, B, ta, 1, ta.ntile_bound, s);
 }
@@ -757,7 +757,7 @@ void runs_per_run(RunsT& tr, const moc_batch_t* B, const moc_runs_t* R, int slid
         const int sl = slide + (r0 + r) * R->slide_stride;
         tr.base_r[r] = B->row_off_host[sl];
         int cap_, tb_;
-        tile_region(B, sl, &tr.slot0_r[r], &cap_, &tb_);
+        tile_region(B, sl, B->n_sel_host ? B->n_sel_host[sl] : -1, &tr.slot0_r[r], &cap_, &tb_);
         tr.cap_r[r] = cap_; tr.ntb_r[r] = tb_;
     }
 }

@@ -35,7 +35,7 @@ COMPACT_STATS = os.environ.get("MOC_COMPACT_STATS", "1") != "0"     # wide banks
 RESERVE_CUS = int(os.environ.get("MOC_RESERVE_CUS", "64"))
 # the training step pools among the forward's tile records (moc_meta_ws_t.tile_ws; 0: re-reads every mixed score, round 3)
 TILE_RECORDS = os.environ.get("MOC_TILE_RECORDS", "1") != "0"
-N_SEL_HOST = os.environ.get("MOC_N_SEL_HOST", "1") != "0"            # moc_batch_t.n_sel_host for the train steps (0: never, diagnostic)
+N_SEL_HOST = os.environ.get("MOC_N_SEL_HOST", "1") != "0"            # moc_batch_t.n_sel_mail / n_sel_host for the train steps (0: never, diagnostic)
 
 # bench.py sets this to a list: every batched score-pass launch then appends
 # (start_event, stop_event, algorithmic_bytes) recorded on the launch stream.
@@ -323,12 +323,15 @@ class SlideBatch:
         self.cu_reserved = None
         self._ws = None
         self.stats_cache = None          # (statistics of every row of X, layout flag): phase A copies instead of reading the bags
-        # moc_batch_t.n_sel_host: a pinned copy of n_sel requested behind every phase A, handed to the train steps once its
-        # event has completed (the look-ahead phase A of a pass ended long before the pass's steps are issued) -- the forward
-        # then takes a slide's S as an argument instead of loading it, launches exactly the workgroups that have rows, and
-        # the step reads fewer record keys per lane.  Masked (training) batches only.
-        self._n_sel_pin = torch.empty(n, dtype=torch.int32).pin_memory() if (N_SEL_HOST and mask is not None) else None
-        self._n_sel_ev = None
+        # moc_batch_t.n_sel_mail: a pinned mailbox of one 64-bit word per slide, (ticket << 32) | S, which compact_kernel's
+        # workgroup of the slide stores beside n_sel[b]; the C step loop reads slide b's word in front of step b's two
+        # launches -- where it carries this batch's current ticket the forward takes S as an argument instead of loading
+        # it, launches exactly the workgroups that have rows, and the step reads fewer record keys per lane; where it has
+        # not arrived the step runs on the device count.  Every phase A takes a fresh ticket (_n_sel_stale), so the words
+        # of an earlier one never pass.  Masked (training) batches only.  The mailbox lives as long as the batch.
+        self._n_sel_mail = torch.zeros(n, dtype=torch.int64).pin_memory() if (N_SEL_HOST and mask is not None) else None
+        self._n_sel_ticket = 0
+        self._n_sel_pin = self._n_sel_ev = None    # (the batched runs' copy of all counts at once: _n_sel_request)
 
     def reserve_cus(self, n: int | None = None, ticket: bool | None = None):
         """This batch's score passes stay off `n` compute units (default MOC_RESERVE_CUS) and hand their tiles out by
@@ -390,24 +393,33 @@ class SlideBatch:
         self._n_sel_stale()
         if SCORE_EVENTS is None and self.stats_cache is None:
             check(lib().moc_phase_a(C.byref(self.c), ptr(bank.image), _stream()), "moc_phase_a")
-            self._n_sel_request()
             return
         # same four launches, with events around the score pass
         check(lib().moc_mask_compact(C.byref(self.c), _stream()), "moc_mask_compact")
         self.phase_a_tail(bank)
 
-    _n_sel_pin = None                   # (class defaults: CompactBatch builds its own fields)
+    _n_sel_mail = None                  # (class defaults: CompactBatch builds its own fields)
+    _n_sel_ticket = 0
+    _n_sel_pin = None
     _n_sel_ev = None
 
     def _n_sel_stale(self):
-        """n_sel is about to be rewritten: the host copy no longer describes it."""
+        """n_sel is about to be rewritten: no host copy describes it any more, and the mailbox words of the launch that
+        rewrites it travel under a fresh ticket (from 1; 0, "none", is skipped on wrap)."""
         self.c.n_sel_host = None
         self._n_sel_ev = None
+        if self._n_sel_mail is None:
+            return
+        self._n_sel_ticket = (self._n_sel_ticket + 1) & 0xFFFFFFFF or 1
+        self.c.n_sel_mail, self.c.n_sel_ticket = ptr(self._n_sel_mail), self._n_sel_ticket
 
     def _n_sel_request(self):
-        """Behind the launches that write n_sel, on their stream: the asynchronous copy into the pinned buffer and its event."""
-        if self._n_sel_pin is None:
+        """The batched runs (moc_amd.runs), whose lockstep launches want every run's count or none: behind the launches that
+        write n_sel, on their stream, the asynchronous copy of all counts into a pinned buffer and its event."""
+        if self._n_sel_mail is None:
             return
+        if self._n_sel_pin is None:
+            self._n_sel_pin = torch.empty(self.n_slides, dtype=torch.int32).pin_memory()
         self.c.n_sel_host = None
         self._n_sel_pin.copy_(self.n_sel, non_blocking=True)
         ev = torch.cuda.Event()
@@ -415,11 +427,15 @@ class SlideBatch:
         self._n_sel_ev = ev
 
     def publish_n_sel(self, allow: bool = True):
-        """Called in front of the train steps: moc_batch_t.n_sel_host = the pinned copy when its event has completed (never
-        waited for), else NULL."""
+        """Called in front of the train steps: hands them the mailbox and the ticket its words must carry (allow), or
+        nothing at all; -> whether there is a mailbox to hand over.  No event is queried or waited for: the C step loop looks at
+        a slide's word when it issues that slide's step (and waits for the first one's, MOC_N_SEL_SPIN_US at the most).
+        (A copy of all counts that _n_sel_request has queued is handed over as moc_batch_t.n_sel_host once its event has
+        completed.)"""
         ev = self._n_sel_ev
-        ok = allow and ev is not None and ev.query()
-        self.c.n_sel_host = ptr(self._n_sel_pin) if ok else None
+        self.c.n_sel_host = ptr(self._n_sel_pin) if (allow and ev is not None and ev.query()) else None
+        ok = allow and self._n_sel_mail is not None
+        self.c.n_sel_mail, self.c.n_sel_ticket = (ptr(self._n_sel_mail), self._n_sel_ticket) if ok else (None, 0)
         return ok
 
     def phase_a_head(self, bank: Bank):
@@ -446,7 +462,6 @@ class SlideBatch:
         self._n_sel_stale()
         self.select()
         self.gather_candidates()
-        self._n_sel_request()
 
     def scores(self, bank: Bank):
         self._layout(False)                      # callers of scores() read `stats` themselves: the full layout
@@ -575,6 +590,7 @@ class BankView(SlideBatch):
         self.c.stats, self.c.sel_flag, self.c.sel_idx = ptr(self.stats), ptr(self.sel_flag), ptr(self.sel_idx)
         self.c.sel_row, self.c.n_sel, self.c.cand = ptr(self.sel_row), ptr(self.n_sel), ptr(self.cand)
         self.c.n_sel_host = None
+        self.c.n_sel_mail, self.c.n_sel_ticket = None, 0      # (the parent's mailbox holds the PARENT's counts)
         self.ticket = self.cu_reserved = None
         self._ws = None
         self.stats_cache = None

@@ -397,6 +397,8 @@ class TrainRuns:
             v.n_kept = c.n_kept + 4 * slide0
         v.n_sel = c.n_sel + 4 * slide0
         v.n_sel_host = None
+        if c.n_sel_mail:                                       # (a per-slide array too: the view's slide 0 is word slide0)
+            v.n_sel_mail = c.n_sel_mail + 8 * slide0
         return v
 
     def _workspace_slabs(self, batch, topks):
@@ -493,6 +495,7 @@ class TrainRuns:
                 batch.phase_a_head(self.bank)
             else:
                 batch.phase_a(self.bank)
+                batch._n_sel_request()                         # (the lockstep launches take all counts or none: the copy)
         else:
             # head: the leaders' kept-row lists (a launch per block of consecutive leader runs)
             bank = self.bank
@@ -519,6 +522,7 @@ class TrainRuns:
         self.trained_phase_a = info["report"]
         if info["plain"]:
             batch.phase_a_tail(self.bank)
+            batch._n_sel_request()
             return
         leader, st = info["leader"], engine._stream()
         if self.bank_set is not None:
