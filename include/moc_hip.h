@@ -595,6 +595,34 @@ int moc_nystrom_token_values(const float* qkv, int64_t n_pad, int heads, int dim
                              const float* k_l, const float* Y, const float* conv_w /* [h, taps] or NULL */, int taps,
                              float scale, float* out /* [n_pad, h*d] */, moc_stream_t stream);
 
+/* The backward of those two products, for training on them (moc_amd/nystrom.py: LandmarkValues, TokenValues).  The softmax
+ * weights are recomputed tile by tile from the operands and one statistic per row; nothing of size n_pad x 256 is written.
+ *   moc_nystrom_landmark_values_lse: moc_nystrom_landmark_values (the same two launches, the same bits in W) which also
+ *       stores lse[h, m] = log sum_tokens exp(q_l[h, m] . k[h, token]), [8, 256].
+ *   moc_nystrom_landmark_backward:   given dW [8, 256, 64]: dqkv's k and v columns (dk = dS^T q_l, dv = P^T dW with
+ *       P = exp(S - lse), dS = P (dW v^T - dW . W)) and dq_l = dS k [8, 256, 64]; dqkv's q columns are written as zeros.
+ *   moc_nystrom_token_backward:      the token product WITHOUT the residual convolution; given dout [n_pad, 512]: dqkv's q
+ *       columns (scale dS k_l), dk_l = dS^T (scale q) and dY = P^T dout, both [8, 256, 64]; dqkv's k and v columns are
+ *       written as zeros.
+ * Each backward entry writes every element of its dqkv [n_pad, 1536].  `ws`: moc_nystrom_backward_workspace bytes, one size
+ * for either backward entry (per-token statistics and the partial sums of each 512-token range, merged in index order: no
+ * atomics, the same bits on every call), less than one [8, n_pad, 256] fp32 score matrix for every valid n_pad; the _lse
+ * entry takes moc_nystrom_workspace bytes like the entry it extends.  MOC_EUNSUPPORTED for another shape; MOC_EINVAL for
+ * a null or not 16-byte aligned pointer, a bad n_pad, a short workspace, a non-finite scale -- all before the first launch.
+ * Additive to ABI 20: the version number is unchanged. */
+size_t moc_nystrom_backward_workspace(int64_t n_pad, int heads, int dim_head, int landmarks);   /* 0: unsupported shape */
+int moc_nystrom_landmark_values_lse(const float* qkv, int64_t n_pad, int heads, int dim_head, int landmarks,
+                                    const float* q_l, float* W, float* lse /* [h, m] */, void* ws, size_t ws_bytes,
+                                    moc_stream_t stream);
+int moc_nystrom_landmark_backward(const float* qkv, int64_t n_pad, int heads, int dim_head, int landmarks,
+                                  const float* q_l, const float* W, const float* lse, const float* dW,
+                                  float* dqkv /* [n_pad, 3*h*d] */, float* dq_l /* [h, m, d] */,
+                                  void* ws, size_t ws_bytes, moc_stream_t stream);
+int moc_nystrom_token_backward(const float* qkv, int64_t n_pad, int heads, int dim_head, int landmarks,
+                               const float* k_l, const float* Y, float scale, const float* dout /* [n_pad, h*d] */,
+                               float* dqkv /* [n_pad, 3*h*d] */, float* dk_l, float* dY,
+                               void* ws, size_t ws_bytes, moc_stream_t stream);
+
 /* The same layer's landmark pseudo-inverse (moc_amd/nystrom.py: moore_penrose_iter_pinv) as a chain of fp32 products on
  * the whole chip, for heads = 8 and landmarks = 256 only.  A = attn2 [8, 256, 256] device fp32, never written:
  *   c = max over all heads and rows of sum_j |A[h, i, j]|, r = likewise of the column sums;  Z0 = A^T / (c r)

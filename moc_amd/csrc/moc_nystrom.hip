@@ -28,40 +28,15 @@
 // lanes read consecutive 16 bytes); each of eight waves takes two 16-token tiles: 256 landmark scores per token in
 // registers, one softmax, the product with Y, then the residual convolution as 12 more MFMA steps over the 48 rows of v
 // around the tile against the banded tap matrix T[i', i] = w[i' - i + taps / 2] (rows outside [0, n_pad) count as zero).
-#include "moc_common.h"
-#include <cmath>
+#include "moc_nystrom_shared.h"
 
 namespace {
 
-constexpr int NY_HEADS = 8, NY_D = 64, NY_M = 256, NY_MAX_TAPS = 33;
-constexpr int NY_ROW = 3 * NY_HEADS * NY_D;              // 1536 floats per token of qkv
-constexpr int NY_OUT = NY_HEADS * NY_D;                  // 512 floats per token of out
-constexpr int NY_CHUNK = 512;                            // tokens per partial range of kernel A
 constexpr int NY_A_LT = 2;                               // 16-landmark tiles per wave of kernel A: eight waves, two per SIMD
 constexpr int NY_A_THREADS = NY_M / (16 * NY_A_LT) * 64;
-constexpr int NY_B_TOK = 256;                            // tokens per workgroup of kernel B
-constexpr int64_t NY_MAX_N = (int64_t)1 << 22;
 constexpr int NY_B_SMEM = 2 * NY_M * NY_D * 4 + 64 * 4;  // k_l image, Y image, tap table
 
-int64_t ny_chunks(int64_t n_pad) { return (n_pad + NY_CHUNK - 1) / NY_CHUNK; }
 size_t ny_ws_bytes(int64_t n_pad) { return (size_t)ny_chunks(n_pad) * NY_HEADS * NY_M * (NY_D + 2) * sizeof(float); }
-bool ny_shape_ok(int64_t n_pad, int heads, int dim_head, int landmarks) {
-    return heads == NY_HEADS && dim_head == NY_D && landmarks == NY_M && n_pad >= NY_M && n_pad % NY_M == 0 && n_pad <= NY_MAX_N;
-}
-
-__device__ __forceinline__ f32x4_t ny_mfma(float a, float b, f32x4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ float4 ny_ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ float ny_col_max(float v) {                 // over the four lanes that share a column
-    v = fmaxf(v, __shfl_xor(v, 16, 64));
-    return fmaxf(v, __shfl_xor(v, 32, 64));
-}
-__device__ __forceinline__ float ny_col_sum(float v) {
-    v += __shfl_xor(v, 16, 64);
-    v += __shfl_xor(v, 32, 64);
-    return v;
-}
 
 struct NyAArgs {
     const float* qkv;      // [n_pad, 1536]
@@ -170,8 +145,9 @@ __global__ __launch_bounds__(NY_A_THREADS) void nystrom_landmark_kernel(NyAArgs 
     }
 }
 
-// one thread per (head, landmark, four features): the ranges in index order
-__global__ __launch_bounds__(256) void nystrom_merge_kernel(const float* part, int chunks, float* W) {
+// one thread per (head, landmark, four features): the ranges in index order; `lse` (or null) takes each landmark's
+// log-sum-exp over the tokens, m + log(den), which the backward recomputes the weights from
+__global__ __launch_bounds__(256) void nystrom_merge_kernel(const float* part, int chunks, float* W, float* lse) {
     const int idx = blockIdx.x * 256 + threadIdx.x;                   // < 8 * 256 * 16
     const int d4 = idx & 15, lm = (idx >> 4) & (NY_M - 1), h = idx >> 12;
     const float* pmx = part + (int64_t)NY_HEADS * chunks * NY_M * NY_D;
@@ -189,6 +165,7 @@ __global__ __launch_bounds__(256) void nystrom_merge_kernel(const float* part, i
     }
     *reinterpret_cast<float4*>(W + ((int64_t)h * NY_M + lm) * NY_D + 4 * d4) =
         float4{num.x / den, num.y / den, num.z / den, num.w / den};
+    if (lse && d4 == 0) lse[h * NY_M + lm] = m + logf(den);
 }
 
 struct NyBArgs {
@@ -312,17 +289,28 @@ __global__ __launch_bounds__(512) void nystrom_token_kernel(NyBArgs a) {
     }
 }
 
-int ny_check_shape(const char* fn, int64_t n_pad, int heads, int dim_head, int landmarks) {
-    if (heads != NY_HEADS || dim_head != NY_D || landmarks != NY_M)
-        MOC_FAIL(MOC_EUNSUPPORTED, "%s: heads=%d dim_head=%d landmarks=%d, only 8 x 64 with 256 landmarks is built", fn, heads,
-                 dim_head, landmarks);
-    MOC_REQUIRE(n_pad >= landmarks && n_pad % landmarks == 0, "%s: n_pad=%lld must be a positive multiple of landmarks=%d", fn,
-                (long long)n_pad, landmarks);
-    if (n_pad > NY_MAX_N) MOC_FAIL(MOC_EUNSUPPORTED, "%s: n_pad=%lld above %lld", fn, (long long)n_pad, (long long)NY_MAX_N);
+// both landmark-side entries: `lse` is null for the one that keeps no statistics
+int ny_landmark_values(const char* fn, const float* qkv, int64_t n_pad, int heads, int dim_head, int landmarks, const float* q_l,
+                       float* W, float* lse, bool want_lse, void* ws, size_t ws_bytes, moc_stream_t stream) {
+    MOC_REQUIRE(qkv, "%s: qkv is null", fn);
+    MOC_REQUIRE(q_l, "%s: q_l is null", fn);
+    MOC_REQUIRE(W, "%s: W is null", fn);
+    MOC_REQUIRE(lse || !want_lse, "%s: lse is null", fn);
+    MOC_REQUIRE(ws, "%s: ws is null", fn);
+    if (const int rc = ny_check_shape(fn, n_pad, heads, dim_head, landmarks)) return rc;
+    MOC_REQUIRE(ny_aligned(qkv) && ny_aligned(q_l) && ny_aligned(W) && ny_aligned(ws),
+                "%s: qkv, q_l, W and ws must be 16-byte aligned", fn);
+    MOC_REQUIRE(ny_aligned(lse), "%s: lse must be 16-byte aligned", fn);
+    MOC_REQUIRE(ws_bytes >= ny_ws_bytes(n_pad), "%s: ws_bytes=%zu, need %zu", fn, ws_bytes, ny_ws_bytes(n_pad));
+    hipStream_t s = (hipStream_t)stream;
+    NyAArgs a;
+    a.qkv = qkv; a.q_l = q_l; a.part = (float*)ws; a.n_pad = n_pad; a.chunks = (int)ny_chunks(n_pad);
+    nystrom_landmark_kernel<<<dim3(a.chunks, NY_HEADS), NY_A_THREADS, 0, s>>>(a);
+    MOC_CHECK_LAUNCH(fn);
+    nystrom_merge_kernel<<<NY_HEADS * NY_M * (NY_D / 4) / 256, 256, 0, s>>>((const float*)ws, a.chunks, W, lse);
+    MOC_CHECK_LAUNCH(fn);
     return MOC_OK;
 }
-
-bool ny_aligned(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
@@ -332,22 +320,15 @@ extern "C" size_t moc_nystrom_workspace(int64_t n_pad, int heads, int dim_head, 
 
 extern "C" int moc_nystrom_landmark_values(const float* qkv, int64_t n_pad, int heads, int dim_head, int landmarks,
                                            const float* q_l, float* W, void* ws, size_t ws_bytes, moc_stream_t stream) {
-    MOC_REQUIRE(qkv, "moc_nystrom_landmark_values: qkv is null");
-    MOC_REQUIRE(q_l, "moc_nystrom_landmark_values: q_l is null");
-    MOC_REQUIRE(W, "moc_nystrom_landmark_values: W is null");
-    MOC_REQUIRE(ws, "moc_nystrom_landmark_values: ws is null");
-    if (const int rc = ny_check_shape("moc_nystrom_landmark_values", n_pad, heads, dim_head, landmarks)) return rc;
-    MOC_REQUIRE(ny_aligned(qkv) && ny_aligned(q_l) && ny_aligned(W) && ny_aligned(ws),
-                "moc_nystrom_landmark_values: qkv, q_l, W and ws must be 16-byte aligned");
-    MOC_REQUIRE(ws_bytes >= ny_ws_bytes(n_pad), "moc_nystrom_landmark_values: ws_bytes=%zu, need %zu", ws_bytes, ny_ws_bytes(n_pad));
-    hipStream_t s = (hipStream_t)stream;
-    NyAArgs a;
-    a.qkv = qkv; a.q_l = q_l; a.part = (float*)ws; a.n_pad = n_pad; a.chunks = (int)ny_chunks(n_pad);
-    nystrom_landmark_kernel<<<dim3(a.chunks, NY_HEADS), NY_A_THREADS, 0, s>>>(a);
-    MOC_CHECK_LAUNCH("moc_nystrom_landmark_values");
-    nystrom_merge_kernel<<<NY_HEADS * NY_M * (NY_D / 4) / 256, 256, 0, s>>>((const float*)ws, a.chunks, W);
-    MOC_CHECK_LAUNCH("moc_nystrom_landmark_values(merge)");
-    return MOC_OK;
+    return ny_landmark_values("moc_nystrom_landmark_values", qkv, n_pad, heads, dim_head, landmarks, q_l, W, nullptr, false, ws,
+                              ws_bytes, stream);
+}
+
+extern "C" int moc_nystrom_landmark_values_lse(const float* qkv, int64_t n_pad, int heads, int dim_head, int landmarks,
+                                               const float* q_l, float* W, float* lse, void* ws, size_t ws_bytes,
+                                               moc_stream_t stream) {
+    return ny_landmark_values("moc_nystrom_landmark_values_lse", qkv, n_pad, heads, dim_head, landmarks, q_l, W, lse, true, ws,
+                              ws_bytes, stream);
 }
 
 extern "C" int moc_nystrom_token_values(const float* qkv, int64_t n_pad, int heads, int dim_head, int landmarks,

@@ -1382,6 +1382,62 @@ def nystrom_token_values(qkv: torch.Tensor, k_l: torch.Tensor, Y: torch.Tensor, 
     return out
 
 
+def nystrom_landmark_values_lse(qkv: torch.Tensor, q_l: torch.Tensor):
+    """nystrom_landmark_values that also returns the per-landmark log-sum-exp over the tokens, [8, 256], from which the
+    backward recomputes the weights (moc_nystrom_landmark_values_lse): (W, lse), W bit for bit the other entry's."""
+    what = "nystrom_landmark_values_lse"
+    n_pad = _nystrom_qkv(qkv, what)
+    q_l = _nystrom_hmd(q_l, "q_l", what)
+    W = torch.empty_like(q_l)
+    lse = torch.empty((NYSTROM_HEADS, NYSTROM_LANDMARKS), dtype=torch.float32, device=qkv.device)
+    nbytes = lib().moc_nystrom_workspace(n_pad, NYSTROM_HEADS, NYSTROM_DIM_HEAD, NYSTROM_LANDMARKS)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=qkv.device)
+    check(lib().moc_nystrom_landmark_values_lse(ptr(qkv.detach()), n_pad, NYSTROM_HEADS, NYSTROM_DIM_HEAD, NYSTROM_LANDMARKS,
+                                                ptr(q_l), ptr(W), ptr(lse), ptr(ws), nbytes, _stream()),
+          "moc_nystrom_landmark_values_lse")
+    return W, lse
+
+
+def _nystrom_backward_ws(n_pad: int, device):
+    nbytes = lib().moc_nystrom_backward_workspace(n_pad, NYSTROM_HEADS, NYSTROM_DIM_HEAD, NYSTROM_LANDMARKS)
+    return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device), nbytes
+
+
+def nystrom_landmark_backward(qkv: torch.Tensor, q_l: torch.Tensor, W: torch.Tensor, lse: torch.Tensor, dW: torch.Tensor):
+    """Backward of nystrom_landmark_values_lse (moc_nystrom_landmark_backward): (dqkv [n_pad, 1536], dq_l [8, 256, 64]) from
+    its inputs, its two results and dW [8, 256, 64].  dqkv holds dk and dv and exact zeros in the q columns.  The weights are
+    recomputed from lse; no score matrix is formed."""
+    what = "nystrom_landmark_backward"
+    n_pad = _nystrom_qkv(qkv, what)
+    q_l, W, dW = _nystrom_hmd(q_l, "q_l", what), _nystrom_hmd(W, "W", what), _nystrom_hmd(dW, "dW", what)
+    assert lse.is_cuda and lse.dtype == torch.float32, f"{what}: fp32 tensors on the GPU (no CPU fallback)"
+    assert lse.shape == (NYSTROM_HEADS, NYSTROM_LANDMARKS), f"{what}: lse must be [8, 256]"
+    lse = lse.detach().contiguous()
+    dqkv, dq_l = torch.empty_like(qkv, requires_grad=False), torch.empty_like(q_l)
+    ws, nbytes = _nystrom_backward_ws(n_pad, qkv.device)
+    check(lib().moc_nystrom_landmark_backward(ptr(qkv.detach()), n_pad, NYSTROM_HEADS, NYSTROM_DIM_HEAD, NYSTROM_LANDMARKS,
+                                              ptr(q_l), ptr(W), ptr(lse), ptr(dW), ptr(dqkv), ptr(dq_l), ptr(ws), nbytes,
+                                              _stream()), "moc_nystrom_landmark_backward")
+    return dqkv, dq_l
+
+
+def nystrom_token_backward(qkv: torch.Tensor, k_l: torch.Tensor, Y: torch.Tensor, scale: float, dout: torch.Tensor):
+    """Backward of nystrom_token_values without a residual (moc_nystrom_token_backward): (dqkv [n_pad, 1536], dk_l, dY
+    [8, 256, 64]) from its inputs and dout [n_pad, 512].  dqkv holds dq and exact zeros in the k and v columns."""
+    what = "nystrom_token_backward"
+    n_pad = _nystrom_qkv(qkv, what)
+    k_l, Y = _nystrom_hmd(k_l, "k_l", what), _nystrom_hmd(Y, "Y", what)
+    assert dout.is_cuda and dout.dtype == torch.float32, f"{what}: fp32 tensors on the GPU (no CPU fallback)"
+    assert dout.shape == (n_pad, NYSTROM_HEADS * NYSTROM_DIM_HEAD), f"{what}: dout must be [n_pad, 512]"
+    dout = dout.detach().contiguous()
+    dqkv, dk_l, dY = torch.empty_like(qkv, requires_grad=False), torch.empty_like(k_l), torch.empty_like(Y)
+    ws, nbytes = _nystrom_backward_ws(n_pad, qkv.device)
+    check(lib().moc_nystrom_token_backward(ptr(qkv.detach()), n_pad, NYSTROM_HEADS, NYSTROM_DIM_HEAD, NYSTROM_LANDMARKS,
+                                           ptr(k_l), ptr(Y), C.c_float(float(scale)), ptr(dout), ptr(dqkv), ptr(dk_l), ptr(dY),
+                                           ptr(ws), nbytes, _stream()), "moc_nystrom_token_backward")
+    return dqkv, dk_l, dY
+
+
 def nystrom_pinv(attn2: torch.Tensor, iters: int) -> torch.Tensor:
     """The landmark pseudo-inverse of the fused Nystrom forward (moc_nystrom_pinv): nystrom.moore_penrose_iter_pinv of
     attn2 [8, 256, 256] -- Z0 = attn2^T / (max row sum x max column sum of |attn2| over all heads), then `iters` times

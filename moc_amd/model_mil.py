@@ -5,7 +5,9 @@ picking the top instance over the N patches runs on the HIP path (pool_autograd)
 through the picked row only, as in the reference.  Parameter names match (`classifier.{0,2}` /
 `fc.0`, `classifiers.{c}`), so reference checkpoints load.  TransMIL (plain torch + the restated Nystrom attention of
 moc_amd/nystrom.py; parity unpinned: the reference's own class cannot be built without the absent third-party
-package) keeps the contract (logits, Y_prob, Y_hat, None, None)."""
+package) keeps the contract (logits, Y_prob, Y_hat, None, None); its switches `fused`, `fused_pinv` and `fused_train`
+(all off by default) put its two attention layers on the HIP kernels of moc_nystrom*.hip -- the no-grad passes, their
+pseudo-inverse, and the passes that want a gradient."""
 from __future__ import annotations
 
 import numpy as np
@@ -166,6 +168,16 @@ class TransMIL(nn.Module):
     @fused_pinv.setter
     def fused_pinv(self, on: bool):
         self.layer1.attn.fused_pinv = self.layer2.attn.fused_pinv = bool(on)
+
+    @property
+    def fused_train(self) -> bool:
+        """Both layers' attention on the fused products in passes that want a gradient too, with the backward of
+        moc_nystrom_bwd.hip (nystrom.NystromAttention.fused_train); acts only together with `fused`."""
+        return bool(self.layer1.attn.fused_train and self.layer2.attn.fused_train)
+
+    @fused_train.setter
+    def fused_train(self, on: bool):
+        self.layer1.attn.fused_train = self.layer2.attn.fused_train = bool(on)
 
     def _tokens(self, data):
         """fc1, wrap-around padding to a square, class token, layer 1, PPEG, layer 2 (:236-266)."""

@@ -13,7 +13,9 @@ and padding (tests/test_baselines_cpu.py).  Plain torch operations: this is a si
 f3); with `fused = True` the no-grad forward runs on the kernels of csrc/moc_nystrom.hip instead, which are checked
 against THIS restatement (tests/test_gpu_nystrom.py) and pin nothing more than it does; `fused_pinv = True` on top of it
 takes the pseudo-inverse from csrc/moc_nystrom_pinv.hip, checked against moore_penrose_iter_pinv below
-(tests/test_gpu_nystrom_pinv.py)."""
+(tests/test_gpu_nystrom_pinv.py); `fused_train = True` on top of `fused` lets the passes that want a gradient run on the same
+two products too, through LandmarkValues / TokenValues below, whose backward is csrc/moc_nystrom_bwd.hip, checked against
+float64 autograd of THIS restatement (tests/test_gpu_nystrom_train.py)."""
 from __future__ import annotations
 
 from math import ceil
@@ -33,6 +35,47 @@ def moore_penrose_iter_pinv(x: torch.Tensor, iters: int = 6) -> torch.Tensor:
         xz = x @ z
         z = 0.25 * z @ (13 * eye - (xz @ (15 * eye - (xz @ (7 * eye - xz)))))
     return z
+
+
+class LandmarkValues(torch.autograd.Function):
+    """W = softmax_over_tokens(q_l k^T) v per head on kernel A, from qkv [n_pad, 1536] and the scaled landmark queries q_l
+    [8, 256, 64]; the forward keeps the per-landmark log-sum-exp, from which the backward (moc_nystrom_landmark_backward)
+    recomputes the weights tile by tile.  The qkv gradient has dk and dv and zeros in the q columns."""
+
+    @staticmethod
+    def forward(ctx, qkv, q_l):
+        from . import engine
+        W, lse = engine.nystrom_landmark_values_lse(qkv, q_l)
+        ctx.save_for_backward(qkv, q_l, W, lse)
+        return W
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dW):
+        from . import engine
+        qkv, q_l, W, lse = ctx.saved_tensors
+        return engine.nystrom_landmark_backward(qkv, q_l, W, lse, dW)
+
+
+class TokenValues(torch.autograd.Function):
+    """out = softmax_256(scale q k_l^T) Y per head and token on kernel B WITHOUT its residual convolution, [n_pad, 512];
+    the backward (moc_nystrom_token_backward) recomputes the weights.  The qkv gradient has dq and zeros in the k and v
+    columns."""
+
+    @staticmethod
+    def forward(ctx, qkv, k_l, Y, scale):
+        from . import engine
+        ctx.save_for_backward(qkv, k_l, Y)
+        ctx.scale = scale
+        return engine.nystrom_token_values(qkv, k_l, Y, None, scale)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        from . import engine
+        qkv, k_l, Y = ctx.saved_tensors
+        dqkv, dk_l, dY = engine.nystrom_token_backward(qkv, k_l, Y, ctx.scale, dout)
+        return dqkv, dk_l, dY, None
 
 
 class NystromAttention(nn.Module):
@@ -55,17 +98,24 @@ class NystromAttention(nn.Module):
     # True: forward_fused, where its kernels apply, takes the pseudo-inverse from engine.nystrom_pinv (moc_nystrom_pinv.hip)
     # instead of moore_penrose_iter_pinv; no effect on any call that runs the torch code
     fused_pinv = False
+    # True: forward_fused, where its kernels apply but for a wanted gradient, keeps the two products on the kernels and
+    # takes their gradient from moc_nystrom_bwd.hip (_forward_fused_train); no effect without `fused`, nor under no_grad
+    fused_train = False
 
     def forward(self, x, mask=None, return_attn=False):
         if self.fused:
             return self.forward_fused(x, mask=mask, return_attn=return_attn)
         return self._forward_torch(x, mask=mask, return_attn=return_attn)
 
+    def _wants_grad(self, x) -> bool:
+        return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
+
     def _fused_applies(self, x, mask, return_attn) -> bool:
+        return not self._wants_grad(x) and self._kernels_apply(x, mask, return_attn)   # the forward kernels form no gradient
+
+    def _kernels_apply(self, x, mask, return_attn) -> bool:
         if mask is not None or return_attn:
             return False
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            return False                                  # the kernels form no gradient
         if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.shape[0] == 1 and x.shape[1] >= 1
                 and x.is_contiguous()):
             return False
@@ -79,7 +129,10 @@ class NystromAttention(nn.Module):
         pseudo-inverse in torch (the pseudo-inverse on moc_nystrom_pinv with `fused_pinv`); W = softmax(q_l k^T) v (kernel A); Y = pinv W; softmax(q k_l^T) Y + res_conv(v) (kernel
         B); to_out.  Neither [8, n, 256] score matrix is formed.  Wherever the kernels do not apply -- a gradient is
         wanted, x is not a contiguous fp32 [1, n, dim] CUDA tensor, another layer shape, mask / return_attn -- this is
-        the torch code above, bit for bit."""
+        the torch code above, bit for bit; with `fused_train`, a call that fails ONLY for the wanted gradient is
+        _forward_fused_train."""
+        if self.fused_train and self._wants_grad(x) and self._kernels_apply(x, mask, return_attn):
+            return self._forward_fused_train(x)
         if not self._fused_applies(x, mask, return_attn):
             return self._forward_torch(x, mask=mask, return_attn=return_attn)
         from . import engine
@@ -101,6 +154,30 @@ class NystromAttention(nn.Module):
         W =engine.nystrom_landmark_values(qkv, q_l)      # softmax over the tokens of q_l k^T, times v
         conv_w = self.res_conv.weight.reshape(h, -1) if self.residual else None
         out = engine.nystrom_token_values(qkv, k_l, pinv @ W, conv_w, self.scale)
+        return self.to_out(out.unsqueeze(0))[:, -n:]
+
+    def _forward_fused_train(self, x):
+        """forward_fused's dataflow with autograd kept ("training"): to_qkv, the landmark means, attn2
+        and its pseudo-inverse are tracked torch operations; W = LandmarkValues(qkv, q_l); Y = pinv W in torch;
+        TokenValues(qkv, k_l, Y) without the residual; then res_conv(v), to_out and the slice in torch.  Neither [8, n, 256]
+        score matrix is formed or kept: both backward kernels recompute their weights.  The pseudo-inverse is ALWAYS
+        moore_penrose_iter_pinv here -- `fused_pinv` is ignored, its kernel forms no gradient -- and the residual
+        convolution and its two gradients stay on torch."""
+        n, h, m = x.shape[1], self.heads, self.num_landmarks
+        if n % m > 0:
+            x = F.pad(x, (0, 0, m - (n % m), 0), value=0)
+        qkv = self.to_qkv(x)[0]                           # [n_pad, 1536]
+        n_pad, inner = qkv.shape[0], qkv.shape[1] // 3
+        means = qkv[:, :2 * inner].reshape(m, n_pad // m, 2 * inner).sum(dim=1) / (n_pad // m)
+        q_l = (means[:, :inner] * self.scale).reshape(m, h, -1).transpose(0, 1).contiguous()                        # h m d
+        k_l = means[:, inner:].reshape(m, h, -1).transpose(0, 1).contiguous()
+        attn2 = (q_l @ k_l.transpose(-1, -2)).softmax(dim=-1)
+        pinv = moore_penrose_iter_pinv(attn2.unsqueeze(0), self.pinv_iterations)[0]
+        W = LandmarkValues.apply(qkv, q_l)
+        out = TokenValues.apply(qkv, k_l, pinv @ W, self.scale)                       # [n_pad, 512]
+        if self.residual:
+            v = qkv[:, 2 * inner:].reshape(1, n_pad, h, -1).transpose(1, 2)         # [1, 8, n_pad, 64], a view
+            out = out + self.res_conv(v).transpose(1, 2).reshape(n_pad, inner)
         return self.to_out(out.unsqueeze(0))[:, -n:]
 
     def _forward_torch(self, x, mask=None, return_attn=False):

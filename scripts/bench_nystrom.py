@@ -8,7 +8,12 @@ moore_penrose_iter_pinv on the same attn2.
 Each figure is the median and the minimum of `--iters` single runs, each between two events, after `--warmup` untimed
 runs.  "faster" is claimed only where a median is below the minimum of the path it is compared with.
 
-    python scripts/bench_nystrom.py [--n 15000] [--iters 30] [--json out.json]
+With --train: forward + backward of one attention layer and of the whole model on the same bag, the torch path (autograd
+keeps both [8, n, 256] score matrices and their softmax outputs) against `fused` + `fused_train` (LandmarkValues /
+TokenValues: the backward of moc_nystrom_bwd.hip recomputes the weights), timed the same way, each with the peak of
+torch.cuda.max_memory_allocated over one step, above what was allocated before it.
+
+    python scripts/bench_nystrom.py [--n 15000] [--iters 30] [--json out.json] [--train]
     rocprofv3 --kernel-trace --stats ... -- python scripts/bench_nystrom.py --trace-layers 8
 """
 import argparse
@@ -77,8 +82,76 @@ def kernel(label, fn, nbytes, flops, iters, warmup):
     return r
 
 
+def train_pair(label, step, switch, iters, warmup):
+    """step() -- one forward + backward -- timed and its peak memory taken on the torch path and with `fused_train`."""
+    r = {}
+    for key, on in (("torch", False), ("fused_train", True)):
+        switch(on)
+        r[key] = times_us(step, iters, warmup)
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        step()
+        torch.cuda.synchronize()
+        r[key]["peak_bytes"] = torch.cuda.max_memory_allocated() - base
+    switch(False)
+    t, f = r["torch"], r["fused_train"]
+    r["fused_train_is_faster"] = f["median_us"] < t["min_us"]
+    print(f"{label:32s}: torch median {t['median_us']:9.1f} us (min {t['min_us']:9.1f}) peak {t['peak_bytes'] / 2**20:8.1f} MiB   "
+          f"fused_train median {f['median_us']:9.1f} us (min {f['min_us']:9.1f}) peak {f['peak_bytes'] / 2**20:8.1f} MiB   "
+          f"{'fused_train faster' if r['fused_train_is_faster'] else 'NOT faster'} (x{t['median_us'] / f['median_us']:.2f} on the "
+          f"medians, x{t['peak_bytes'] / max(f['peak_bytes'], 1):.2f} on the peaks)")
+    return r
+
+
+def train(a, dev, g, bag, model, attn, out):
+    side = math.ceil(math.sqrt(a.n))
+    n_tok = side * side + 1
+    out["tokens"] = n_tok
+    x = torch.nn.functional.layer_norm(torch.randn(1, n_tok, 512, generator=g), (512,)).to(dev)
+    cot = torch.randn(1, n_tok, 512, generator=g).to(dev)
+    label = torch.tensor([1], device=dev)
+
+    def flags(module):
+        return lambda on: (setattr(module, "fused", on), setattr(module, "fused_train", on))
+
+    def layer_step():
+        attn.zero_grad(set_to_none=True)
+        xi = x.detach().requires_grad_(True)
+        (attn(xi) * cot).sum().backward()
+
+    def model_step():
+        model.zero_grad(set_to_none=True)
+        torch.nn.functional.cross_entropy(model(bag)[0], label).backward()
+    out["train_model"] = train_pair(f"TransMIL {a.n} x 512, fwd + bwd", model_step, flags(model), a.iters, a.warmup)
+    out["train_layer"] = train_pair(f"one layer, {n_tok} tokens, fwd + bwd", layer_step, flags(attn), a.iters, a.warmup)
+
+    # each backward entry alone against its two bounds.  Bytes: qkv's columns it reads, twice (once per kernel), dout likewise,
+    # and the dqkv it writes; products: [256, n] x 64 per head, 7 on the landmark side (S, dP twice; dv, dk, dq_l), 8 on the
+    # token side (S twice, dP three times -- delta takes a walk of its own --; dq, dk_l, dY)
+    with torch.no_grad():
+        n_pad = -(-n_tok // M) * M
+        out["n_pad"] = n_pad
+        qkv = attn.to_qkv(torch.nn.functional.pad(x, (0, 0, n_pad - n_tok, 0)))[0].contiguous()
+        l = n_pad // M
+        q_l = ((qkv[:, :512] * attn.scale).reshape(M, l, H, D).sum(1) / l).transpose(0, 1).contiguous()
+        k_l = (qkv[:, 512:1024].reshape(M, l, H, D).sum(1) / l).transpose(0, 1).contiguous()
+        W, lse = engine.nystrom_landmark_values_lse(qkv, q_l)
+        dW = torch.randn(H, M, D, generator=g).to(dev)
+        dout = torch.randn(n_pad, H * D, generator=g).to(dev)
+        scores = 2.0 * H * M * n_pad * D
+        out["landmark_backward"] = kernel("moc_nystrom_landmark_backward",
+                                          lambda: engine.nystrom_landmark_backward(qkv, q_l, W, lse, dW),
+                                          (2 * 2 + 3) * n_pad * 512 * 4, 7 * scores, a.iters, a.warmup)
+        out["token_backward"] = kernel("moc_nystrom_token_backward",
+                                       lambda: engine.nystrom_token_backward(qkv, k_l, W, attn.scale, dout),
+                                       (2 * 2 + 3) * n_pad * 512 * 4, 8 * scores, a.iters, a.warmup)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--train", action="store_true", help="time forward + backward: the torch path against fused_train")
     ap.add_argument("--n", type=int, default=15000)
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
@@ -94,6 +167,13 @@ def main():
     model = TransMIL(n_classes=2, size_arg="conch").to(dev).eval()
     attn = model.layer1.attn
     out = {"n": a.n}
+    if a.train:
+        train(a, dev, g, bag, model, attn, out)
+        if a.json:
+            os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+            with open(a.json, "w") as f:
+                json.dump(out, f, indent=1)
+        return
     with torch.no_grad():
         side = math.ceil(math.sqrt(a.n))                                  # TransMIL pads the bag to a square, + class token
         n_tok = side * side + 1
