@@ -623,6 +623,24 @@ int moc_nystrom_token_backward(const float* qkv, int64_t n_pad, int heads, int d
                                float* dqkv /* [n_pad, 3*h*d] */, float* dk_l, float* dY,
                                void* ws, size_t ws_bytes, moc_stream_t stream);
 
+/* The backward of moc_nystrom_token_values' residual convolution, for training on kernel B WITH it (moc_amd/nystrom.py:
+ * TokenValuesResidual).  With out[i, 64 h + d] += sum_t w[h, t] v[i + t - taps / 2, h, d] and dout [n_pad, 512]:
+ *   dv[j, h, d] = sum_t w[h, t] dout[j - t + taps / 2, h, d]      written to dqkv's v columns (1024 + 64 h + d) ONLY: the q
+ *       and k columns are not touched, so the entry runs in stream order after moc_nystrom_token_backward on the same dqkv
+ *       and replaces that entry's zeros;
+ *   dw[h, t]    = sum_i sum_d dout[i, h, d] v[i + t - taps / 2, h, d]      every element of dconv_w [8, taps] is written.
+ * Rows outside [0, n_pad) count as zero and are not read.  dw is summed in fp32 over the 64 features of one (token, tap)
+ * pair and in double above that; each 256-token block leaves 33 doubles per head in `ws`
+ * (moc_nystrom_conv_backward_workspace bytes) and a merge launch adds the blocks in index order: no atomics, the same bits
+ * on every call.  MOC_EUNSUPPORTED for another shape and for taps > 33; MOC_EINVAL for a null or not 16-byte aligned
+ * pointer, a bad n_pad, taps < 1 or even, a short workspace -- all before the first launch.  Additive to ABI 20: the
+ * version number is unchanged. */
+size_t moc_nystrom_conv_backward_workspace(int64_t n_pad, int heads, int dim_head, int landmarks, int taps);  /* 0: unsupported */
+int moc_nystrom_conv_backward(const float* qkv, int64_t n_pad, int heads, int dim_head, int landmarks,
+                              const float* conv_w /* [h, taps] */, int taps, const float* dout /* [n_pad, h*d] */,
+                              float* dqkv /* [n_pad, 3*h*d] */, float* dconv_w /* [h, taps] */,
+                              void* ws, size_t ws_bytes, moc_stream_t stream);
+
 /* The same layer's landmark pseudo-inverse (moc_amd/nystrom.py: moore_penrose_iter_pinv) as a chain of fp32 products on
  * the whole chip, for heads = 8 and landmarks = 256 only.  A = attn2 [8, 256, 256] device fp32, never written:
  *   c = max over all heads and rows of sum_j |A[h, i, j]|, r = likewise of the column sums;  Z0 = A^T / (c r)

@@ -151,6 +151,9 @@ SIGNATURES = {
                                                 C.c_size_t, _p]),
     "moc_nystrom_token_backward": (C.c_int, [_p, C.c_int64, C.c_int, C.c_int, C.c_int, _p, _p, C.c_float, _p, _p, _p, _p, _p,
                                              C.c_size_t, _p]),
+    "moc_nystrom_conv_backward_workspace": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "moc_nystrom_conv_backward": (C.c_int, [_p, C.c_int64, C.c_int, C.c_int, C.c_int, _p, C.c_int, _p, _p, _p, _p,
+                                            C.c_size_t, _p]),
     "moc_nystrom_pinv_workspace": (C.c_size_t, [C.c_int, C.c_int]),
     "moc_nystrom_pinv": (C.c_int, [_p, C.c_int, C.c_int, C.c_int, _p, _p, C.c_size_t, _p]),
     "moc_cu_census": (C.c_int, [_p, C.c_int, C.c_int, _p]),

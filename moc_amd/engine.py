@@ -1438,6 +1438,30 @@ def nystrom_token_backward(qkv: torch.Tensor, k_l: torch.Tensor, Y: torch.Tensor
     return dqkv, dk_l, dY
 
 
+def nystrom_conv_backward(qkv: torch.Tensor, conv_w: torch.Tensor, dout: torch.Tensor, dqkv: torch.Tensor) -> torch.Tensor:
+    """Backward of nystrom_token_values' residual convolution (moc_nystrom_conv_backward): from qkv [n_pad, 1536], conv_w
+    [8, taps] and dout [n_pad, 512] it WRITES dv into the v columns of the dqkv it is given (a contiguous [n_pad, 1536], e.g.
+    nystrom_token_backward's: the q and k columns are left as they are) and returns dconv_w [8, taps]."""
+    what = "nystrom_conv_backward"
+    n_pad = _nystrom_qkv(qkv, what)
+    for t in (conv_w, dout, dqkv):
+        assert t.is_cuda and t.dtype == torch.float32, f"{what}: fp32 tensors on the GPU (no CPU fallback)"
+    assert conv_w.dim() == 2 and conv_w.shape[0] == NYSTROM_HEADS, f"{what}: conv_w must be [8, taps]"
+    taps = conv_w.shape[1]
+    assert taps % 2 == 1 and taps <= NYSTROM_MAX_TAPS, f"{what}: taps={taps} must be odd and at most 33"
+    assert dout.shape == (n_pad, NYSTROM_HEADS * NYSTROM_DIM_HEAD), f"{what}: dout must be [n_pad, 512]"
+    assert dqkv.shape == qkv.shape and dqkv.is_contiguous() and not dqkv.requires_grad, \
+        f"{what}: dqkv must be a contiguous [n_pad, 1536] that wants no gradient"
+    conv_w, dout = conv_w.detach().contiguous(), dout.detach().contiguous()
+    dconv_w = torch.empty_like(conv_w)
+    nbytes = lib().moc_nystrom_conv_backward_workspace(n_pad, NYSTROM_HEADS, NYSTROM_DIM_HEAD, NYSTROM_LANDMARKS, taps)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=qkv.device)
+    check(lib().moc_nystrom_conv_backward(ptr(qkv.detach()), n_pad, NYSTROM_HEADS, NYSTROM_DIM_HEAD, NYSTROM_LANDMARKS,
+                                          ptr(conv_w), taps, ptr(dout), ptr(dqkv), ptr(dconv_w), ptr(ws), nbytes, _stream()),
+          "moc_nystrom_conv_backward")
+    return dconv_w
+
+
 def nystrom_pinv(attn2: torch.Tensor, iters: int) -> torch.Tensor:
     """The landmark pseudo-inverse of the fused Nystrom forward (moc_nystrom_pinv): nystrom.moore_penrose_iter_pinv of
     attn2 [8, 256, 256] -- Z0 = attn2^T / (max row sum x max column sum of |attn2| over all heads), then `iters` times

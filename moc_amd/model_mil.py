@@ -5,7 +5,7 @@ picking the top instance over the N patches runs on the HIP path (pool_autograd)
 through the picked row only, as in the reference.  Parameter names match (`classifier.{0,2}` /
 `fc.0`, `classifiers.{c}`), so reference checkpoints load.  TransMIL (plain torch + the restated Nystrom attention of
 moc_amd/nystrom.py; parity unpinned: the reference's own class cannot be built without the absent third-party
-package) keeps the contract (logits, Y_prob, Y_hat, None, None); its switches `fused`, `fused_pinv` and `fused_train`
+package) keeps the contract (logits, Y_prob, Y_hat, None, None); its switches `fused`, `fused_pinv`, `fused_train` and `fused_conv`
 (all off by default) put its two attention layers on the HIP kernels of moc_nystrom*.hip -- the no-grad passes, their
 pseudo-inverse, and the passes that want a gradient."""
 from __future__ import annotations
@@ -178,6 +178,16 @@ class TransMIL(nn.Module):
     @fused_train.setter
     def fused_train(self, on: bool):
         self.layer1.attn.fused_train = self.layer2.attn.fused_train = bool(on)
+
+    @property
+    def fused_conv(self) -> bool:
+        """Both layers' residual convolution inside kernel B in passes that want a gradient, with its two gradients from
+        moc_nystrom_conv_bwd.hip (nystrom.NystromAttention.fused_conv); acts only together with `fused` and `fused_train`."""
+        return bool(self.layer1.attn.fused_conv and self.layer2.attn.fused_conv)
+
+    @fused_conv.setter
+    def fused_conv(self, on: bool):
+        self.layer1.attn.fused_conv = self.layer2.attn.fused_conv = bool(on)
 
     def _tokens(self, data):
         """fc1, wrap-around padding to a square, class token, layer 1, PPEG, layer 2 (:236-266)."""

@@ -15,7 +15,9 @@ against THIS restatement (tests/test_gpu_nystrom.py) and pin nothing more than i
 takes the pseudo-inverse from csrc/moc_nystrom_pinv.hip, checked against moore_penrose_iter_pinv below
 (tests/test_gpu_nystrom_pinv.py); `fused_train = True` on top of `fused` lets the passes that want a gradient run on the same
 two products too, through LandmarkValues / TokenValues below, whose backward is csrc/moc_nystrom_bwd.hip, checked against
-float64 autograd of THIS restatement (tests/test_gpu_nystrom_train.py)."""
+float64 autograd of THIS restatement (tests/test_gpu_nystrom_train.py); `fused_conv = True` on top of both keeps kernel B's
+residual convolution in those passes too, through TokenValuesResidual, whose backward adds csrc/moc_nystrom_conv_bwd.hip
+(the convolution's value and tap gradients), checked the same way (tests/test_gpu_nystrom_conv.py)."""
 from __future__ import annotations
 
 from math import ceil
@@ -78,6 +80,28 @@ class TokenValues(torch.autograd.Function):
         return dqkv, dk_l, dY, None
 
 
+class TokenValuesResidual(torch.autograd.Function):
+    """TokenValues WITH kernel B's residual convolution of v by conv_w [8, taps]: the forward is bit for bit what the no-grad
+    fused forward computes; the backward is moc_nystrom_token_backward, then moc_nystrom_conv_backward on the same qkv
+    gradient, which leaves dq in the q columns, zeros in the k columns and the convolution's dv in the v columns."""
+
+    @staticmethod
+    def forward(ctx, qkv, k_l, Y, conv_w, scale):
+        from . import engine
+        ctx.save_for_backward(qkv, k_l, Y, conv_w)
+        ctx.scale = scale
+        return engine.nystrom_token_values(qkv, k_l, Y, conv_w, scale)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        from . import engine
+        qkv, k_l, Y, conv_w = ctx.saved_tensors
+        dqkv, dk_l, dY = engine.nystrom_token_backward(qkv, k_l, Y, ctx.scale, dout)
+        dconv_w = engine.nystrom_conv_backward(qkv, conv_w, dout, dqkv)
+        return dqkv, dk_l, dY, dconv_w, None
+
+
 class NystromAttention(nn.Module):
     def __init__(self, dim, dim_head=64, heads=8, num_landmarks=256, pinv_iterations=6, residual=True,
                  residual_conv_kernel=33, eps=1e-8, dropout=0.0):
@@ -101,6 +125,9 @@ class NystromAttention(nn.Module):
     # True: forward_fused, where its kernels apply but for a wanted gradient, keeps the two products on the kernels and
     # takes their gradient from moc_nystrom_bwd.hip (_forward_fused_train); no effect without `fused`, nor under no_grad
     fused_train = False
+    # True: _forward_fused_train, for a layer with a residual, keeps the residual convolution inside kernel B and takes its two
+    # gradients from moc_nystrom_conv_bwd.hip (TokenValuesResidual); no effect on any call that does not run _forward_fused_train
+    fused_conv = False
 
     def forward(self, x, mask=None, return_attn=False):
         if self.fused:
@@ -162,7 +189,8 @@ class NystromAttention(nn.Module):
         TokenValues(qkv, k_l, Y) without the residual; then res_conv(v), to_out and the slice in torch.  Neither [8, n, 256]
         score matrix is formed or kept: both backward kernels recompute their weights.  The pseudo-inverse is ALWAYS
         moore_penrose_iter_pinv here -- `fused_pinv` is ignored, its kernel forms no gradient -- and the residual
-        convolution and its two gradients stay on torch."""
+        convolution and its two gradients stay on torch, unless `fused_conv` is set: then the residual is kernel B's own
+        (TokenValuesResidual) and res_conv's forward is not called."""
         n, h, m = x.shape[1], self.heads, self.num_landmarks
         if n % m > 0:
             x = F.pad(x, (0, 0, m - (n % m), 0), value=0)
@@ -174,10 +202,13 @@ class NystromAttention(nn.Module):
         attn2 = (q_l @ k_l.transpose(-1, -2)).softmax(dim=-1)
         pinv = moore_penrose_iter_pinv(attn2.unsqueeze(0), self.pinv_iterations)[0]
         W = LandmarkValues.apply(qkv, q_l)
-        out = TokenValues.apply(qkv, k_l, pinv @ W, self.scale)                       # [n_pad, 512]
-        if self.residual:
-            v = qkv[:, 2 * inner:].reshape(1, n_pad, h, -1).transpose(1, 2)         # [1, 8, n_pad, 64], a view
-            out = out + self.res_conv(v).transpose(1, 2).reshape(n_pad, inner)
+        if self.residual and self.fused_conv:                                         # (the reshape stays tracked)
+            out = TokenValuesResidual.apply(qkv, k_l, pinv @ W, self.res_conv.weight.reshape(h, -1), self.scale)
+        else:
+            out = TokenValues.apply(qkv, k_l, pinv @ W, self.scale)                   # [n_pad, 512]
+            if self.residual:
+                v = qkv[:, 2 * inner:].reshape(1, n_pad, h, -1).transpose(1, 2)     # [1, 8, n_pad, 64], a view
+                out = out + self.res_conv(v).transpose(1, 2).reshape(n_pad, inner)
         return self.to_out(out.unsqueeze(0))[:, -n:]
 
     def _forward_torch(self, x, mask=None, return_attn=False):

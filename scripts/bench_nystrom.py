@@ -10,8 +10,11 @@ runs.  "faster" is claimed only where a median is below the minimum of the path 
 
 With --train: forward + backward of one attention layer and of the whole model on the same bag, the torch path (autograd
 keeps both [8, n, 256] score matrices and their softmax outputs) against `fused` + `fused_train` (LandmarkValues /
-TokenValues: the backward of moc_nystrom_bwd.hip recomputes the weights), timed the same way, each with the peak of
-torch.cuda.max_memory_allocated over one step, above what was allocated before it.
+TokenValues: the backward of moc_nystrom_bwd.hip recomputes the weights) and against those two with `fused_conv` on top
+(TokenValuesResidual: the residual convolution stays in kernel B, its gradients are moc_nystrom_conv_bwd.hip's), all three
+in the same run and timed the same way, each with the peak of torch.cuda.max_memory_allocated over one step, above what was
+allocated before it.  Then each backward entry alone against its two bounds, and the torch pieces all paths share, each
+alone, forward + backward: res_conv, moore_penrose_iter_pinv, to_qkv, and the model's pos_layer (PPEG).
 
     python scripts/bench_nystrom.py [--n 15000] [--iters 30] [--json out.json] [--train]
     rocprofv3 --kernel-trace --stats ... -- python scripts/bench_nystrom.py --trace-layers 8
@@ -83,10 +86,11 @@ def kernel(label, fn, nbytes, flops, iters, warmup):
 
 
 def train_pair(label, step, switch, iters, warmup):
-    """step() -- one forward + backward -- timed and its peak memory taken on the torch path and with `fused_train`."""
+    """step() -- one forward + backward -- timed and its peak memory taken on the torch path, with `fused` + `fused_train`,
+    and with `fused_conv` on top of those; switch(fused_train, fused_conv) sets the flags."""
     r = {}
-    for key, on in (("torch", False), ("fused_train", True)):
-        switch(on)
+    for key, flags in (("torch", (False, False)), ("fused_train", (True, False)), ("fused_conv", (True, True))):
+        switch(*flags)
         r[key] = times_us(step, iters, warmup)
         torch.cuda.synchronize()
         torch.cuda.empty_cache()
@@ -95,13 +99,25 @@ def train_pair(label, step, switch, iters, warmup):
         step()
         torch.cuda.synchronize()
         r[key]["peak_bytes"] = torch.cuda.max_memory_allocated() - base
-    switch(False)
-    t, f = r["torch"], r["fused_train"]
+    switch(False, False)
+    t, f, c = r["torch"], r["fused_train"], r["fused_conv"]
     r["fused_train_is_faster"] = f["median_us"] < t["min_us"]
+    r["fused_conv_is_faster_than_fused_train"] = c["median_us"] < f["min_us"]
     print(f"{label:32s}: torch median {t['median_us']:9.1f} us (min {t['min_us']:9.1f}) peak {t['peak_bytes'] / 2**20:8.1f} MiB   "
           f"fused_train median {f['median_us']:9.1f} us (min {f['min_us']:9.1f}) peak {f['peak_bytes'] / 2**20:8.1f} MiB   "
           f"{'fused_train faster' if r['fused_train_is_faster'] else 'NOT faster'} (x{t['median_us'] / f['median_us']:.2f} on the "
           f"medians, x{t['peak_bytes'] / max(f['peak_bytes'], 1):.2f} on the peaks)")
+    print(f"{'':32s}  fused_train + fused_conv median {c['median_us']:9.1f} us (min {c['min_us']:9.1f}) peak "
+          f"{c['peak_bytes'] / 2**20:8.1f} MiB   "
+          f"{'faster than fused_train' if r['fused_conv_is_faster_than_fused_train'] else 'NOT faster than fused_train'} "
+          f"(x{f['median_us'] / c['median_us']:.2f} on the medians, x{t['median_us'] / c['median_us']:.2f} on the torch path's)")
+    return r
+
+
+def piece(label, step, iters, warmup):
+    """One torch piece of the layer or the model alone, forward + backward, on the shape the model gives it."""
+    r = times_us(step, iters, warmup)
+    print(f"{label:32s}: fwd + bwd median {r['median_us']:9.1f} us (min {r['min_us']:9.1f})")
     return r
 
 
@@ -114,7 +130,8 @@ def train(a, dev, g, bag, model, attn, out):
     label = torch.tensor([1], device=dev)
 
     def flags(module):
-        return lambda on: (setattr(module, "fused", on), setattr(module, "fused_train", on))
+        return lambda on, conv: (setattr(module, "fused", on), setattr(module, "fused_train", on),
+                                 setattr(module, "fused_conv", conv))
 
     def layer_step():
         attn.zero_grad(set_to_none=True)
@@ -147,11 +164,41 @@ def train(a, dev, g, bag, model, attn, out):
         out["token_backward"] = kernel("moc_nystrom_token_backward",
                                        lambda: engine.nystrom_token_backward(qkv, k_l, W, attn.scale, dout),
                                        (2 * 2 + 3) * n_pad * 512 * 4, 8 * scores, a.iters, a.warmup)
+        # the residual convolution's backward alone: it reads dout and qkv's v columns and writes dv; two banded products of
+        # 48 rows per 16-token tile (dv, and the [48, 16] tile whose diagonals are the tap gradients)
+        w = attn.res_conv.weight.detach().reshape(H, TAPS).contiguous()
+        dqkv = torch.zeros_like(qkv)
+        out["conv_backward"] = kernel("moc_nystrom_conv_backward", lambda: engine.nystrom_conv_backward(qkv, w, dout, dqkv),
+                                      3 * n_pad * 512 * 4, 2 * 2.0 * n_pad * 512 * 48, a.iters, a.warmup)
+
+    # the torch pieces every path shares, each alone, forward + backward, on the shapes the model gives them: by these
+    # numbers the next kernel on this path is chosen
+    def backward_of(make, *leaves):
+        def step():
+            for t in leaves:
+                t.grad = None
+            make().sum().backward()
+        return step
+
+    v = torch.randn(1, H, n_pad, D, generator=g).to(dev).requires_grad_(True)
+    out["piece_res_conv"] = piece(f"res_conv on [1, 8, {n_pad}, 64]", backward_of(lambda: attn.res_conv(v), v, attn.res_conv.weight),
+                                  a.iters, a.warmup)
+    attn2 = (q_l @ k_l.transpose(-1, -2)).softmax(dim=-1).requires_grad_(True)
+    out["piece_pinv"] = piece("moore_penrose_iter_pinv [8, 256, 256]",
+                              backward_of(lambda: moore_penrose_iter_pinv(attn2.unsqueeze(0), attn.pinv_iterations), attn2),
+                              a.iters, a.warmup)
+    xp = torch.nn.functional.pad(x, (0, 0, n_pad - n_tok, 0)).requires_grad_(True)
+    out["piece_to_qkv"] = piece(f"to_qkv on [1, {n_pad}, 512]", backward_of(lambda: attn.to_qkv(xp), xp, attn.to_qkv.weight),
+                                a.iters, a.warmup)
+    xt = x.detach().clone().requires_grad_(True)
+    ppeg = model.pos_layer
+    out["piece_pos_layer"] = piece(f"pos_layer (PPEG) on [1, {n_tok}, 512]",
+                                   backward_of(lambda: ppeg(xt, side, side), xt, *ppeg.parameters()), a.iters, a.warmup)
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--train", action="store_true", help="time forward + backward: the torch path against fused_train")
+    ap.add_argument("--train", action="store_true", help="time forward + backward: the torch path against fused_train and fused_train + fused_conv")
     ap.add_argument("--n", type=int, default=15000)
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
