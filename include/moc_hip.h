@@ -654,6 +654,30 @@ size_t moc_nystrom_pinv_workspace(int heads, int landmarks);          /* 0: unsu
 int moc_nystrom_pinv(const float* A /* [h, m, m] */, int heads, int landmarks, int iters,
                      float* Z /* [h, m, m] */, void* ws, size_t ws_bytes, moc_stream_t stream);
 
+/* moc_nystrom_pinv made to keep every iterate, for training (moc_amd/nystrom.py: LandmarkPinv): Zs[t] = Z_t for
+ * t = 0 .. iters, and Zs[iters] is bit for bit what moc_nystrom_pinv returns.  The same launches, the same workspace size
+ * (moc_nystrom_pinv_workspace), the same refusals, with Zs [(iters + 1), h, m, m] in Z's place. */
+int moc_nystrom_pinv_iterates(const float* A /* [h, m, m] */, int heads, int landmarks, int iters,
+                              float* Zs /* [iters + 1, h, m, m] */, void* ws, size_t ws_bytes, moc_stream_t stream);
+
+/* The gradient through moc_nystrom_pinv_iterates: dA [h, m, m] from A, the iterates Zs and dZ = d(Zs[iters]).  For
+ * t = iters - 1 .. 0, with XZ, P2, P3 recomputed from Z_t (only the iterates are saved):
+ *   dP3 = -0.25 Z_t^T dZ;  dP2 = -(XZ^T dP3);  dXZ = dP3 (15 I - P2)^T + dP2 (7 I - XZ)^T - XZ^T dP2
+ *   dA += dXZ Z_t^T;       dZ <- 0.25 dZ (13 I - P3)^T + A^T dXZ
+ * then through Z0 = A^T / (c r):  dA += dZ^T / (c r);  dden = -sum(dZ o Z0) / (c r), one reduction in double in a fixed
+ * order;  the rows whose sum of |A| IS c share dden r evenly, each of their elements + share x sign(A) (torch's rule for a
+ * full max(); sign(0) = 0), and the columns whose sum IS r share dden c likewise -- the sums are the forward's own code.
+ * Products of one to three terms with either operand transposed on the way into LDS, independent products side by side in
+ * one launch: 3 + 4 iters product launches and four for the init, 31 at six iterations, in stream order; no atomics, no
+ * grid-wide barrier: the same bits on every call.  Every element of dA is written; no input is.  `ws` holds
+ * moc_nystrom_pinv_backward_workspace bytes (eleven matrices, the sums, the partials).  MOC_EUNSUPPORTED for another
+ * shape; MOC_EINVAL for null or not 16-byte aligned pointers, any two of A, Zs, dZ, dA and ws overlapping, a short
+ * workspace, iters outside 0..64 -- all before the first launch.  Additive to ABI 20: the version number is unchanged. */
+size_t moc_nystrom_pinv_backward_workspace(int heads, int landmarks);  /* 0: unsupported shape */
+int moc_nystrom_pinv_backward(const float* A /* [h, m, m] */, int heads, int landmarks, int iters,
+                              const float* Zs /* [iters + 1, h, m, m] */, const float* dZ /* [h, m, m] */,
+                              float* dA /* [h, m, m] */, void* ws, size_t ws_bytes, moc_stream_t stream);
+
 /* a10-a15 fused: `n` consecutive meta-steps (one slide each, slides slide0..slide0+n-1 in
  * order, one Adam step per slide: main_moc.py:380-410), parameters and Adam moments
  * updated in place.  Per-slide loss/pooled land in ws->loss / ws->pooled. */

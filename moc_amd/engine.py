@@ -1478,3 +1478,43 @@ def nystrom_pinv(attn2: torch.Tensor, iters: int) -> torch.Tensor:
     check(lib().moc_nystrom_pinv(ptr(attn2), NYSTROM_HEADS, NYSTROM_LANDMARKS, iters, ptr(Z), ptr(ws), nbytes, _stream()),
           "moc_nystrom_pinv")
     return Z
+
+
+def _nystrom_mmm(t: torch.Tensor, name: str, what: str) -> torch.Tensor:
+    assert t.is_cuda and t.dtype == torch.float32, f"{what}: fp32 tensors on the GPU (no CPU fallback)"
+    assert t.shape == (NYSTROM_HEADS, NYSTROM_LANDMARKS, NYSTROM_LANDMARKS), f"{what}: {name} must be [8, 256, 256]"
+    return t.detach().contiguous()
+
+
+def nystrom_pinv_iterates(attn2: torch.Tensor, iters: int) -> torch.Tensor:
+    """nystrom_pinv that keeps every iterate (moc_nystrom_pinv_iterates): Zs [iters + 1, 8, 256, 256] with Zs[t] = Z_t, and
+    Zs[iters] bit for bit nystrom_pinv's result.  What nystrom_pinv_backward needs; no gradient of its own."""
+    what = "nystrom_pinv_iterates"
+    attn2 = _nystrom_mmm(attn2, "attn2", what)
+    iters = int(iters)
+    assert 0 <= iters <= 64, f"{what}: iters={iters} must be in 0..64"
+    Zs = torch.empty((iters + 1,) + tuple(attn2.shape), dtype=torch.float32, device=attn2.device)
+    nbytes = lib().moc_nystrom_pinv_workspace(NYSTROM_HEADS, NYSTROM_LANDMARKS)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=attn2.device)
+    check(lib().moc_nystrom_pinv_iterates(ptr(attn2), NYSTROM_HEADS, NYSTROM_LANDMARKS, iters, ptr(Zs), ptr(ws), nbytes, _stream()),
+          "moc_nystrom_pinv_iterates")
+    return Zs
+
+
+def nystrom_pinv_backward(attn2: torch.Tensor, Zs: torch.Tensor, dZ: torch.Tensor, iters: int) -> torch.Tensor:
+    """The gradient through nystrom_pinv_iterates (moc_nystrom_pinv_backward): d attn2 [8, 256, 256] from attn2, its iterates
+    Zs [iters + 1, 8, 256, 256] and dZ = d(Zs[iters]), the scaling by the two maximal sums included (ties share evenly, as
+    torch's max() does).  3 + 4 iters product launches and four more; XZ, P2 and P3 are recomputed."""
+    what = "nystrom_pinv_backward"
+    attn2, dZ = _nystrom_mmm(attn2, "attn2", what), _nystrom_mmm(dZ, "dZ", what)
+    iters = int(iters)
+    assert 0 <= iters <= 64, f"{what}: iters={iters} must be in 0..64"
+    assert Zs.is_cuda and Zs.dtype == torch.float32, f"{what}: fp32 tensors on the GPU (no CPU fallback)"
+    assert Zs.shape == (iters + 1,) + tuple(attn2.shape), f"{what}: Zs must be [iters + 1, 8, 256, 256]"
+    Zs = Zs.detach().contiguous()
+    dA = torch.empty_like(attn2)
+    nbytes = lib().moc_nystrom_pinv_backward_workspace(NYSTROM_HEADS, NYSTROM_LANDMARKS)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=attn2.device)
+    check(lib().moc_nystrom_pinv_backward(ptr(attn2), NYSTROM_HEADS, NYSTROM_LANDMARKS, iters, ptr(Zs), ptr(dZ), ptr(dA), ptr(ws),
+                                          nbytes, _stream()), "moc_nystrom_pinv_backward")
+    return dA

@@ -5,8 +5,8 @@ picking the top instance over the N patches runs on the HIP path (pool_autograd)
 through the picked row only, as in the reference.  Parameter names match (`classifier.{0,2}` /
 `fc.0`, `classifiers.{c}`), so reference checkpoints load.  TransMIL (plain torch + the restated Nystrom attention of
 moc_amd/nystrom.py; parity unpinned: the reference's own class cannot be built without the absent third-party
-package) keeps the contract (logits, Y_prob, Y_hat, None, None); its switches `fused`, `fused_pinv`, `fused_train` and `fused_conv`
-(all off by default) put its two attention layers on the HIP kernels of moc_nystrom*.hip -- the no-grad passes, their
+package) keeps the contract (logits, Y_prob, Y_hat, None, None); its switches `fused`, `fused_pinv`, `fused_train`, `fused_conv`
+and `fused_pinv_train` (all off by default) put its two attention layers on the HIP kernels of moc_nystrom*.hip -- the no-grad passes, their
 pseudo-inverse, and the passes that want a gradient."""
 from __future__ import annotations
 
@@ -188,6 +188,16 @@ class TransMIL(nn.Module):
     @fused_conv.setter
     def fused_conv(self, on: bool):
         self.layer1.attn.fused_conv = self.layer2.attn.fused_conv = bool(on)
+
+    @property
+    def fused_pinv_train(self) -> bool:
+        """Both layers' pseudo-inverse and its gradient on moc_nystrom_pinv.hip in passes that want a gradient
+        (nystrom.NystromAttention.fused_pinv_train); acts only together with `fused` and `fused_train`."""
+        return bool(self.layer1.attn.fused_pinv_train and self.layer2.attn.fused_pinv_train)
+
+    @fused_pinv_train.setter
+    def fused_pinv_train(self, on: bool):
+        self.layer1.attn.fused_pinv_train = self.layer2.attn.fused_pinv_train = bool(on)
 
     def _tokens(self, data):
         """fc1, wrap-around padding to a square, class token, layer 1, PPEG, layer 2 (:236-266)."""

@@ -17,7 +17,10 @@ takes the pseudo-inverse from csrc/moc_nystrom_pinv.hip, checked against moore_p
 two products too, through LandmarkValues / TokenValues below, whose backward is csrc/moc_nystrom_bwd.hip, checked against
 float64 autograd of THIS restatement (tests/test_gpu_nystrom_train.py); `fused_conv = True` on top of both keeps kernel B's
 residual convolution in those passes too, through TokenValuesResidual, whose backward adds csrc/moc_nystrom_conv_bwd.hip
-(the convolution's value and tap gradients), checked the same way (tests/test_gpu_nystrom_conv.py)."""
+(the convolution's value and tap gradients), checked the same way (tests/test_gpu_nystrom_conv.py);
+`fused_pinv_train = True` on top of `fused` and `fused_train` takes the pseudo-inverse of those passes from LandmarkPinv, whose
+forward is moc_nystrom_pinv_iterates and whose backward is moc_nystrom_pinv_backward (csrc/moc_nystrom_pinv.hip), checked
+against float64 autograd of moore_penrose_iter_pinv (tests/test_gpu_nystrom_pinv_bwd.py)."""
 from __future__ import annotations
 
 from math import ceil
@@ -102,6 +105,27 @@ class TokenValuesResidual(torch.autograd.Function):
         return dqkv, dk_l, dY, dconv_w, None
 
 
+class LandmarkPinv(torch.autograd.Function):
+    """moore_penrose_iter_pinv of attn2 [8, 256, 256] on moc_nystrom_pinv_iterates: the forward keeps attn2 and the
+    iters + 1 iterates ((iters + 1) x 2 MiB) and returns the last, bit for bit engine.nystrom_pinv's result; the backward
+    (moc_nystrom_pinv_backward) recomputes XZ, P2 and P3 of every iteration from them."""
+
+    @staticmethod
+    def forward(ctx, attn2, iters):
+        from . import engine
+        Zs = engine.nystrom_pinv_iterates(attn2, iters)
+        ctx.save_for_backward(attn2, Zs)
+        ctx.iters = iters
+        return Zs[iters]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dZ):
+        from . import engine
+        attn2, Zs = ctx.saved_tensors
+        return engine.nystrom_pinv_backward(attn2, Zs, dZ, ctx.iters), None
+
+
 class NystromAttention(nn.Module):
     def __init__(self, dim, dim_head=64, heads=8, num_landmarks=256, pinv_iterations=6, residual=True,
                  residual_conv_kernel=33, eps=1e-8, dropout=0.0):
@@ -128,6 +152,9 @@ class NystromAttention(nn.Module):
     # True: _forward_fused_train, for a layer with a residual, keeps the residual convolution inside kernel B and takes its two
     # gradients from moc_nystrom_conv_bwd.hip (TokenValuesResidual); no effect on any call that does not run _forward_fused_train
     fused_conv = False
+    # True: _forward_fused_train takes the pseudo-inverse and its gradient from moc_nystrom_pinv.hip (LandmarkPinv) instead of
+    # moore_penrose_iter_pinv under autograd; no effect on any call that does not run _forward_fused_train
+    fused_pinv_train = False
 
     def forward(self, x, mask=None, return_attn=False):
         if self.fused:
@@ -187,8 +214,9 @@ class NystromAttention(nn.Module):
         """forward_fused's dataflow with autograd kept ("training"): to_qkv, the landmark means, attn2
         and its pseudo-inverse are tracked torch operations; W = LandmarkValues(qkv, q_l); Y = pinv W in torch;
         TokenValues(qkv, k_l, Y) without the residual; then res_conv(v), to_out and the slice in torch.  Neither [8, n, 256]
-        score matrix is formed or kept: both backward kernels recompute their weights.  The pseudo-inverse is ALWAYS
-        moore_penrose_iter_pinv here -- `fused_pinv` is ignored, its kernel forms no gradient -- and the residual
+        score matrix is formed or kept: both backward kernels recompute their weights.  The pseudo-inverse is
+        moore_penrose_iter_pinv here -- `fused_pinv` is ignored, its entry forms no gradient -- unless `fused_pinv_train` is set:
+        then it is LandmarkPinv, the same kernels with the iterates kept and a backward of their own.  The residual
         convolution and its two gradients stay on torch, unless `fused_conv` is set: then the residual is kernel B's own
         (TokenValuesResidual) and res_conv's forward is not called."""
         n, h, m = x.shape[1], self.heads, self.num_landmarks
@@ -200,7 +228,10 @@ class NystromAttention(nn.Module):
         q_l = (means[:, :inner] * self.scale).reshape(m, h, -1).transpose(0, 1).contiguous()                        # h m d
         k_l = means[:, inner:].reshape(m, h, -1).transpose(0, 1).contiguous()
         attn2 = (q_l @ k_l.transpose(-1, -2)).softmax(dim=-1)
-        pinv = moore_penrose_iter_pinv(attn2.unsqueeze(0), self.pinv_iterations)[0]
+        if self.fused_pinv_train:
+            pinv = LandmarkPinv.apply(attn2, self.pinv_iterations)
+        else:
+            pinv = moore_penrose_iter_pinv(attn2.unsqueeze(0), self.pinv_iterations)[0]
         W = LandmarkValues.apply(qkv, q_l)
         if self.residual and self.fused_conv:                                         # (the reshape stays tracked)
             out = TokenValuesResidual.apply(qkv, k_l, pinv @ W, self.res_conv.weight.reshape(h, -1), self.scale)

@@ -11,10 +11,13 @@ runs.  "faster" is claimed only where a median is below the minimum of the path 
 With --train: forward + backward of one attention layer and of the whole model on the same bag, the torch path (autograd
 keeps both [8, n, 256] score matrices and their softmax outputs) against `fused` + `fused_train` (LandmarkValues /
 TokenValues: the backward of moc_nystrom_bwd.hip recomputes the weights) and against those two with `fused_conv` on top
-(TokenValuesResidual: the residual convolution stays in kernel B, its gradients are moc_nystrom_conv_bwd.hip's), all three
+(TokenValuesResidual: the residual convolution stays in kernel B, its gradients are moc_nystrom_conv_bwd.hip's) and against
+all three with `fused_pinv_train` on top (LandmarkPinv: the pseudo-inverse and its gradient on moc_nystrom_pinv.hip), all four
 in the same run and timed the same way, each with the peak of torch.cuda.max_memory_allocated over one step, above what was
 allocated before it.  Then each backward entry alone against its two bounds, and the torch pieces all paths share, each
-alone, forward + backward: res_conv, moore_penrose_iter_pinv, to_qkv, and the model's pos_layer (PPEG).
+alone, forward + backward: res_conv, moore_penrose_iter_pinv, to_qkv, and the model's pos_layer (PPEG); beside
+moore_penrose_iter_pinv, on the same attn2, moc_nystrom_pinv_iterates + moc_nystrom_pinv_backward with independent products
+sharing launches (the default) and with one product per launch.
 
     python scripts/bench_nystrom.py [--n 15000] [--iters 30] [--json out.json] [--train]
     rocprofv3 --kernel-trace --stats ... -- python scripts/bench_nystrom.py --trace-layers 8
@@ -87,9 +90,11 @@ def kernel(label, fn, nbytes, flops, iters, warmup):
 
 def train_pair(label, step, switch, iters, warmup):
     """step() -- one forward + backward -- timed and its peak memory taken on the torch path, with `fused` + `fused_train`,
-    and with `fused_conv` on top of those; switch(fused_train, fused_conv) sets the flags."""
+    with `fused_conv` on top of those, and with `fused_pinv_train` on top of all three; switch(fused_train, fused_conv,
+    fused_pinv_train) sets the flags."""
     r = {}
-    for key, flags in (("torch", (False, False)), ("fused_train", (True, False)), ("fused_conv", (True, True))):
+    for key, flags in (("torch", (False, False, False)), ("fused_train", (True, False, False)), ("fused_conv", (True, True, False)),
+                       ("fused_pinv_train", (True, True, True))):
         switch(*flags)
         r[key] = times_us(step, iters, warmup)
         torch.cuda.synchronize()
@@ -99,10 +104,11 @@ def train_pair(label, step, switch, iters, warmup):
         step()
         torch.cuda.synchronize()
         r[key]["peak_bytes"] = torch.cuda.max_memory_allocated() - base
-    switch(False, False)
-    t, f, c = r["torch"], r["fused_train"], r["fused_conv"]
+    switch(False, False, False)
+    t, f, c, p = r["torch"], r["fused_train"], r["fused_conv"], r["fused_pinv_train"]
     r["fused_train_is_faster"] = f["median_us"] < t["min_us"]
     r["fused_conv_is_faster_than_fused_train"] = c["median_us"] < f["min_us"]
+    r["fused_pinv_train_is_faster_than_fused_conv"] = p["median_us"] < c["min_us"]
     print(f"{label:32s}: torch median {t['median_us']:9.1f} us (min {t['min_us']:9.1f}) peak {t['peak_bytes'] / 2**20:8.1f} MiB   "
           f"fused_train median {f['median_us']:9.1f} us (min {f['min_us']:9.1f}) peak {f['peak_bytes'] / 2**20:8.1f} MiB   "
           f"{'fused_train faster' if r['fused_train_is_faster'] else 'NOT faster'} (x{t['median_us'] / f['median_us']:.2f} on the "
@@ -111,6 +117,10 @@ def train_pair(label, step, switch, iters, warmup):
           f"{c['peak_bytes'] / 2**20:8.1f} MiB   "
           f"{'faster than fused_train' if r['fused_conv_is_faster_than_fused_train'] else 'NOT faster than fused_train'} "
           f"(x{f['median_us'] / c['median_us']:.2f} on the medians, x{t['median_us'] / c['median_us']:.2f} on the torch path's)")
+    print(f"{'':32s}  ... + fused_pinv_train median {p['median_us']:9.1f} us (min {p['min_us']:9.1f}) peak "
+          f"{p['peak_bytes'] / 2**20:8.1f} MiB   "
+          f"{'faster than fused_conv' if r['fused_pinv_train_is_faster_than_fused_conv'] else 'NOT faster than fused_conv'} "
+          f"(x{c['median_us'] / p['median_us']:.2f} on the medians, x{t['median_us'] / p['median_us']:.2f} on the torch path's)")
     return r
 
 
@@ -130,8 +140,8 @@ def train(a, dev, g, bag, model, attn, out):
     label = torch.tensor([1], device=dev)
 
     def flags(module):
-        return lambda on, conv: (setattr(module, "fused", on), setattr(module, "fused_train", on),
-                                 setattr(module, "fused_conv", conv))
+        return lambda on, conv, pinv: (setattr(module, "fused", on), setattr(module, "fused_train", on),
+                                       setattr(module, "fused_conv", conv), setattr(module, "fused_pinv_train", pinv))
 
     def layer_step():
         attn.zero_grad(set_to_none=True)
@@ -187,6 +197,24 @@ def train(a, dev, g, bag, model, attn, out):
     out["piece_pinv"] = piece("moore_penrose_iter_pinv [8, 256, 256]",
                               backward_of(lambda: moore_penrose_iter_pinv(attn2.unsqueeze(0), attn.pinv_iterations), attn2),
                               a.iters, a.warmup)
+    # the same on the kernels: the iterates and their backward, 2 + 4 iters launches, then 7 + 4 iters with independent
+    # products side by side, or 4 + 8 iters with one product per launch (the diagnostic switch is read on every call)
+    its, x2, dz = attn.pinv_iterations, attn2.detach(), torch.randn(H, M, M, generator=g).to(dev)
+
+    def pinv_step():
+        engine.nystrom_pinv_backward(x2, engine.nystrom_pinv_iterates(x2, its), dz, its)
+    for key, env, launches in (("grouped", "1", 7 + 4 * its), ("ungrouped", "0", 4 + 8 * its)):
+        os.environ["MOC_PINV_BWD_GROUPED"] = env
+        r = piece(f"moc_nystrom_pinv_iterates + _backward, {key}", pinv_step, a.iters, a.warmup)
+        r["launches"] = 2 + 4 * its + launches
+        out["pinv_train_" + key] = r
+    del os.environ["MOC_PINV_BWD_GROUPED"]
+    gr, un, tp = out["pinv_train_grouped"], out["pinv_train_ungrouped"], out["piece_pinv"]
+    out["pinv_train_grouped_is_faster_than_ungrouped"] = gr["median_us"] < un["min_us"]
+    out["pinv_train_is_faster_than_torch"] = gr["median_us"] < tp["min_us"]
+    print(f"{'':32s}  grouped ({gr['launches']} launches) {'faster' if gr['median_us'] < un['min_us'] else 'NOT faster'} than ungrouped "
+          f"({un['launches']}); {'faster' if gr['median_us'] < tp['min_us'] else 'NOT faster'} than torch "
+          f"(x{tp['median_us'] / gr['median_us']:.2f} on the medians)")
     xp = torch.nn.functional.pad(x, (0, 0, n_pad - n_tok, 0)).requires_grad_(True)
     out["piece_to_qkv"] = piece(f"to_qkv on [1, {n_pad}, 512]", backward_of(lambda: attn.to_qkv(xp), xp, attn.to_qkv.weight),
                                 a.iters, a.warmup)
@@ -198,7 +226,7 @@ def train(a, dev, g, bag, model, attn, out):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--train", action="store_true", help="time forward + backward: the torch path against fused_train and fused_train + fused_conv")
+    ap.add_argument("--train", action="store_true", help="time forward + backward: the torch path against fused_train, + fused_conv and + fused_pinv_train")
     ap.add_argument("--n", type=int, default=15000)
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
