@@ -76,7 +76,13 @@ enum { MOC_STATS_COMPACT = 1,
         * more selectable rows (the default there is the 64-row kernel: every W1 fragment feeds four row tiles -- at
         * 25,000 rows the sixteen-row workgroups re-read 390 KB of W1 image 1,580 times); the same bits -- the bit exists
         * so that tests can say so */
-       MOC_FORWARD_ROWS16 = 32 };
+       MOC_FORWARD_ROWS16 = 32,
+       /* moc_scores / moc_scores_timed on fp32 bags against a bank of one n-tile (Ce <= 16): the LDS-DMA ring kernel
+        * (one loader wave and three consumer waves per CU, rows through a ring of 16 KiB LDS slots, at most 64 VGPRs)
+        * instead of the register-buffered streaming kernel, where its LDS fits; the same bits in every output.  Other
+        * shapes keep their kernels.  The ring kernel walks the tiles statically over every CU: a batch that carries this
+        * bit AND a tile_ticket or cu_reserved is refused.  moc_scores_form() says which form a batch gets. */
+       MOC_SCORES_RING = 64 };
 
 /* bits of `discard_bits`, in the order of main_moc.py:341-350 */
 enum { MOC_SEL_TOPK = 1, MOC_SEL_DELTA_SOFTMAX = 2, MOC_SEL_DELTA_DIFF = 4, MOC_SEL_BOTTOMK = 8 };
@@ -242,6 +248,9 @@ int moc_scores(const moc_batch_t* B, const void* bank, moc_stream_t stream);
  * time stamps (hipExtLaunchKernel): hipEventElapsedTime(start, stop) is then the kernel's duration as a profiler
  * reports it, whatever else the GPU is running.  bench.py's `roofline` uses it. */
 int moc_scores_timed(const moc_batch_t* B, const void* bank, moc_stream_t stream, void* start_event, void* stop_event);
+/* Which kernel form moc_scores gives this batch (no launch): 0 streaming, 1 wide ring, 2 wide, 3 generic, 4 the LDS-DMA
+ * ring of MOC_SCORES_RING; negative: the batch is refused (moc_last_error has the text moc_scores would give). */
+int moc_scores_form(const moc_batch_t* B);
 
 /* a2 for several NARROW banks in one read of the bags (additive in ABI 20): prompt-bank selection.  A bank of at most 16
  * columns is one n-tile of the score kernel's image; up to moc_scores_banks_max of them laid side by side are an image its

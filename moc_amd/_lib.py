@@ -25,6 +25,8 @@ MOC_CAND_FROM_STATS = 4
 MOC_FORWARD_ROWS64 = 8
 MOC_FORWARD_FOUR_WAVES = 16
 MOC_FORWARD_ROWS16 = 32
+MOC_SCORES_RING = 64
+SCORE_FORM_RING = 4               # moc_scores_form: the LDS-DMA ring kernel (SCORE_RING of moc_scores_plan.h)
 SEL_BITS = {"topk": 1, "delta_softmax": 2, "delta_diff": 4, "bottomk": 8}
 
 _p = C.c_void_p
@@ -86,6 +88,7 @@ SIGNATURES = {
     "moc_mask_compact": (C.c_int, [_BP, _p]),
     "moc_scores": (C.c_int, [_BP, _p, _p]),
     "moc_scores_timed": (C.c_int, [_BP, _p, _p, _p, _p]),
+    "moc_scores_form": (C.c_int, [_BP]),
     "moc_scores_from_cache": (C.c_int, [_BP, _p, C.c_int64, _p]),
     "moc_scores_banks_max": (C.c_int, [C.c_int, C.c_int]),
     "moc_bank_set_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),

@@ -14,6 +14,7 @@
 #include <cstddef>
 #include <cstdlib>
 #include "moc_meta_internal.h"
+#include "moc_scores_plan.h"
 
 using namespace moc_meta_internal;
 
@@ -385,6 +386,8 @@ constexpr int FKS_PSTR = H + 4;                             // row stride of a p
 __host__ __device__ constexpr int fks_lds_bytes(int D) {
     return 3 * 16 * D * 2 + 4 * 16 * FKS_PSTR * 4 + 16 * GATE_STR * 4 + 16 * 4 * 4 + 4 * GATE_STR * 4;
 }
+// (the score pass's ring form sizes its LDS to leave room for one of these workgroups on its CU: moc_scores_plan.h)
+static_assert(fks_lds_bytes(512) == (int)SCORE_RING_BESIDE_LDS, "moc_scores_plan.h restates fks_lds_bytes(512)");
 // The gate chain's operands in LDS: the hidden tile Hs [16] and W2 [4], rows of H floats at a stride of GATE_STR = H + 4
 // floats -- 17 sixteen-byte slots, so chunk c of row r lies in slot (r + c) mod 16 of the 256-byte bank row.  The one wave
 // that forms the 16 x 4 gates (lane = row * 4 + gate) reads a row as sixteen ds_read_b128 at immediate offsets from one

@@ -64,13 +64,48 @@ static inline int score_banks_max(int D, int dtype) {
     return g;
 }
 
-enum { SCORE_STREAM, SCORE_WIDE_RING, SCORE_WIDE, SCORE_GENERIC };
+// ---- the LDS-DMA ring form (scores_ring_kernel, moc_scores_ring.hip): fp32 bags, one n-tile, one persistent workgroup
+// per CU of one loader wave and three consumer waves.  The loader moves 16-row x 1 KiB units (the streaming form's unit:
+// sixteen 1 KiB A fragments) into ring slots by LDS-DMA; nothing of a tile lives in registers, so the workgroup is small
+// enough in registers AND in LDS to share its CU with the training forward.  Its dynamic LDS:
+//   [image][slots x 16 KiB][3 waves x 16 x 17 floats][n x 8 B first slot | n x 8 B first X row | (n + 1) x 4 B tile prefix
+//   | n x 4 B kept rows][pad to 16][slots x 16 B tile descriptor][slots x 4 B FULL][slots x 4 B FREE]
+// The slot count is what is left of the CU's LDS beside ONE workgroup of the training forward at D = 512
+// (fks_lds_bytes(512), moc_meta_forward.hip, which asserts the figure here): at D = 256 and 32 slides four slots, at
+// D = 512 three.  (The step kernels' launch limit, lds::TILE_MAX_LDS, is the whole CU and leaves room for nothing; a step
+// workgroup of the benchmark's shape holds 39 KiB and fits in the same room.)  Fewer than three slots -- one in flight,
+// one published, one being read -- and the form does not apply.
+constexpr size_t SCORE_RING_BESIDE_LDS = 72256;     // fks_lds_bytes(512)
+constexpr size_t SCORE_RING_SLOT = 16 * 1024;
+constexpr int SCORE_RING_SLOTS_MIN = 3, SCORE_RING_SLOTS_MAX = 8;
+struct RingLds {
+    size_t img;
+    int n, slots;
+    size_t ring() const { return img; }
+    size_t tiles() const { return ring() + slots * SCORE_RING_SLOT; }
+    size_t meta() const { return tiles() + (size_t)3 * 16 * 17 * sizeof(float); }
+    size_t desc() const { return (meta() + (size_t)24 * n + 4 + 15) & ~(size_t)15; }
+    size_t full() const { return desc() + (size_t)16 * slots; }
+    size_t free_() const { return full() + (size_t)4 * slots; }
+    size_t bytes() const { return free_() + (size_t)4 * slots; }
+};
+// slots of a launch over n slides (0: the ring form does not apply)
+constexpr int score_ring_slots(size_t img, int n) {
+    const size_t fixed = img + (size_t)3 * 16 * 17 * sizeof(float) + (size_t)24 * n + 4 + 15;
+    const size_t room = SCORE_MAX_LDS - SCORE_RING_BESIDE_LDS;
+    if (fixed >= room) return 0;
+    const size_t s = (room - fixed) / (SCORE_RING_SLOT + 24);
+    return s < (size_t)SCORE_RING_SLOTS_MIN ? 0 : s > (size_t)SCORE_RING_SLOTS_MAX ? SCORE_RING_SLOTS_MAX : (int)s;
+}
+
+enum { SCORE_STREAM, SCORE_WIDE_RING, SCORE_WIDE, SCORE_GENERIC, SCORE_RING };
 enum {
     SCORE_PLAN_OK,
     SCORE_PLAN_SLIDES_LDS,     // streaming, one n-tile: the slides' metadata does not fit in one launch (`need` bytes)
     SCORE_PLAN_RESERVED,       // reserved compute units without a ticket array
     SCORE_PLAN_ROW_LDS,        // generic: one image and the tiles do not fit (`need` bytes)
-    SCORE_PLAN_NO_STREAM       // banks_entry, and the streaming form does not apply (`need`: one bank, one slide)
+    SCORE_PLAN_NO_STREAM,      // banks_entry, and the streaming form does not apply (`need`: one bank, one slide)
+    SCORE_PLAN_RING_TICKET     // MOC_SCORES_RING with a ticket array or a reserved set: the ring form walks statically, everywhere
 };
 
 struct ScoreShape {
@@ -80,11 +115,12 @@ struct ScoreShape {
     bool ticket, reserved;     // moc_batch_t.tile_ticket / cu_reserved given
     int lookahead_cap;         // workgroups of a launch with a ticket array, at most (0: no cap)
     bool banks_entry;          // moc_scores_banks: the streaming static form or nothing; one n-tile may go in chunks
+    bool ring = false;         // moc_batch_t.flags & MOC_SCORES_RING: the ring form where it applies (fp32, one n-tile)
 };
 
 struct ScorePlan {
     int form;
-    int unit;                  // streaming: NF, 16-byte loads per lane and unit; generic: CH, columns per image chunk
+    int unit;                  // streaming: NF, 16-byte loads per lane and unit; generic: CH, columns per image chunk; ring: slots
     int NT;
     bool ticketed;             // streaming: the ticketed walk, with the batch's reserved set; else both stay out
     size_t smem;
@@ -101,6 +137,24 @@ static inline ScorePlan score_plan(const ScoreShape& q) {
     const size_t img = score_img_bytes(q.D, q.dtype);
     P.NT = q.NT;
     P.gy = 1;
+    // the ring form, only for a batch that asks for it: never beside a ticket or a reserved set (it has no ticketed walk and
+    // needs no free CUs); shapes it does not cover keep the forms below
+    if (q.ring && !q.banks_entry) {
+        if (q.ticket || q.reserved) {
+            P.err = SCORE_PLAN_RING_TICKET;
+            return P;
+        }
+        const int slots = (!bf && q.NT == 1) ? score_ring_slots(img, q.n_slides) : 0;
+        if (slots > 0) {
+            P.form = SCORE_RING;
+            P.unit = slots;
+            P.chunk = q.n_slides;
+            P.smem = RingLds{img, q.n_slides, slots}.bytes();
+            const int64_t tiles = (q.total_rows + 15) / 16 + 2 * (int64_t)q.n_slides;
+            P.gx = tiles < 256 ? (int)tiles : 256;         // one workgroup per CU
+            return P;
+        }
+    }
     // streaming form: persistent workgroups over the flat tile list, the whole bank image (all NT n-tiles) resident in
     // LDS.  Applies while image + epilogue tiles + at least one slide's metadata fit; a batch with more slides than fit
     // beside the image goes out in chunks.

@@ -33,6 +33,23 @@ COMPACT_STATS = os.environ.get("MOC_COMPACT_STATS", "1") != "0"     # wide banks
 # 64 -> 45.6 k, 96 -> 42.9 k meta-steps/s; the ticketed walk alone costs the score pass 7 % (fp32) / 19 % (bf16), so
 # passes with nothing beside them (evaluation) keep the static walk.
 RESERVE_CUS = int(os.environ.get("MOC_RESERVE_CUS", "64"))
+
+
+def score_ring_mode(value):
+    """MOC_SCORE_RING: which score passes ask for the LDS-DMA ring kernel (MOC_SCORES_RING, include/moc_hip.h) -- "0" none,
+    "lookahead" the look-ahead phase A of a train pass (which then takes no ticket and reserves no compute units: the ring
+    kernel shares every CU with the meta-steps), "all" evaluation's fp32 launches against one-n-tile banks as well."""
+    v = (value or "0").strip().lower()
+    if v not in ("0", "lookahead", "all"):
+        raise ValueError(f"MOC_SCORE_RING={value!r}: expected 0, lookahead or all")
+    return v
+
+
+# Default "lookahead": bench.py --gpus 1 --steps 1600 --warmup 160, eight alternating runs in one call -- 59.3 k meta-steps/s
+# (57.2-59.9) against 57.1 k (56.4-58.2) for the register kernel off 64 reserved CUs (profiles/NOTES.md, "The look-ahead
+# score pass as an LDS-DMA ring").  "all" is not measured yet: alone on the chip the ring kernel is 30 % slower than the
+# register kernel, so evaluation keeps the latter.
+SCORE_RING = score_ring_mode(os.environ.get("MOC_SCORE_RING", "lookahead"))
 # the training step pools among the forward's tile records (moc_meta_ws_t.tile_ws; 0: re-reads every mixed score, round 3)
 TILE_RECORDS = os.environ.get("MOC_TILE_RECORDS", "1") != "0"
 N_SEL_HOST = os.environ.get("MOC_N_SEL_HOST", "1") != "0"            # moc_batch_t.n_sel_mail / n_sel_host for the train steps (0: never, diagnostic)
@@ -166,7 +183,8 @@ def timed_scores(batch, bank):
     e1.record()
     h0, h1 = e0.cuda_event, e1.cuda_event
     assert h0 and h1, "torch did not hand out the HIP event handles"
-    check(lib().moc_scores_timed(C.byref(batch.c), ptr(bank.image), _stream(), C.c_void_p(h0), C.c_void_p(h1)), "moc_scores_timed")
+    c = batch._score_c() if hasattr(batch, "_score_c") else batch.c
+    check(lib().moc_scores_timed(C.byref(c), ptr(bank.image), _stream(), C.c_void_p(h0), C.c_void_p(h1)), "moc_scores_timed")
     return e0, e1
 
 
@@ -348,6 +366,45 @@ class SlideBatch:
         self.c.tile_ticket = ptr(self.ticket) if use_ticket else None
         self.c.cu_reserved = ptr(self.cu_reserved)
 
+    def use_score_ring(self, on: bool = True):
+        """This batch's score passes ask for the ring kernel (MOC_SCORES_RING): no ticket, no reserved compute units.
+        -> whether moc_scores gives the batch that kernel (fp32 bags, one n-tile, LDS for at least three ring slots); where
+        it does not, the bit is cleared again (static walk, whole chip, until reserve_cus says otherwise).  on=False clears it."""
+        if on:
+            self.reserve_cus(0)
+            self.c.flags |= _lib.MOC_SCORES_RING
+            if lib().moc_scores_form(C.byref(self.c)) == _lib.SCORE_FORM_RING:
+                return True
+        self.c.flags &= ~_lib.MOC_SCORES_RING
+        return False
+
+    def lookahead(self):
+        """For a phase A that runs beside the meta-steps of another pass.  The batch takes the ticket array and the reserved
+        compute units of the register kernel (reserve_cus) either way; where MOC_SCORE_RING asks for the ring kernel and the
+        batch can have it, its score launches go out WITHOUT them and with the ring bit (_score_c) -- the ring kernel shares
+        every CU with the steps.  A caller that takes the ticket off the batch (bench.py's `whole_chip` figure) gets the
+        register kernel's static walk, as before."""
+        self.reserve_cus()
+        self._ring_lookahead = False
+        if SCORE_RING != "0":
+            if self.c.tile_ticket is None:
+                self.use_score_ring()                 # (nothing could be reserved on this device: the bit in the batch itself)
+            else:
+                self._ring_lookahead = True
+                self._ring_lookahead = lib().moc_scores_form(C.byref(self._score_c())) == _lib.SCORE_FORM_RING
+
+    _ring_lookahead = False
+
+    def _score_c(self):
+        """The moc_batch_t a score launch gets: the batch's own, or for a look-ahead batch in ring mode a copy with
+        MOC_SCORES_RING and neither ticket nor reserved set."""
+        if not self._ring_lookahead or self.c.tile_ticket is None:
+            return self.c
+        v = MocBatch.from_buffer_copy(self.c)
+        v.flags |= _lib.MOC_SCORES_RING
+        v.tile_ticket = v.cu_reserved = None
+        return v
+
     def set_mask(self, host_mask_u8: torch.Tensor, kept_rows: int):
         """New keep flags for the same visits (next epoch): async H2D into the resident mask array."""
         assert self.mask is not None and host_mask_u8.numel() == self.total and host_mask_u8.dtype == torch.uint8
@@ -377,7 +434,10 @@ class SlideBatch:
         """Statistics layout of the next score pass and of what reads it (include/moc_hip.h MOC_STATS_COMPACT);
         cand_from_stats: an evaluation pass -- the forward reads the candidate scores from the statistics, the
         [2C+2, S] candidate columns of wide banks are never written (MOC_CAND_FROM_STATS)."""
-        self.c.flags = ((_lib.MOC_STATS_COMPACT if compact else 0) | (_lib.MOC_CAND_FROM_STATS if cand_from_stats else 0) |
+        ring = self.c.flags & _lib.MOC_SCORES_RING
+        if SCORE_RING == "all" and self.c.dtype == _lib.MOC_F32 and self.Ce <= 16 and not self.c.tile_ticket and not self.c.cu_reserved:
+            ring = _lib.MOC_SCORES_RING            # (shapes the ring kernel does not cover keep their kernels: moc_scores_plan.h)
+        self.c.flags = ((_lib.MOC_STATS_COMPACT if compact else 0) | (_lib.MOC_CAND_FROM_STATS if cand_from_stats else 0) | ring |
                         (self.c.flags & (_lib.MOC_SELECT_PER_COLUMN | _lib.MOC_FORWARD_ROWS64 | _lib.MOC_FORWARD_FOUR_WAVES | _lib.MOC_FORWARD_ROWS16)))
 
     def _eval_layout(self, compact: bool):
@@ -392,7 +452,7 @@ class SlideBatch:
         (self._eval_layout if for_eval else self._layout)(COMPACT_STATS and self.Ce > 16)
         self._n_sel_stale()
         if SCORE_EVENTS is None and self.stats_cache is None:
-            check(lib().moc_phase_a(C.byref(self.c), ptr(bank.image), _stream()), "moc_phase_a")
+            check(lib().moc_phase_a(C.byref(self._score_c()), ptr(bank.image), _stream()), "moc_phase_a")
             return
         # same four launches, with events around the score pass
         check(lib().moc_mask_compact(C.byref(self.c), _stream()), "moc_mask_compact")
@@ -455,7 +515,7 @@ class SlideBatch:
             assert compact == bool(self.c.flags & _lib.MOC_STATS_COMPACT) and cache.size(1) == self.X.size(0)
             check(lib().moc_scores_from_cache(C.byref(self.c), ptr(cache), cache.size(1), _stream()), "moc_scores_from_cache")
         elif SCORE_EVENTS is None:
-            check(lib().moc_scores(C.byref(self.c), ptr(bank.image), _stream()), "moc_scores")
+            check(lib().moc_scores(C.byref(self._score_c()), ptr(bank.image), _stream()), "moc_scores")
         else:
             e0, e1 = timed_scores(self, bank)
             SCORE_EVENTS.append((e0, e1, self.kept_rows_host * self.D * self.X.element_size()))

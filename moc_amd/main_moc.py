@@ -227,11 +227,12 @@ class ResidentBags:
                 for b in batches:
                     b.stats_cache = self._stats_caches[ck][0]
             if PREFETCH_PHASE_A and Ce <= 16 and not self.loader_seed_draw and not self.cache_scores:     # (loader_seed_draw: phase A always runs in line)
-                # phase A runs beside the meta-steps of the pass before: leave them CUs.  (Banks of one n-tile only: wider
+                # phase A runs beside the meta-steps of the pass before: leave them CUs, or (MOC_SCORE_RING) share every CU
+                # with them.  (Banks of one n-tile only: wider
                 # ones run ONE score workgroup per CU -- thirty classes with 64 CUs left free: score pass 242 -> 447 us,
                 # 18.9 -> 18.8 k meta-steps/s.)
                 for b in batches:
-                    b.reserve_cus()
+                    b.lookahead()
             lab = torch.tensor([self.labels[k] for k in order], dtype=torch.int64).to(self.X.device)
             stage = [torch.empty(T, dtype=torch.uint8).pin_memory() for _ in range(2)]     # (only when torch itself must draw)
             drawer = engine.MaskDrawer(T, batches[0]._row_off_c, len(sizes))
