@@ -173,7 +173,17 @@ typedef struct moc_meta {
                                          MFMA operand order for the forward pass, three 16-bit terms
                                          per weight for every storage (ABI 19).  Derived data the
                                          library rebuilds / keeps in sync itself; contents need not
-                                         survive between calls.                                */
+                                         survive between calls.
+                                         RANGE, fp16 bags only: the fp16 image holds the three fp16 terms
+                                         of w * 2^10, so every |W1[i]| must stay below 32 (beyond 64 the
+                                         high term overflows fp16).  This is the CALLER's contract: the
+                                         library does not check it -- the step kernels rewrite W1 and its
+                                         image on the device, and a check would cost a host round trip
+                                         per step.  nn.Linear starts at |w| <= 1/sqrt(D); a caller whose
+                                         weights can grow that far keeps its bags in bf16 or fp32, whose
+                                         images have fp32's exponent range (no such limit).  The
+                                         classifier bank's fp16 limit, |w| < 2, IS checked
+                                         (moc_prepare_bank).                                    */
     double lr, beta1, beta2, eps, weight_decay; /* the optimizer's Python floats, unrounded     */
     int32_t H;                        /* hidden width, must be 64                          */
     int32_t D;                        /* input width (== batch D)                          */

@@ -112,6 +112,30 @@ def test_fp32_forward_error_bound_against_float64(dev, D, train):
     assert float(err.mean()) <= 2 * float(old_err.mean()), (float(err.mean()), float(old_err.mean()))
 
 
+@pytest.mark.parametrize("scale", [2.0 ** -6, 0.3, 5.0, 32.0])
+@pytest.mark.parametrize("D", [256, 512])
+@pytest.mark.parametrize("train", [True, False])
+def test_fp32_forward_error_bound_at_scale(dev, D, train, scale):
+    """The bound above with rows times `scale` and b1 as initialised.  It is relative above 1 already and 1e-6 absolute
+    below; that form is kept, and the absolute part takes the factor max(1, scale) for the product term -- the rounding
+    of x W1^T grows with the products' size, not with that of a pre-activation that cancels or that b1 dominates:
+    |error| <= 1e-6 max(|pre|, max(1, scale)).  The "within twice the fp32 chain" clause stays as it is."""
+    n_slides, rows = (1, 300) if train else (4, 1024)
+    x, W1, b1, h1, _ = _h1_of(dev, D, n_slides, rows, 11 + D, scale=scale)
+    pre64 = x.astype(np.float64) @ W1.T.astype(np.float64) + b1.astype(np.float64)
+    ref = np.maximum(pre64, 0.0)
+    err = np.abs(h1.astype(np.float64) - ref)
+    bound = 1e-6 * max(1.0, D / 512)
+    worst = float((err / np.maximum(np.abs(pre64), max(1.0, scale))).max())
+    old = np.maximum((_fp32_chain(x, W1) + b1).astype(np.float32).astype(np.float64), 0.0)
+    old_err = np.abs(old - ref)
+    print(f"scale {scale:g}: max |pre| {float(np.abs(pre64).max()):.3g}, error {float(err.max()):.3e} (fp32 chain {float(old_err.max()):.3e}), "
+          f"worst / bound {worst / bound:.3f}")
+    assert worst <= bound, float(err.max())
+    assert float(err.max()) <= 2 * float(old_err.max()), (float(err.max()), float(old_err.max()))
+    assert float(err.mean()) <= 2 * float(old_err.mean()), (float(err.mean()), float(old_err.mean()))
+
+
 @pytest.mark.parametrize("D", [256, 512, 1024])
 def test_w1_image_is_the_three_term_split_after_the_image_kernel(dev, D):
     _, W1, _, _, meta = _h1_of(dev, D, 1, 64, 5)

@@ -116,6 +116,30 @@ def test_ring_slots_wrap_and_idle_workgroups_end(dev, D, N):
         _same_bits(E, X, [N], Cn, bank, m)
 
 
+@pytest.mark.parametrize("D", [256, 512])
+def test_ring_kernel_over_more_than_64_slides_with_empty_ones(dev, D):
+    """150 slides of 1 ... 40 rows (production batches have hundreds): the tile prefix scan carries across its 64-slide
+    chunks, and under a half mask that leaves some slides without a kept row the loader gallops over empty slides."""
+    E = _engine()
+    Cn, n = 2, 150
+    g = torch.Generator().manual_seed(8)
+    sizes = torch.randint(1, 41, (n,), generator=g).tolist()
+    sizes[:6] = [1, 1, 2, 40, 1, 1]
+    W, We = synth.make_bank(101, D, Cn)
+    X = synth.make_bag(102 + D, sum(sizes), D, We, Cn, label=0).to(dev).contiguous()
+    bank = E.Bank.get(W.to(dev), We.to(dev), torch.float32, dev)
+    half = (torch.rand(sum(sizes), generator=g) > 0.5).to(torch.uint8)
+    half[0] = 1                                                     # (the first slide keeps its row)
+    off, empty = 0, []
+    for i, s in enumerate(sizes):
+        if int(half[off:off + s].sum()) == 0:
+            empty.append(i)
+        off += s
+    assert len(empty) >= 3 and any(i >= 64 for i in empty) and any(i < 64 for i in empty), "slides without a kept row, in several chunks"
+    for mask in (None, half):
+        _same_bits(E, X, sizes, Cn, bank, mask)
+
+
 def test_shapes_the_ring_kernel_does_not_cover_keep_their_kernels(dev):
     """16-bit bags and banks of more than one n-tile: the bit is accepted and the batch takes the kernel it always took."""
     E = _engine()
