@@ -697,6 +697,35 @@ int moc_nystrom_pinv_backward(const float* A /* [h, m, m] */, int heads, int lan
                               const float* Zs /* [iters + 1, h, m, m] */, const float* dZ /* [h, m, m] */,
                               float* dA /* [h, m, m] */, void* ws, size_t ws_bytes, moc_stream_t stream);
 
+/* TransMIL's PPEG (moc_amd/model_mil.py: PPEG): the depth-wise 7 x 7, 5 x 5 and 3 x 3 convolutions over the H x W token
+ * square, the identity and the three biases in one launch, and their gradients in two.  x, out, dout, dx are
+ * [1 + H W, dim] device fp32, row 0 the class token, row 1 + y W + x_ position (y, x_); w7 [dim, 1, 7, 7], w5 [dim, 1, 5, 5],
+ * w3 [dim, 1, 3, 3] and the biases [dim] as nn.Conv2d stores them.  With zero padding outside the square, p a position:
+ *   out[0]        = x[0]
+ *   out[1 + p, c] = x[1 + p, c] + ((b7[c] + b5[c]) + b3[c]) + sum_{dy, dx in -3..3} w[c, dy, dx] x[1 + p + (dy, dx), c]
+ *                   w = (w7 + pad(w5)) + pad(w3): one 7 x 7 table per channel, the 5 x 5 and the 3 x 3 in its centre
+ *   dx[0]         = dout[0]
+ *   dx[1 + p, c]  = dout[1 + p, c] + sum_{dy, dx} w[c, dy, dx] dout[1 + p - (dy, dx), c]
+ *   G[c, dy, dx]  = sum_p dout[1 + p, c] x[1 + p + (dy, dx), c]
+ *   dw7 = G;  dw5 = G's central 5 x 5;  dw3 = G's central 3 x 3;  db7 = db5 = db3 = sum_p dout[1 + p, c]
+ * Positions outside the square count as zero and are not read.  Every element of out, of dx and of the six gradient
+ * tensors is written; no input is.  An output is one fp32 chain of 49 products; G and the bias sum are added in fp32 over
+ * at most 64 products and in double above that: each block of at least 128 positions leaves 50 doubles per channel in `ws`
+ * (moc_ppeg_backward_workspace bytes: at most 2 MiB while H W < 1,024, below one [H W, 512] fp32 tensor from there on) and
+ * a merge launch adds the blocks in index order and rounds to fp32 once: no atomics, the same bits on every call.  Built
+ * for dim = 512, H, W >= 1, H W <= 2^22.  MOC_EUNSUPPORTED for another dim; MOC_EINVAL for a null or not 16-byte aligned
+ * pointer, H or W below 1 or a product above the limit, a short workspace, out overlapping x, dx overlapping dout or x
+ * (the halo is read after neighbours are written: in place cannot work) -- all before the first launch.  Additive to ABI
+ * 20: the version number is unchanged. */
+int moc_ppeg_forward(const float* x /* [1 + H W, dim] */, int H, int W, int dim, const float* w7, const float* b7,
+                     const float* w5, const float* b5, const float* w3, const float* b3, float* out /* [1 + H W, dim] */,
+                     moc_stream_t stream);
+size_t moc_ppeg_backward_workspace(int H, int W, int dim);            /* 0: unsupported shape */
+int moc_ppeg_backward(const float* x /* [1 + H W, dim] */, int H, int W, int dim, const float* w7, const float* w5,
+                      const float* w3, const float* dout /* [1 + H W, dim] */, float* dx /* [1 + H W, dim] */, float* dw7,
+                      float* db7, float* dw5, float* db5, float* dw3, float* db3, void* ws, size_t ws_bytes,
+                      moc_stream_t stream);
+
 /* a10-a15 fused: `n` consecutive meta-steps (one slide each, slides slide0..slide0+n-1 in
  * order, one Adam step per slide: main_moc.py:380-410), parameters and Adam moments
  * updated in place.  Per-slide loss/pooled land in ws->loss / ws->pooled. */

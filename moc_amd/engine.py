@@ -1578,3 +1578,60 @@ def nystrom_pinv_backward(attn2: torch.Tensor, Zs: torch.Tensor, dZ: torch.Tenso
     check(lib().moc_nystrom_pinv_backward(ptr(attn2), NYSTROM_HEADS, NYSTROM_LANDMARKS, iters, ptr(Zs), ptr(dZ), ptr(dA), ptr(ws),
                                           nbytes, _stream()), "moc_nystrom_pinv_backward")
     return dA
+
+
+PPEG_DIM, PPEG_MAX_POSITIONS = 512, 1 << 22                                            # what moc_ppeg_* is built for
+
+
+def _ppeg_tokens(t: torch.Tensor, H: int, W: int, name: str, what: str) -> torch.Tensor:
+    assert t.is_cuda and t.dtype == torch.float32, f"{what}: fp32 tensors on the GPU (no CPU fallback)"
+    assert H >= 1 and W >= 1 and H * W <= PPEG_MAX_POSITIONS, f"{what}: H={H} W={W} must be at least 1, H W at most 2^22"
+    n = 1 + H * W
+    assert t.shape in ((n, PPEG_DIM), (1, n, PPEG_DIM)), f"{what}: {name} must be [1 + H W, 512] (or [1, 1 + H W, 512])"
+    return t.detach().contiguous()
+
+
+def _ppeg_params(ws, bs, what: str):
+    out = []
+    for k, w in zip((7, 5, 3), ws):
+        assert w.is_cuda and w.dtype == torch.float32, f"{what}: fp32 tensors on the GPU (no CPU fallback)"
+        assert w.shape == (PPEG_DIM, 1, k, k), f"{what}: w{k} must be [512, 1, {k}, {k}]"
+        out.append(w.detach().contiguous())
+    for k, b in zip((7, 5, 3), bs):
+        assert b.is_cuda and b.dtype == torch.float32, f"{what}: fp32 tensors on the GPU (no CPU fallback)"
+        assert b.shape == (PPEG_DIM,), f"{what}: b{k} must be [512]"
+        out.append(b.detach().contiguous())
+    return out
+
+
+def ppeg_forward(x: torch.Tensor, H: int, W: int, w7, b7, w5, b5, w3, b3) -> torch.Tensor:
+    """TransMIL's PPEG in one launch (moc_ppeg_forward): from x [1 + H W, 512] (or [1, 1 + H W, 512]), row 0 the class token,
+    and the three depth-wise convolutions' weights [512, 1, k, k] and biases [512], out of x's shape with
+    out[0] = x[0], out[1 + p] = x[1 + p] + (b7 + b5 + b3) + the 7 x 7, 5 x 5 and 3 x 3 convolutions at position p.  No gradient."""
+    what = "ppeg_forward"
+    H, W = int(H), int(W)
+    xc = _ppeg_tokens(x, H, W, "x", what)
+    w7, w5, w3, b7, b5, b3 = _ppeg_params((w7, w5, w3), (b7, b5, b3), what)
+    out = torch.empty_like(xc)
+    check(lib().moc_ppeg_forward(ptr(xc), H, W, PPEG_DIM, ptr(w7), ptr(b7), ptr(w5), ptr(b5), ptr(w3), ptr(b3), ptr(out),
+                                 _stream()), "moc_ppeg_forward")
+    return out
+
+
+def ppeg_backward(x: torch.Tensor, H: int, W: int, w7, w5, w3, dout: torch.Tensor):
+    """Backward of ppeg_forward (moc_ppeg_backward): (dx, dw7, db7, dw5, db5, dw3, db3) from its x, its three weights and dout
+    of x's shape.  dx has x's shape; the weight gradients are the three windows of one 7 x 7 table of sums and the three
+    bias gradients are one sum, added in double above 64 products in a fixed order: two calls give the same bits."""
+    what = "ppeg_backward"
+    H, W = int(H), int(W)
+    xc, dc = _ppeg_tokens(x, H, W, "x", what), _ppeg_tokens(dout, H, W, "dout", what)
+    assert dc.shape == xc.shape, f"{what}: dout must have x's shape"
+    w7, w5, w3 = _ppeg_params((w7, w5, w3), (), what)
+    dx = torch.empty_like(xc)
+    dw7, dw5, dw3 = torch.empty_like(w7), torch.empty_like(w5), torch.empty_like(w3)
+    db7, db5, db3 = (torch.empty(PPEG_DIM, dtype=torch.float32, device=xc.device) for _ in range(3))
+    nbytes = lib().moc_ppeg_backward_workspace(H, W, PPEG_DIM)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=xc.device)
+    check(lib().moc_ppeg_backward(ptr(xc), H, W, PPEG_DIM, ptr(w7), ptr(w5), ptr(w3), ptr(dc), ptr(dx), ptr(dw7), ptr(db7),
+                                  ptr(dw5), ptr(db5), ptr(dw3), ptr(db3), ptr(ws), nbytes, _stream()), "moc_ppeg_backward")
+    return dx, dw7, db7, dw5, db5, dw3, db3

@@ -7,7 +7,8 @@ through the picked row only, as in the reference.  Parameter names match (`class
 moc_amd/nystrom.py; parity unpinned: the reference's own class cannot be built without the absent third-party
 package) keeps the contract (logits, Y_prob, Y_hat, None, None); its switches `fused`, `fused_pinv`, `fused_train`, `fused_conv`
 and `fused_pinv_train` (all off by default) put its two attention layers on the HIP kernels of moc_nystrom*.hip -- the no-grad passes, their
-pseudo-inverse, and the passes that want a gradient."""
+pseudo-inverse, and the passes that want a gradient; `fused_ppeg` (off by default, a switch of its own) puts `pos_layer` on
+moc_ppeg.hip."""
 from __future__ import annotations
 
 import numpy as np
@@ -111,8 +112,34 @@ class TransLayer(nn.Module):
         return x + self.attn(self.norm(x))
 
 
+class PPEGFused(torch.autograd.Function):
+    """PPEG on moc_ppeg.hip for passes that want a gradient: the forward is engine.ppeg_forward's launch, bit for bit the
+    no-grad pass; it keeps x and the three weights, and the backward is engine.ppeg_backward (one 49-tap pass over dout
+    with the table read backwards, and 50 sums per channel)."""
+
+    @staticmethod
+    def forward(ctx, x, H, W, w7, b7, w5, b5, w3, b3):
+        from . import engine
+        ctx.save_for_backward(x, w7, w5, w3)
+        ctx.hw = (H, W)
+        return engine.ppeg_forward(x, H, W, w7, b7, w5, b5, w3, b3)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        from . import engine
+        x, w7, w5, w3 = ctx.saved_tensors
+        dx, dw7, db7, dw5, db5, dw3, db3 = engine.ppeg_backward(x, ctx.hw[0], ctx.hw[1], w7, w5, w3, dout)
+        return dx, None, None, dw7, db7, dw5, db5, dw3, db3
+
+
 class PPEG(nn.Module):
-    """models/model_mil.py:125-139: depth-wise 7 / 5 / 3 convolutions over the patch tokens laid out as a square."""
+    """models/model_mil.py:125-139: depth-wise 7 / 5 / 3 convolutions over the patch tokens laid out as a square.
+    `fused = True` (off by default) takes the whole module -- the three convolutions, the identity, the biases and the
+    class-token row -- from moc_ppeg.hip where `_fusable` holds, with and without a gradient; everything else is the
+    torch code below, bit for bit."""
+
+    fused = False
 
     def __init__(self, dim=512):
         super().__init__()
@@ -120,7 +147,28 @@ class PPEG(nn.Module):
         self.proj1 = nn.Conv2d(dim, dim, 5, 1, 5 // 2, groups=dim)
         self.proj2 = nn.Conv2d(dim, dim, 3, 1, 3 // 2, groups=dim)
 
+    def _fusable(self, x, H, W) -> bool:
+        """x a contiguous fp32 CUDA [1, 1 + H W, 512]; all six parameters fp32 CUDA; the three convolutions as built."""
+        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.shape[0] == 1 and x.shape[2] == 512
+                and H >= 1 and W >= 1 and x.shape[1] == 1 + H * W and H * W <= (1 << 22) and x.is_contiguous()):
+            return False
+        for conv, k in ((self.proj, 7), (self.proj1, 5), (self.proj2, 3)):
+            if not (conv.kernel_size == (k, k) and conv.padding == (k // 2, k // 2) and conv.groups == 512
+                    and conv.stride == (1, 1) and conv.dilation == (1, 1) and conv.padding_mode == "zeros"
+                    and conv.bias is not None and conv.weight.shape == (512, 1, k, k)):
+                return False
+            for p in (conv.weight, conv.bias):
+                if not (p.is_cuda and p.dtype == torch.float32):
+                    return False
+        return True
+
     def forward(self, x, H, W):
+        if self.fused and self._fusable(x, H, W):
+            params = (self.proj.weight, self.proj.bias, self.proj1.weight, self.proj1.bias, self.proj2.weight, self.proj2.bias)
+            if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
+                return PPEGFused.apply(x, H, W, *params)
+            from . import engine
+            return engine.ppeg_forward(x, H, W, *params)
         B, _, C = x.shape
         cls_token, feat_token = x[:, 0], x[:, 1:]
         cnn_feat = feat_token.transpose(1, 2).view(B, C, H, W)
@@ -198,6 +246,16 @@ class TransMIL(nn.Module):
     @fused_pinv_train.setter
     def fused_pinv_train(self, on: bool):
         self.layer1.attn.fused_pinv_train = self.layer2.attn.fused_pinv_train = bool(on)
+
+    @property
+    def fused_ppeg(self) -> bool:
+        """`pos_layer` on moc_ppeg.hip (PPEG.fused), with and without a gradient: a switch of its own, which needs none of
+        the attention switches and changes none of them."""
+        return bool(self.pos_layer.fused)
+
+    @fused_ppeg.setter
+    def fused_ppeg(self, on: bool):
+        self.pos_layer.fused = bool(on)
 
     def _tokens(self, data):
         """fc1, wrap-around padding to a square, class token, layer 1, PPEG, layer 2 (:236-266)."""

@@ -15,7 +15,10 @@ TokenValues: the backward of moc_nystrom_bwd.hip recomputes the weights) and aga
 all three with `fused_pinv_train` on top (LandmarkPinv: the pseudo-inverse and its gradient on moc_nystrom_pinv.hip), all four
 in the same run and timed the same way, each with the peak of torch.cuda.max_memory_allocated over one step, above what was
 allocated before it.  Then each backward entry alone against its two bounds, and the torch pieces all paths share, each
-alone, forward + backward: res_conv, moore_penrose_iter_pinv, to_qkv, and the model's pos_layer (PPEG); beside
+alone, forward + backward: res_conv, moore_penrose_iter_pinv, to_qkv, and the model's pos_layer (PPEG) -- that one also on
+moc_ppeg.hip (`PPEG.fused`), with the two entries alone against the bytes they must move, and the whole model with
+`fused_ppeg` on top of the other four switches; without --train the no-grad model pass and pos_layer with and without
+`fused_ppeg`; beside
 moore_penrose_iter_pinv, on the same attn2, moc_nystrom_pinv_iterates + moc_nystrom_pinv_backward with independent products
 sharing launches (the default) and with one product per launch.
 
@@ -88,13 +91,16 @@ def kernel(label, fn, nbytes, flops, iters, warmup):
     return r
 
 
-def train_pair(label, step, switch, iters, warmup):
+def train_pair(label, step, switch, iters, warmup, ppeg=False):
     """step() -- one forward + backward -- timed and its peak memory taken on the torch path, with `fused` + `fused_train`,
-    with `fused_conv` on top of those, and with `fused_pinv_train` on top of all three; switch(fused_train, fused_conv,
-    fused_pinv_train) sets the flags."""
+    with `fused_conv` on top of those, with `fused_pinv_train` on top of all three and, for the model (`ppeg`), with
+    `fused_ppeg` on top of all four; switch(fused_train, fused_conv, fused_pinv_train, fused_ppeg) sets the flags."""
     r = {}
-    for key, flags in (("torch", (False, False, False)), ("fused_train", (True, False, False)), ("fused_conv", (True, True, False)),
-                       ("fused_pinv_train", (True, True, True))):
+    configs = [("torch", (False, False, False, False)), ("fused_train", (True, False, False, False)),
+               ("fused_conv", (True, True, False, False)), ("fused_pinv_train", (True, True, True, False))]
+    if ppeg:
+        configs.append(("fused_ppeg", (True, True, True, True)))
+    for key, flags in configs:
         switch(*flags)
         r[key] = times_us(step, iters, warmup)
         torch.cuda.synchronize()
@@ -104,7 +110,7 @@ def train_pair(label, step, switch, iters, warmup):
         step()
         torch.cuda.synchronize()
         r[key]["peak_bytes"] = torch.cuda.max_memory_allocated() - base
-    switch(False, False, False)
+    switch(False, False, False, False)
     t, f, c, p = r["torch"], r["fused_train"], r["fused_conv"], r["fused_pinv_train"]
     r["fused_train_is_faster"] = f["median_us"] < t["min_us"]
     r["fused_conv_is_faster_than_fused_train"] = c["median_us"] < f["min_us"]
@@ -121,7 +127,35 @@ def train_pair(label, step, switch, iters, warmup):
           f"{p['peak_bytes'] / 2**20:8.1f} MiB   "
           f"{'faster than fused_conv' if r['fused_pinv_train_is_faster_than_fused_conv'] else 'NOT faster than fused_conv'} "
           f"(x{c['median_us'] / p['median_us']:.2f} on the medians, x{t['median_us'] / p['median_us']:.2f} on the torch path's)")
+    if ppeg:
+        q = r["fused_ppeg"]
+        r["fused_ppeg_is_faster_than_fused_pinv_train"] = q["median_us"] < p["min_us"]
+        print(f"{'':32s}  ... + fused_ppeg median {q['median_us']:9.1f} us (min {q['min_us']:9.1f}) peak "
+              f"{q['peak_bytes'] / 2**20:8.1f} MiB   "
+              f"{'faster than fused_pinv_train' if r['fused_ppeg_is_faster_than_fused_pinv_train'] else 'NOT faster than fused_pinv_train'} "
+              f"(x{p['median_us'] / q['median_us']:.2f} on the medians, x{t['median_us'] / q['median_us']:.2f} on the torch path's)")
     return r
+
+
+def stream_kernel(label, fn, nbytes, iters, warmup):
+    """A kernel with no matrix products (moc_ppeg_*) against the bytes it must move."""
+    r = times_us(fn, iters, warmup)
+    sec = r["median_us"] * 1e-6
+    r.update(bytes=nbytes, bytes_per_s=nbytes / sec, hbm_bound_us=nbytes / HBM_PEAK * 1e6)
+    r["fraction_of_bound"] = r["hbm_bound_us"] / r["median_us"]
+    print(f"{label:24s}: median {r['median_us']:8.1f} us (min {r['min_us']:8.1f})   {nbytes / 1e6:6.1f} MB at "
+          f"{r['bytes_per_s'] / 1e9:.0f} GB/s (bound {r['hbm_bound_us']:.1f} us)   {r['fraction_of_bound']:.2f} of the bound")
+    return r
+
+
+def ppeg_entries(ppeg, x, side, cot, out, iters, warmup):
+    """The two PPEG entries alone on x [1, 1 + side^2, 512].  Bytes: the forward reads x and writes out, the backward reads x
+    and dout and writes dx; weights, gradients of weights and the workspace are below 1% of either."""
+    row = x.shape[1] * 512 * 4
+    p = [t.detach() for t in (ppeg.proj.weight, ppeg.proj.bias, ppeg.proj1.weight, ppeg.proj1.bias, ppeg.proj2.weight, ppeg.proj2.bias)]
+    out["ppeg_forward"] = stream_kernel("moc_ppeg_forward", lambda: engine.ppeg_forward(x, side, side, *p), 2 * row, iters, warmup)
+    out["ppeg_backward"] = stream_kernel("moc_ppeg_backward", lambda: engine.ppeg_backward(x, side, side, p[0], p[2], p[4], cot),
+                                         3 * row, iters, warmup)
 
 
 def piece(label, step, iters, warmup):
@@ -140,8 +174,9 @@ def train(a, dev, g, bag, model, attn, out):
     label = torch.tensor([1], device=dev)
 
     def flags(module):
-        return lambda on, conv, pinv: (setattr(module, "fused", on), setattr(module, "fused_train", on),
-                                       setattr(module, "fused_conv", conv), setattr(module, "fused_pinv_train", pinv))
+        return lambda on, conv, pinv, ppeg: (setattr(module, "fused", on), setattr(module, "fused_train", on),
+                                             setattr(module, "fused_conv", conv), setattr(module, "fused_pinv_train", pinv),
+                                             hasattr(module, "pos_layer") and setattr(module, "fused_ppeg", ppeg))
 
     def layer_step():
         attn.zero_grad(set_to_none=True)
@@ -151,7 +186,7 @@ def train(a, dev, g, bag, model, attn, out):
     def model_step():
         model.zero_grad(set_to_none=True)
         torch.nn.functional.cross_entropy(model(bag)[0], label).backward()
-    out["train_model"] = train_pair(f"TransMIL {a.n} x 512, fwd + bwd", model_step, flags(model), a.iters, a.warmup)
+    out["train_model"] = train_pair(f"TransMIL {a.n} x 512, fwd + bwd", model_step, flags(model), a.iters, a.warmup, ppeg=True)
     out["train_layer"] = train_pair(f"one layer, {n_tok} tokens, fwd + bwd", layer_step, flags(attn), a.iters, a.warmup)
 
     # each backward entry alone against its two bounds.  Bytes: qkv's columns it reads, twice (once per kernel), dout likewise,
@@ -222,6 +257,16 @@ def train(a, dev, g, bag, model, attn, out):
     ppeg = model.pos_layer
     out["piece_pos_layer"] = piece(f"pos_layer (PPEG) on [1, {n_tok}, 512]",
                                    backward_of(lambda: ppeg(xt, side, side), xt, *ppeg.parameters()), a.iters, a.warmup)
+    # the same on moc_ppeg.hip (PPEG.fused), then its two entries alone
+    ppeg.fused = True
+    out["piece_pos_layer_fused"] = piece("pos_layer (PPEG), fused", backward_of(lambda: ppeg(xt, side, side), xt, *ppeg.parameters()),
+                                         a.iters, a.warmup)
+    ppeg.fused = False
+    tp, fp = out["piece_pos_layer"], out["piece_pos_layer_fused"]
+    out["pos_layer_fused_is_faster"] = fp["median_us"] < tp["min_us"]
+    print(f"{'':32s}  fused {'faster' if out['pos_layer_fused_is_faster'] else 'NOT faster'} than torch "
+          f"(x{tp['median_us'] / fp['median_us']:.2f} on the medians)")
+    ppeg_entries(ppeg, x, side, cot, out, a.iters, a.warmup)
 
 
 def main():
@@ -290,6 +335,22 @@ def main():
         out["pinv_is_faster"] = k["median_us"] < t["min_us"]
         print(f"{'moore_penrose_iter_pinv':24s}: median {t['median_us']:8.1f} us (min {t['min_us']:8.1f})   moc_nystrom_pinv "
               f"{'faster' if out['pinv_is_faster'] else 'NOT faster'} (x{t['median_us'] / k['median_us']:.2f} on the medians)")
+        # the no-grad model pass with `fused` + `fused_pinv`, without and with `fused_ppeg` on top; pos_layer alone likewise
+        model.fused = model.fused_pinv = True
+        ppeg = model.pos_layer
+        for key, fn in (("model", lambda: model(bag)), ("pos_layer", lambda: ppeg(x, side, side))):
+            r = {}
+            for on in (False, True):
+                model.fused_ppeg = on
+                r["fused_ppeg" if on else "torch_ppeg"] = times_us(fn, a.iters, a.warmup)
+            t, f = r["torch_ppeg"], r["fused_ppeg"]
+            r["fused_ppeg_is_faster"] = f["median_us"] < t["min_us"]
+            out["nograd_ppeg_" + key] = r
+            print(f"{'no-grad ' + key:24s}: torch pos_layer median {t['median_us']:9.1f} us (min {t['min_us']:9.1f})   fused_ppeg median "
+                  f"{f['median_us']:9.1f} us (min {f['min_us']:9.1f})   {'fused_ppeg faster' if r['fused_ppeg_is_faster'] else 'NOT faster'} "
+                  f"(x{t['median_us'] / f['median_us']:.2f} on the medians)")
+        model.fused = model.fused_pinv = model.fused_ppeg = False
+        ppeg_entries(ppeg, x, side, torch.randn(1, n_tok, 512, generator=g).to(dev), out, a.iters, a.warmup)
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
         with open(a.json, "w") as f:
