@@ -697,6 +697,20 @@ int moc_nystrom_pinv_backward(const float* A /* [h, m, m] */, int heads, int lan
                               const float* Zs /* [iters + 1, h, m, m] */, const float* dZ /* [h, m, m] */,
                               float* dA /* [h, m, m] */, void* ws, size_t ws_bytes, moc_stream_t stream);
 
+/* Rows of the same layer's attention matrix attn1 pinv attn3, for attention maps (moc_amd/nystrom.py:
+ * NystromAttention.forward_rows).  With lse what moc_nystrom_landmark_values_lse returns for the same qkv and q_l, and
+ * coef[h, r, :] = softmax_256(scale q[i_r, h] k_l[h]^T) pinv[h] the caller's 256-vector per head and wanted row i_r:
+ *   out[h, r, j] = sum_m coef[h, r, m] exp(q_l[h, m] . k[j, h] - lse[h, m])          r < R, j < n_pad
+ * One launch of one workgroup per head and 256 tokens; attn3, the [8, 256, n_pad] score matrix, is not formed; no running
+ * maximum (s - lse <= 0 up to rounding), no workspace, no atomics: the same bits on every call.  Every output is four fp32
+ * chains (landmark tile lt in chain lt & 3, in index order) added pairwise.  Every element of out [8, R, n_pad] is written; no input is.
+ * MOC_EUNSUPPORTED for another head, landmark or dim_head shape and for n_pad above 2^22; MOC_EINVAL for n_pad not a positive
+ * multiple of 256, R outside 1..16, a null or not 16-byte aligned pointer, out overlapping qkv, q_l, lse or coef -- all
+ * before the launch.  Additive to ABI 20: the version number is unchanged. */
+int moc_nystrom_attention_rows(const float* qkv /* [n_pad, 1536] */, int64_t n_pad, int heads, int dim_head, int landmarks,
+                               const float* q_l /* [8, 256, 64], scaled */, const float* lse /* [8, 256] */,
+                               const float* coef /* [8, R, 256] */, int R, float* out /* [8, R, n_pad] */, moc_stream_t stream);
+
 /* TransMIL's PPEG (moc_amd/model_mil.py: PPEG): the depth-wise 7 x 7, 5 x 5 and 3 x 3 convolutions over the H x W token
  * square, the identity and the three biases in one launch, and their gradients in two.  x, out, dout, dx are
  * [1 + H W, dim] device fp32, row 0 the class token, row 1 + y W + x_ position (y, x_); w7 [dim, 1, 7, 7], w5 [dim, 1, 5, 5],

@@ -162,6 +162,7 @@ SIGNATURES = {
     "moc_nystrom_pinv_iterates": (C.c_int, [_p, C.c_int, C.c_int, C.c_int, _p, _p, C.c_size_t, _p]),
     "moc_nystrom_pinv_backward_workspace": (C.c_size_t, [C.c_int, C.c_int]),
     "moc_nystrom_pinv_backward": (C.c_int, [_p, C.c_int, C.c_int, C.c_int, _p, _p, _p, _p, C.c_size_t, _p]),
+    "moc_nystrom_attention_rows": (C.c_int, [_p, C.c_int64, C.c_int, C.c_int, C.c_int, _p, _p, _p, C.c_int, _p, _p]),
     "moc_ppeg_forward": (C.c_int, [_p, C.c_int, C.c_int, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p]),
     "moc_ppeg_backward_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "moc_ppeg_backward": (C.c_int, [_p, C.c_int, C.c_int, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,

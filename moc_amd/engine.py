@@ -1580,6 +1580,30 @@ def nystrom_pinv_backward(attn2: torch.Tensor, Zs: torch.Tensor, dZ: torch.Tenso
     return dA
 
 
+NYSTROM_MAX_ROWS = 16                                                                  # rows per moc_nystrom_attention_rows call
+
+
+def nystrom_attention_rows(qkv: torch.Tensor, q_l: torch.Tensor, lse: torch.Tensor, coef: torch.Tensor) -> torch.Tensor:
+    """R rows of the layer's attention matrix attn1 pinv attn3 over all n_pad keys (moc_nystrom_attention_rows): out
+    [8, R, n_pad] with out[h, r, j] = sum_m coef[h, r, m] exp(q_l[h, m] . k[j, h] - lse[h, m]), from qkv [n_pad, 1536], the
+    scaled landmark queries q_l [8, 256, 64], nystrom_landmark_values_lse's lse [8, 256] for the same two, and coef
+    [8, R, 256] = softmax_256(scale q[rows] k_l^T) pinv, 1 <= R <= NYSTROM_MAX_ROWS.  attn3 is not formed; no gradient."""
+    what = "nystrom_attention_rows"
+    n_pad = _nystrom_qkv(qkv, what)
+    q_l = _nystrom_hmd(q_l, "q_l", what)
+    assert lse.is_cuda and lse.dtype == torch.float32 and coef.is_cuda and coef.dtype == torch.float32, \
+        f"{what}: fp32 tensors on the GPU (no CPU fallback)"
+    assert lse.shape == (NYSTROM_HEADS, NYSTROM_LANDMARKS), f"{what}: lse must be [8, 256]"
+    assert coef.dim() == 3 and coef.shape[0] == NYSTROM_HEADS and coef.shape[2] == NYSTROM_LANDMARKS \
+        and 1 <= coef.shape[1] <= NYSTROM_MAX_ROWS, f"{what}: coef must be [8, R, 256] with R in 1..{NYSTROM_MAX_ROWS}"
+    lse, coef = lse.detach().contiguous(), coef.detach().contiguous()
+    R = coef.shape[1]
+    out = torch.empty((NYSTROM_HEADS, R, n_pad), dtype=torch.float32, device=qkv.device)
+    check(lib().moc_nystrom_attention_rows(ptr(qkv.detach()), n_pad, NYSTROM_HEADS, NYSTROM_DIM_HEAD, NYSTROM_LANDMARKS, ptr(q_l),
+                                           ptr(lse), ptr(coef), R, ptr(out), _stream()), "moc_nystrom_attention_rows")
+    return out
+
+
 PPEG_DIM, PPEG_MAX_POSITIONS = 512, 1 << 22                                            # what moc_ppeg_* is built for
 
 

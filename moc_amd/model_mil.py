@@ -8,7 +8,8 @@ moc_amd/nystrom.py; parity unpinned: the reference's own class cannot be built w
 package) keeps the contract (logits, Y_prob, Y_hat, None, None); its switches `fused`, `fused_pinv`, `fused_train`, `fused_conv`
 and `fused_pinv_train` (all off by default) put its two attention layers on the HIP kernels of moc_nystrom*.hip -- the no-grad passes, their
 pseudo-inverse, and the passes that want a gradient; `fused_ppeg` (off by default, a switch of its own) puts `pos_layer` on
-moc_ppeg.hip."""
+moc_ppeg.hip.  `TransMIL.attention_maps(data)` returns forward's logits and the class token's attention over the bag's
+patches in either layer, under the same switches (with `fused`, the rows come from moc_nystrom_rows.hip)."""
 from __future__ import annotations
 
 import numpy as np
@@ -110,6 +111,11 @@ class TransLayer(nn.Module):
 
     def forward(self, x):
         return x + self.attn(self.norm(x))
+
+    def forward_rows(self, x, rows):
+        """(forward(x), the wanted rows of the attention matrix) without a gradient: NystromAttention.forward_rows."""
+        out, attn = self.attn.forward_rows(self.norm(x), rows)
+        return x + out, attn
 
 
 class PPEGFused(torch.autograd.Function):
@@ -257,8 +263,8 @@ class TransMIL(nn.Module):
     def fused_ppeg(self, on: bool):
         self.pos_layer.fused = bool(on)
 
-    def _tokens(self, data):
-        """fc1, wrap-around padding to a square, class token, layer 1, PPEG, layer 2 (:236-266)."""
+    def _embed(self, data):
+        """fc1, wrap-around padding to a square, class token: (tokens [B, 1 + side^2, 512], side, n)."""
         if len(data.shape) == 2:
             data = data.unsqueeze(0)
         h = self._fc1(data.float())                                       # [B, n, 512]
@@ -266,9 +272,30 @@ class TransMIL(nn.Module):
         side = int(np.ceil(np.sqrt(H)))
         h = torch.cat([h, h[:, :side * side - H, :]], dim=1)              # pad with the first rows again
         h = torch.cat((self.cls_token.expand(h.shape[0], -1, -1).to(h.device), h), dim=1)
+        return h, side, data.shape[1]
+
+    def _tokens(self, data):
+        """_embed, layer 1, PPEG, layer 2 (:236-266)."""
+        h, side, n = self._embed(data)
         h = self.layer1(h)
         h = self.pos_layer(h, side, side)
-        return self.layer2(h), data.shape[1]
+        return self.layer2(h), n
+
+    def attention_maps(self, data):
+        """(logits, {"layer1": [8, n], "layer2": [8, n]}) under no_grad: _tokens' walk with each layer's attention asked
+        for the class token's row too (TransLayer.forward_rows), then forward's head.  `logits` is bit for bit
+        forward(data)[0] under no_grad in eval() with the same switches; a map is the class token's row of that layer's
+        Nystrom attention per head over the bag's n patches -- the class token's own column and the wrap-around rows that
+        square the bag are dropped -- as NystromAttention.forward_rows describes it: an approximation, not renormalised,
+        slightly negative in places.  All six switches keep their meaning; with `fused` the rows come from
+        moc_nystrom_rows.hip.  A batch of B bags gives [B, 8, n] maps."""
+        with torch.no_grad():
+            h, side, n = self._embed(data)
+            h, a1 = self.layer1.forward_rows(h, [0])
+            h = self.pos_layer(h, side, side)
+            h, a2 = self.layer2.forward_rows(h, [0])
+            logits = self._fc2(self.norm(h)[:, 0])
+            return logits, {"layer1": a1[..., 0, 1:n + 1], "layer2": a2[..., 0, 1:n + 1]}
 
     def forward_patch_level(self, data):
         h, n = self._tokens(data)

@@ -20,7 +20,10 @@ residual convolution in those passes too, through TokenValuesResidual, whose bac
 (the convolution's value and tap gradients), checked the same way (tests/test_gpu_nystrom_conv.py);
 `fused_pinv_train = True` on top of `fused` and `fused_train` takes the pseudo-inverse of those passes from LandmarkPinv, whose
 forward is moc_nystrom_pinv_iterates and whose backward is moc_nystrom_pinv_backward (csrc/moc_nystrom_pinv.hip), checked
-against float64 autograd of moore_penrose_iter_pinv (tests/test_gpu_nystrom_pinv_bwd.py)."""
+against float64 autograd of moore_penrose_iter_pinv (tests/test_gpu_nystrom_pinv_bwd.py).  `forward_rows(x, rows)` is the
+layer's answer to "where does this token look": the forward's result and the wanted rows of attn1 @ pinv @ attn3, on
+csrc/moc_nystrom_rows.hip where `fused` applies and on torch elsewhere, checked against a float64 evaluation of the whole
+matrix (tests/test_nystrom_rows_cpu.py, tests/test_gpu_nystrom_rows.py)."""
 from __future__ import annotations
 
 from math import ceil
@@ -241,6 +244,86 @@ class NystromAttention(nn.Module):
                 v = qkv[:, 2 * inner:].reshape(1, n_pad, h, -1).transpose(1, 2)     # [1, 8, n_pad, 64], a view
                 out = out + self.res_conv(v).transpose(1, 2).reshape(n_pad, inner)
         return self.to_out(out.unsqueeze(0))[:, -n:]
+
+    def forward_rows(self, x, rows):
+        """(out, attn) under no_grad: `out` is bit for bit what forward(x) returns under no_grad for the same module state,
+        `attn` [heads, len(rows), n] ([b, heads, len(rows), n] for a batch) the wanted rows of the layer's attention matrix
+        attn1 @ pinv @ attn3, columns restricted to the last n (the real tokens) and not renormalised.  `rows`: one or more
+        indices into the unpadded sequence, 0 <= r < n.  Neither result carries a gradient.
+
+        What a row is: a Nystrom row is an approximation of softmax(scale q k^T)'s.  It can be slightly negative (the
+        pseudo-inverse has entries of either sign).  Over all n_pad columns it sums to coef.sum(), coef = attn1[row] @ pinv,
+        about 1, because each row of attn3 sums to one; the front padding's zero keys take their share of that: a random
+        37-token sequence padded to 48 leaves 0.77 on the real tokens.  The residual convolution, which adds values without
+        any weights, is not part of it.
+
+        With `fused`, where forward_fused's kernels apply (_kernels_apply) and for at most 16 rows, the forward is
+        forward_fused's own (kernel A through engine.nystrom_landmark_values_lse, whose W is bit for bit the other entry's;
+        `fused_pinv` honoured), coef [8, R, 256] comes from the rows' own q in torch, and the rows from
+        engine.nystrom_attention_rows (csrc/moc_nystrom_rows.hip), one pass over the keys that reuses kernel A's
+        log-sum-exp: attn3, the [8, 256, n_pad] score matrix, is not formed.  Everywhere else -- the CPU, another layer
+        shape, more rows, a batch -- the same quantities come from torch for the wanted rows only, attn1[rows] @ pinv @
+        attn3, which forms attn3."""
+        with torch.no_grad():
+            n = x.shape[1]
+            rows = [int(r) for r in (rows.reshape(-1).tolist() if torch.is_tensor(rows) else rows)]
+            if len(rows) < 1 or min(rows) < 0 or max(rows) >= n:
+                raise ValueError(f"forward_rows: rows must be one or more indices in 0..{n - 1}, got {rows}")
+            idx = torch.tensor(rows, dtype=torch.long, device=x.device)
+            kernels = self.fused and self._kernels_apply(x, None, False)
+            if kernels and idx.numel() <= 16:
+                return self._rows_fused(x, idx)
+            out, attn = self._rows_torch(x, idx)
+            if kernels:                                   # more than 16 rows: the rows from torch, forward's own bits in `out`
+                out = self.forward_fused(x)
+            return out, attn
+
+    def _rows_fused(self, x, idx):
+        """forward_fused's dataflow with kernel A's log-sum-exp kept, then the rows (forward_rows)."""
+        from . import engine
+        n, h, m = x.shape[1], self.heads, self.num_landmarks
+        if n % m > 0:
+            x = F.pad(x, (0, 0, m - (n % m), 0), value=0)
+        qkv = self.to_qkv(x)[0]                           # [n_pad, 1536]
+        l, inner = qkv.shape[0] // m, qkv.shape[1] // 3
+        means = qkv[:, :2 * inner].reshape(m, l, 2 * inner).sum(dim=1) / l
+        q_l = (means[:, :inner] * self.scale).reshape(m, h, -1).transpose(0, 1).contiguous()                        # h m d
+        k_l = means[:, inner:].reshape(m, h, -1).transpose(0, 1).contiguous()
+        attn2 = (q_l @ k_l.transpose(-1, -2)).softmax(dim=-1)
+        if self.fused_pinv:
+            pinv = engine.nystrom_pinv(attn2, self.pinv_iterations)
+        else:
+            pinv = moore_penrose_iter_pinv(attn2.unsqueeze(0), self.pinv_iterations)[0]
+        W, lse = engine.nystrom_landmark_values_lse(qkv, q_l)
+        conv_w = self.res_conv.weight.reshape(h, -1) if self.residual else None
+        out = engine.nystrom_token_values(qkv, k_l, pinv @ W, conv_w, self.scale)
+        q_r = qkv[idx + (qkv.shape[0] - n), :inner].reshape(idx.numel(), h, -1).transpose(0, 1) * self.scale       # h R d
+        coef = (q_r @ k_l.transpose(-1, -2)).softmax(dim=-1) @ pinv                                                # h R m
+        attn = engine.nystrom_attention_rows(qkv, q_l, lse, coef)
+        return self.to_out(out.unsqueeze(0))[:, -n:], attn[..., -n:]
+
+    def _rows_torch(self, x, idx):
+        """_forward_torch's dataflow, operation for operation (`out` has its bits), and attn1[rows] @ pinv @ attn3."""
+        b, n, _ = x.shape
+        h, m = self.heads, self.num_landmarks
+        if n % m > 0:
+            x = F.pad(x, (0, 0, m - (n % m), 0), value=0)
+        q, k, v = self.to_qkv(x).chunk(3, dim=-1)
+        q, k, v = (t.reshape(b, t.shape[1], h, -1).transpose(1, 2) for t in (q, k, v))      # b h n d
+        q = q * self.scale
+        l = ceil(n / m)
+        q_l = q.reshape(b, h, -1, l, q.shape[-1]).sum(dim=3) / l
+        k_l = k.reshape(b, h, -1, l, k.shape[-1]).sum(dim=3) / l
+        attn1 = (q @ k_l.transpose(-1, -2)).softmax(dim=-1)
+        attn2 = (q_l @ k_l.transpose(-1, -2)).softmax(dim=-1)
+        attn3 = (q_l @ k.transpose(-1, -2)).softmax(dim=-1)
+        pinv = moore_penrose_iter_pinv(attn2, self.pinv_iterations)
+        out = (attn1 @ pinv) @ (attn3 @ v)
+        if self.residual:
+            out = out + self.res_conv(v)
+        out = out.transpose(1, 2).reshape(b, out.shape[2], -1)
+        attn = ((attn1[:, :, idx + (attn1.shape[2] - n)] @ pinv) @ attn3)[..., -n:]          # b h R n
+        return self.to_out(out)[:, -n:], attn[0] if b == 1 else attn
 
     def _forward_torch(self, x, mask=None, return_attn=False):
         assert mask is None and not return_attn, "the reference calls attn(x) only (models/model_mil.py:119)"

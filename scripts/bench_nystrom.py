@@ -22,7 +22,12 @@ moc_ppeg.hip (`PPEG.fused`), with the two entries alone against the bytes they m
 moore_penrose_iter_pinv, on the same attn2, moc_nystrom_pinv_iterates + moc_nystrom_pinv_backward with independent products
 sharing launches (the default) and with one product per launch.
 
-    python scripts/bench_nystrom.py [--n 15000] [--iters 30] [--json out.json] [--train]
+With --maps: moc_nystrom_attention_rows alone (R = 1 and R = 16) against its two bounds, then TransMIL.attention_maps on
+the same bag with `fused` + `fused_pinv` + `fused_ppeg` against the same call with `fused = False` (the torch rows path, which
+forms attn3, the [8, 256, n_pad] score matrix), each with its peak memory, and the plain no-grad forward under the same three
+switches, which is what the maps are an addition to.
+
+    python scripts/bench_nystrom.py [--n 15000] [--iters 30] [--json out.json] [--train | --maps]
     rocprofv3 --kernel-trace --stats ... -- python scripts/bench_nystrom.py --trace-layers 8
 """
 import argparse
@@ -269,8 +274,57 @@ def train(a, dev, g, bag, model, attn, out):
     ppeg_entries(ppeg, x, side, cot, out, a.iters, a.warmup)
 
 
+def maps(a, dev, g, bag, model, attn, out):
+    side = math.ceil(math.sqrt(a.n))
+    n_tok = side * side + 1
+    n_pad = -(-n_tok // M) * M
+    out.update(tokens=n_tok, n_pad=n_pad)
+    with torch.no_grad():
+        x = torch.nn.functional.layer_norm(torch.randn(1, n_tok, 512, generator=g), (512,)).to(dev)
+        qkv = attn.to_qkv(torch.nn.functional.pad(x, (0, 0, n_pad - n_tok, 0)))[0].contiguous()
+        l = n_pad // M
+        q_l = ((qkv[:, :512] * attn.scale).reshape(M, l, H, D).sum(1) / l).transpose(0, 1).contiguous()
+        k_l = (qkv[:, 512:1024].reshape(M, l, H, D).sum(1) / l).transpose(0, 1).contiguous()
+        pinv = moore_penrose_iter_pinv((q_l @ k_l.transpose(-1, -2)).softmax(dim=-1).unsqueeze(0), attn.pinv_iterations)[0]
+        _, lse = engine.nystrom_landmark_values_lse(qkv, q_l)
+        # the entry alone.  Bytes: qkv's k columns and the rows it writes; products: the [256, n] x 64 scores per head and the
+        # second product at the 16 rows of its MFMA tile, whatever R is
+        for R in (1, 16):
+            q_r = qkv[n_pad - n_tok:n_pad - n_tok + R, :512].reshape(R, H, D).transpose(0, 1) * attn.scale
+            coef = ((q_r @ k_l.transpose(-1, -2)).softmax(dim=-1) @ pinv).contiguous()
+            out[f"attention_rows_R{R}"] = kernel(f"moc_nystrom_attention_rows R={R}",
+                                                 lambda: engine.nystrom_attention_rows(qkv, q_l, lse, coef),
+                                                 n_pad * 512 * 4 + H * R * n_pad * 4, 2.0 * H * M * n_pad * (D + 16), a.iters, a.warmup)
+    model.fused_pinv = model.fused_ppeg = True
+    r = {}
+    for key, fused, fn in (("torch", False, lambda: model.attention_maps(bag)), ("fused", True, lambda: model.attention_maps(bag)),
+                           ("forward", True, lambda: model(bag))):
+        model.fused = fused
+        with torch.no_grad():
+            r[key] = times_us(fn, a.iters, a.warmup)
+            torch.cuda.synchronize()
+            torch.cuda.empty_cache()
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            fn()
+            torch.cuda.synchronize()
+            r[key]["peak_bytes"] = torch.cuda.max_memory_allocated() - base
+    model.fused = model.fused_pinv = model.fused_ppeg = False
+    t, f, p = r["torch"], r["fused"], r["forward"]
+    r["fused_is_faster"] = f["median_us"] < t["min_us"]
+    r["over_forward_us"] = f["median_us"] - p["median_us"]
+    out["attention_maps"] = r
+    print(f"{'attention_maps ' + str(a.n) + ' x 512':24s}: torch rows median {t['median_us']:9.1f} us (min {t['min_us']:9.1f}) peak "
+          f"{t['peak_bytes'] / 2**20:8.1f} MiB   fused median {f['median_us']:9.1f} us (min {f['min_us']:9.1f}) peak "
+          f"{f['peak_bytes'] / 2**20:8.1f} MiB   {'fused faster' if r['fused_is_faster'] else 'NOT faster'} "
+          f"(x{t['median_us'] / f['median_us']:.2f} on the medians, x{t['peak_bytes'] / max(f['peak_bytes'], 1):.2f} on the peaks)")
+    print(f"{'':24s}  the plain no-grad forward, same switches: median {p['median_us']:9.1f} us (min {p['min_us']:9.1f}) peak "
+          f"{p['peak_bytes'] / 2**20:8.1f} MiB: the maps cost {r['over_forward_us']:.1f} us over it on the medians")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--maps", action="store_true", help="time moc_nystrom_attention_rows and TransMIL.attention_maps, fused against the torch rows path")
     ap.add_argument("--train", action="store_true", help="time forward + backward: the torch path against fused_train, + fused_conv and + fused_pinv_train")
     ap.add_argument("--n", type=int, default=15000)
     ap.add_argument("--iters", type=int, default=30)
@@ -287,8 +341,8 @@ def main():
     model = TransMIL(n_classes=2, size_arg="conch").to(dev).eval()
     attn = model.layer1.attn
     out = {"n": a.n}
-    if a.train:
-        train(a, dev, g, bag, model, attn, out)
+    if a.train or a.maps:
+        (train if a.train else maps)(a, dev, g, bag, model, attn, out)
         if a.json:
             os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
             with open(a.json, "w") as f:
